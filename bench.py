@@ -229,6 +229,69 @@ def cpu_baseline(params, cam, n_tiles_sample, n_gauss_sample, dbg, W, H, full=Fa
                       f"{t_pre * ns / N + t_bin + t_tiles + t_loss + t_adam:.1f} s"}
 
 
+DUMP_BUDGET_BYTES = 60 * 2**20     # --dump-outputs: array data; with the .npy headers and manifest.json under 64 MB
+DUMP_GAUSSIAN_ROWS = 65_536         # per-Gaussian arrays keep this many rows (the same seeded rows in every array)
+
+
+def dump_outputs(out_dir, per_gaussian, other, n_gaussians, seed=0):
+    """--dump-outputs: the arrays of the last timed step as out_dir/<name>.npy (float32; float64 stays float64) plus
+    manifest.json (shape before sampling, how each array was sampled).  At most DUMP_BUDGET_BYTES in all: per-Gaussian
+    arrays keep the same DUMP_GAUSSIAN_ROWS rows (sorted torch.randperm(N) of a seeded generator); the other arrays share
+    what is left, smallest first, and one larger than its share keeps a seeded sample of its flattened elements.  The
+    samples depend only on the shapes and the seed, so two builds run with the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = None
+    if n_gaussians > DUMP_GAUSSIAN_ROWS:
+        rows = torch.randperm(n_gaussians, generator=torch.Generator().manual_seed(seed))[:DUMP_GAUSSIAN_ROWS].sort().values
+    host, manifest = {}, {}
+
+    def to_host(t):
+        t = t.detach()
+        return (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+
+    for name, t in per_gaussian.items():
+        if t.shape[0] != n_gaussians:
+            raise ValueError(f"{name}: leading dimension {t.shape[0]}, expected {n_gaussians}")
+        manifest[name] = {"shape": list(t.shape), "sample": None if rows is None else
+                          f"rows: {DUMP_GAUSSIAN_ROWS} of {n_gaussians} (sorted randperm, seed {seed})"}
+        host[name] = to_host(t if rows is None else t[rows.to(t.device)])
+    left = DUMP_BUDGET_BYTES - sum(a.nbytes for a in host.values())
+    other = {k: to_host(t) for k, t in other.items()}
+    for i, name in enumerate(sorted(other, key=lambda k: other[k].nbytes)):
+        a = other[name]
+        share = left // (len(other) - i)
+        manifest[name] = {"shape": list(a.shape), "sample": None}
+        if a.nbytes > share:
+            k = share // a.itemsize
+            idx = torch.randperm(a.size, generator=torch.Generator().manual_seed(seed))[:k].sort().values.numpy()
+            a = a.reshape(-1)[idx]
+            manifest[name]["sample"] = f"flattened elements: {k} of {other[name].size} (sorted randperm, seed {seed})"
+        host[name] = a
+        left -= a.nbytes
+    assert sum(a.nbytes for a in host.values()) <= DUMP_BUDGET_BYTES
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        manifest[name]["dtype"] = str(a.dtype)
+    with open(os.path.join(out_dir, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+    log(f"wrote {len(host)} arrays ({sum(a.nbytes for a in host.values()) / 2**20:.1f} MB) to {out_dir}")
+
+
+def step_outputs(model, pkg, losses):
+    """What a caller of one training step holds afterwards: the updated parameters (raw tensors, as the optimiser sees
+    them), the render package of the step (image, allmap / derived maps, radii, the screen-space gradient) and its losses."""
+    per_g = {"xyz": model._xyz, "features_dc": model._features_dc, "features_rest": model._features_rest,
+             "opacity": model._opacity, "scaling": model._scaling, "rotation": model._rotation, "radii": pkg["radii"]}
+    vs = pkg["viewspace_points"].grad
+    if vs is not None:
+        per_g["viewspace_points_grad"] = vs
+    other = {k: v for k, v in pkg.items()
+             if torch.is_tensor(v) and k not in ("radii", "viewspace_points", "visibility_filter")}
+    other.update({f"loss_{k}": v for k, v in losses.items() if torch.is_tensor(v)})
+    return per_g, other
+
+
 def wide_payload_bench(args, preset, N, W, H, radius_px):
     """BASELINE.json config 5 ("extra per-Gaussian feature channels rendered / backpropped"; build-defined: SURVEY section 0
     fact 5): the operator with colors_precomp [N,C] -- forward + backward through the C-ABI, per-kernel times from the
@@ -258,8 +321,10 @@ def wide_payload_bench(args, preset, N, W, H, radius_px):
         c, r, am = rast(means3D=ins["means3D"], means2D=m2d, colors_precomp=col, opacities=ins["opacities"],
                         scales=ins["scales"], rotations=ins["rotations"])
         ((c * wc).sum() + (am * wa).sum()).backward()
+        grads = {f"grad_{k}": t.grad for k, t in (("colors", col), ("means2D", m2d), *ins.items()) if t.grad is not None}
         for t in (col, m2d, *ins.values()):
             t.grad = None
+        return c, r, am, grads
     for _ in range(max(args.warmup, 2)):
         step()
     _t.cuda.synchronize()
@@ -267,11 +332,16 @@ def wide_payload_bench(args, preset, N, W, H, radius_px):
     _lib.profile_reset()
     _lib.profile_enable(True)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()
     _t.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     _lib.profile_enable(False)
+    if args.dump_outputs:
+        c, r, am, grads = last
+        dump_outputs(args.dump_outputs, {"radii": r, **grads}, {"color": c, "allmap": am}, N)
+    del last
     prof = {k: round(ms / max(n, 1), 4) for k, (ms, n) in _lib.profile_read().items() if n}
     out = {"metric": f"rasterizer fwd+bwd iters/sec @{N} Gaussians {W}x{H}, {C}-channel payload", "value": args.steps / elapsed,
            "unit": "iters/s", "n_gpus": 1, "steps": args.steps, "warmup": max(args.warmup, 2), "ms_per_step": elapsed / args.steps * 1e3,
@@ -322,7 +392,13 @@ def main():
     ap.add_argument("--channels", type=int, default=3,
                     help="wide per-pixel payload (BASELINE.json config 5): time the operator's forward + backward with "
                          "colors_precomp [N,C], C = 4..64 (multiple of 4), on the chosen preset instead of the training step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (updated parameters, render package, "
+                         "losses; a fixed seeded sample where large, at most 64 MB in all) as DIR/<name>.npy + DIR/manifest.json")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    torch.manual_seed(0)      # the scene, views and target have their own seeded generators; this pins anything else
     preset = PRESETS[args.preset]
     N = args.gaussians or preset["gaussians"]
     W, H = args.width or preset["width"], args.height or preset["height"]
@@ -430,7 +506,7 @@ def main():
     # (gsr_adam_sh_factored_next), the next forward skips the SH colour pass.  GSR_BENCH_COLOR_CACHE=0: off (A/B aid)
     next_cam = cam if os.environ.get("GSR_BENCH_COLOR_CACHE", "1") != "0" else None
     def step(i):
-        training_step(model, cam, gt, opt, pipe, bg, base_iter + i, view_parallel=vp, next_cam=next_cam)
+        return training_step(model, cam, gt, opt, pipe, bg, base_iter + i, view_parallel=vp, next_cam=next_cam)
 
     if dropin:
         # One iteration of the reference's loop (train.py:93-216) around the drop-in operator: render() with torch
@@ -457,6 +533,7 @@ def main():
             ema[0] = 0.4 * loss.item() + 0.6 * ema[0]
             model.optimizer.step()
             model.optimizer.zero_grad(set_to_none=True)
+            return pkg, {"l1": Ll1.detach(), "loss": loss.detach(), "total": total.detach()}
 
     # Python's cyclic garbage collector runs when allocation counts cross a threshold, i.e. at arbitrary steps, and a full
     # collection stalls the host for a millisecond or more -- in a 20-step timed region that is several per cent of noise
@@ -509,8 +586,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i in range(args.steps):
+    for i in range(args.steps - 1):
         step(args.warmup + i)
+    last = step(args.warmup + args.steps - 1)     # what the last timed step returns: --dump-outputs
     torch.cuda.synchronize()
     local_elapsed = time.perf_counter() - t0
     if world > 1:
@@ -520,6 +598,9 @@ def main():
     _lib.profile_enable(False)
     prof = _lib.profile_read()
     log(f"timed {args.steps} steps in {elapsed:.3f}s")
+    if args.dump_outputs and rank == 0:     # before any later step reuses the buffers of this one
+        dump_outputs(args.dump_outputs, *step_outputs(model, *last), model._xyz.shape[0])
+    del last
     per_rank_ms = [local_elapsed / args.steps * 1e3]
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)

@@ -42,6 +42,30 @@ def test_default_line_carries_the_contract_fields(gpu_device):
     assert full["value"] > 0 and full["steps"] >= 10
 
 
+def test_dump_outputs_of_the_last_timed_step_repeat(gpu_device, tmp_path):
+    """--dump-outputs: the last timed step's parameters, render package and losses, within 64 MB; two runs with the same
+    arguments write the same arrays bit for bit, and --steps sets the number of timed steps."""
+    import numpy as np
+    runs = []
+    for d in ("a", "b"):
+        line = _bench("--no-cpu-baseline", "--dump-outputs", str(tmp_path / d))
+        assert line["steps"] == 6 and abs(line["value"] * line["ms_per_step"] - 1000.0) < 1.0
+        runs.append({p.stem: np.load(p) for p in sorted((tmp_path / d).glob("*.npy"))})
+    a, b = runs
+    for k in ("xyz", "features_dc", "features_rest", "opacity", "scaling", "rotation", "radii", "viewspace_points_grad",
+              "render", "loss_total"):
+        assert k in a, k
+    assert a["xyz"].shape == (30000, 3) and a["render"].shape == (3, 272, 480)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64_000_000
+    assert all(x.dtype in (np.float32, np.float64) and np.isfinite(x).all() for x in a.values())
+    assert sorted(a) == sorted(b)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    seven = _bench("--no-cpu-baseline", "--steps", "7", "--dump-outputs", str(tmp_path / "c"))
+    assert seven["steps"] == 7
+    assert not np.array_equal(np.load(tmp_path / "c" / "xyz.npy"), a["xyz"])    # one more Adam step moved the parameters
+
+
 def test_dropin_mode_and_evaluation_flags(gpu_device):
     drop = _bench("--no-cpu-baseline", "--mode", "dropin")
     assert drop["config"]["mode"].startswith("dropin") and drop["value"] > 0 and drop["with_all_seven_allmap_channels"] is None

@@ -131,6 +131,37 @@ def test_schedule_script_presets_match_bench():
         assert FS.PRESETS[name] == (p["gaussians"], p["width"], p["height"], p["radius_px"])
 
 
+def test_bench_dump_outputs_budget_and_fixed_samples(tmp_path):
+    """bench.py --dump-outputs: per-Gaussian arrays keep the same seeded rows, larger arrays a seeded sample of their
+    elements, everything together fits the budget, and the same inputs give the same files."""
+    import json
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 200_000
+    g = torch.Generator().manual_seed(3)
+    per_g = {"xyz": torch.randn(n, 3, generator=g), "features_rest": torch.randn(n, 15, 3, generator=g),
+             "radii": torch.randint(0, 9, (n,), generator=g, dtype=torch.int32)}
+    other = {"render": torch.rand(3, 1080, 1920, generator=g), "allmap": torch.rand(7, 1080, 1920, generator=g),
+             "loss_total": torch.tensor(0.25, dtype=torch.float64)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), per_g, other, n)
+    names = sorted(list(per_g) + list(other))
+    assert sorted(p.name for p in (tmp_path / "a").glob("*.npy")) == [f"{k}.npy" for k in names]
+    loaded = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in names}
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64_000_000
+    assert all(loaded[k].dtype == np.float32 for k in names if k != "loss_total") and loaded["loss_total"].dtype == np.float64
+    man = json.load(open(tmp_path / "a" / "manifest.json"))
+    assert man["render"]["shape"] == [3, 1080, 1920] and man["loss_total"]["sample"] is None
+    rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:bench.DUMP_GAUSSIAN_ROWS].sort().values
+    assert np.array_equal(loaded["xyz"], per_g["xyz"][rows].numpy())
+    assert np.array_equal(loaded["radii"], per_g["radii"][rows].float().numpy())
+    assert loaded["features_rest"].shape == (bench.DUMP_GAUSSIAN_ROWS, 15, 3)
+    assert np.all(np.isin(loaded["allmap"], other["allmap"].numpy()))          # a sample of the elements, not a recomputation
+    for k in names:
+        assert np.array_equal(loaded[k], np.load(tmp_path / "b" / f"{k}.npy")), k
+
+
 def test_loss_utils_refuses_what_it_does_not_implement():
     """gaussmart_amd.loss_utils (the reference's l1_loss / ssim signatures on the fused kernel): argument checks run before any
     device work, and a CPU tensor is refused -- there is no CPU path behind these names."""
