@@ -16,7 +16,7 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSR_LIB_PATH: developer aid for same-box A/B runs of two builds of the library (scripts/ab_builds.sh)
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "lib", "libgsr_hip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_SCRATCH, GSR_BUF_SCRATCH2 = range(5)
 GSR_BUF_SYNC_SH = 100     # not a buffer: "the SH colour pass is about to be enqueued" (GSR_FLAG_DEFER_COLOR)
@@ -73,6 +73,14 @@ class GsrRowScanJob(C.Structure):
     """include/gsr.h: the scan of the backward's row counts, offered to kernels between the forward and the backward."""
     _fields_ = [("counts", C.c_void_p), ("slot_off", C.c_void_p), ("workspace", C.c_void_p), ("n", C.c_int64),
                 ("stage", C.c_int32)]
+
+
+class GsrTsdfVolume(C.Structure):
+    """include/gsr.h: a block-sparse TSDF volume in caller-owned device memory (gaussmart_amd/tsdf.py)."""
+    _fields_ = [("voxel_size", C.c_float), ("sdf_trunc", C.c_float),
+                ("block_lo", C.c_int32 * 3), ("block_hi", C.c_int32 * 3),
+                ("block_index", C.c_void_p), ("pool", C.c_void_p), ("pool_blocks", C.c_int64), ("n_alloc", C.c_int64),
+                ("n_views", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t)
@@ -139,7 +147,7 @@ def lib():
         L.gsr_regularizer_backward.restype = C.c_int32
         L.gsr_regularizer_backward.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_float,
                                                C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-        # (every symbol below is part of ABI 5 / 6: a library without one of them fails the version check above, so there are
+        # (every symbol below is part of ABI 5 / 6 / 7: a library without one of them fails the version check above, so there are
         # no per-symbol guards)
         L.gsr_regularizer_backward_partials.restype = C.c_int32
         L.gsr_regularizer_backward_partials.argtypes = L.gsr_regularizer_backward.argtypes[:-1] + [C.c_void_p, C.c_void_p]
@@ -190,6 +198,21 @@ def lib():
                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsr_densify_stats.restype = C.c_int32
         L.gsr_densify_stats.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        V = C.POINTER(GsrTsdfVolume)
+        L.gsr_tsdf_sizes.restype = C.c_int32
+        L.gsr_tsdf_sizes.argtypes = [V, C.POINTER(C.c_int64), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.gsr_tsdf_touch.restype = C.c_int32
+        L.gsr_tsdf_touch.argtypes = [V, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                     C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int64), C.c_void_p]
+        L.gsr_tsdf_integrate.restype = C.c_int32
+        L.gsr_tsdf_integrate.argtypes = [V, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                         C.POINTER(C.c_float), C.c_float, C.c_int64, C.c_void_p]
+        L.gsr_mcubes_workspace_bytes.restype = C.c_size_t
+        L.gsr_mcubes_workspace_bytes.argtypes = [C.c_int64]
+        L.gsr_mcubes_count.restype = C.c_int32
+        L.gsr_mcubes_count.argtypes = [V, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]
+        L.gsr_mcubes_emit.restype = C.c_int32
+        L.gsr_mcubes_emit.argtypes = [V, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]
         L.gsr_profile_reset.restype = None

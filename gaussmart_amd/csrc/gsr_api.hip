@@ -164,6 +164,8 @@ static unsigned long long* pinned_words(size_t words) {
     return buf;
 }
 static uint32_t* pinned_counter() { return reinterpret_cast<uint32_t*>(pinned_words(1)); }
+// the same slot for the one read-back of the TSDF / marching-cubes entry points (tsdf.hip, mcubes.hip)
+unsigned long long* gsr_pinned_words(size_t words) { return pinned_words(words); }
 
 // above this many bytes of worst-case gradient rows the backward reads the exact row count back (one host wait)
 static size_t exact_rows_threshold() {

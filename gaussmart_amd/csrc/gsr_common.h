@@ -18,6 +18,8 @@ void gsr_set_error(const char* fmt, ...);
         }                                                                           \
     } while (0)
 #define GSR_LAUNCH_CHECK() GSR_HIP_CHECK(hipGetLastError())
+// pinned host words of the calling thread for a synchronous device -> host read (gsr_api.hip); NULL if allocation fails
+unsigned long long* gsr_pinned_words(size_t words);
 
 // ---------------------------------------------------------------- profiler hooks
 enum GsrKernelId {

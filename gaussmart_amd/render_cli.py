@@ -1,0 +1,92 @@
+"""Command-line rendering and mesh export, the counterpart of the reference's render.py (bounded TSDF path):
+
+    python -m gaussmart_amd.render_cli -s <scene> -m <model dir> [--iteration -1] [--skip_train] [--skip_test]
+        [--skip_mesh] [--voxel_size V] [--depth_trunc D] [--sdf_trunc S] [--num_cluster 50] [--mesh_res 1024]
+        [--depth_ratio R]
+
+Writes MODEL/{train,test}/ours_<it>/{renders,gt,vis} and MODEL/train/ours_<it>/fuse.ply, fuse_post.ply (what the reference's
+scripts/dtu_eval_mesh.py reads).  --unbounded and --render_path are not supported.
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+from .gaussian_model import GaussianModel
+from .gaussian_renderer import render
+from .mesh import GaussianExtractor, post_process_mesh
+from .params import PipelineParams
+from .scene_io import Scene
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--source_path", "-s", required=True)
+    ap.add_argument("--model_path", "-m", required=True)
+    ap.add_argument("--images", "-i", default=None)
+    ap.add_argument("--resolution", "-r", type=int, default=-1)
+    ap.add_argument("--white_background", "-w", action="store_true")
+    ap.add_argument("--eval", action="store_true")
+    ap.add_argument("--sh_degree", type=int, default=3)
+    ap.add_argument("--depth_ratio", type=float, default=0.0)
+    ap.add_argument("--iteration", default=-1, type=int)
+    ap.add_argument("--skip_train", action="store_true")
+    ap.add_argument("--skip_test", action="store_true")
+    ap.add_argument("--skip_mesh", action="store_true")
+    ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--render_path", action="store_true")
+    ap.add_argument("--voxel_size", default=-1.0, type=float, help="Mesh: voxel size for TSDF")
+    ap.add_argument("--depth_trunc", default=-1.0, type=float, help="Mesh: Max depth range for TSDF")
+    ap.add_argument("--sdf_trunc", default=-1.0, type=float, help="Mesh: truncation value for TSDF")
+    ap.add_argument("--num_cluster", default=50, type=int, help="Mesh: number of connected clusters to export")
+    ap.add_argument("--unbounded", action="store_true", help="Mesh: using unbounded mode for meshing (not supported)")
+    ap.add_argument("--mesh_res", default=1024, type=int, help="Mesh: resolution for unbounded mesh extraction")
+    args = ap.parse_args(argv)
+    if args.unbounded:
+        sys.exit("render_cli: --unbounded is not supported (only the bounded TSDF mesh path is implemented)")
+    if args.render_path:
+        sys.exit("render_cli: --render_path (trajectory videos) is not supported")
+    print("Rendering " + args.model_path)
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    pipe = PipelineParams(depth_ratio=args.depth_ratio)
+    gaussians = GaussianModel(args.sh_degree, device=dev)
+    scene = Scene(args.source_path, gaussians, model_path=args.model_path, load_iteration=args.iteration,
+                  images=args.images, eval=args.eval, white_background=args.white_background, resolution=args.resolution,
+                  data_device=dev, shuffle=False)
+    bg_color = [1, 1, 1] if args.white_background else [0, 0, 0]
+    train_dir = os.path.join(args.model_path, "train", f"ours_{scene.loaded_iter}")
+    test_dir = os.path.join(args.model_path, "test", f"ours_{scene.loaded_iter}")
+    ex = GaussianExtractor(gaussians, render, pipe, bg_color=bg_color)
+
+    if not args.skip_train:
+        print("export training images ...")
+        os.makedirs(train_dir, exist_ok=True)
+        ex.reconstruction(scene.getTrainCameras())
+        ex.export_image(train_dir)
+    if not args.skip_test and len(scene.getTestCameras()) > 0:
+        print("export rendered testing images ...")
+        os.makedirs(test_dir, exist_ok=True)
+        ex.reconstruction(scene.getTestCameras())
+        ex.export_image(test_dir)
+
+    if not args.skip_mesh:
+        print("export mesh ...")
+        os.makedirs(train_dir, exist_ok=True)
+        ex.gaussians.active_sh_degree = 0   # diffuse texture only
+        ex.reconstruction(scene.getTrainCameras())
+        name = "fuse.ply"
+        depth_trunc = (ex.radius * 2.0) if args.depth_trunc < 0 else args.depth_trunc
+        voxel_size = (depth_trunc / args.mesh_res) if args.voxel_size < 0 else args.voxel_size
+        sdf_trunc = 5.0 * voxel_size if args.sdf_trunc < 0 else args.sdf_trunc
+        mesh = ex.extract_mesh_bounded(voxel_size=voxel_size, sdf_trunc=sdf_trunc, depth_trunc=depth_trunc)
+        mesh.write_ply(os.path.join(train_dir, name))
+        print("mesh saved at {}".format(os.path.join(train_dir, name)))
+        mesh_post = post_process_mesh(mesh, cluster_to_keep=args.num_cluster)
+        mesh_post.write_ply(os.path.join(train_dir, name.replace(".ply", "_post.ply")))
+        print("mesh post processed saved at {}".format(os.path.join(train_dir, name.replace(".ply", "_post.ply"))))
+
+
+if __name__ == "__main__":
+    main()

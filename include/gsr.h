@@ -34,8 +34,9 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 6   /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
-                                6: gsr_surface_maps_forward / _backward */
+#define GSR_ABI_VERSION 7   /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
+                                6: gsr_surface_maps_forward / _backward;
+                                7: TSDF fusion and marching cubes (GsrTsdfVolume, gsr_tsdf_*, gsr_mcubes_*) */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -387,6 +388,84 @@ int32_t gsr_compact_apply(int32_t count, const void* const* src, void* const* ds
  * ||grad2d[i,:]||; denom[i] += 1.  grad2d = means2D.grad [N,3]; the three state arrays are device f32 [N]. */
 int32_t gsr_densify_stats(int32_t n, const int32_t* radii, const float* grad2d, float* max_radii2D,
                           float* xyz_gradient_accum, float* denom, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- mesh export: TSDF fusion + marching cubes
+ * The bounded mesh path of the reference (utils/mesh_utils.py:125-170, Open3D's ScalableTSDFVolume with RGB8 colour, then
+ * its marching cubes), as kernels (tsdf.hip, mcubes.hip).
+ *
+ * Volume: voxel g (integer, world-anchored) has its centre at (g + 0.5) * voxel_size; voxels are grouped in 16^3 blocks,
+ * block b holds voxels [16 b, 16 b + 16).  A dense int32 block-index grid covers the block AABB [block_lo, block_hi)
+ * (x fastest); an entry is -1 or a slot of the voxel pool.  The pool is SoA, f32 [5][pool_blocks][4096]: tsdf, weight,
+ * r, g, b (colour on the 0..255 scale); voxel (x, y, z) of a block is entry x + 16 (y + 16 z).  A new block starts at 0
+ * everywhere: the caller zero-fills pool memory it adds.  Slots are handed out in block-grid order by a scan over each view's
+ * new blocks (no atomic counter), so the pool layout and the order of the emitted mesh are the same on every run.
+ *
+ * Recalled Open3D rules (from memory of Open3D's ScalableTSDFVolume / RGBD integration, not read: neither its source nor a
+ * build is available to this project -- like the three recalled quirks of the rasterizer above), each kept in one named
+ * place of tsdf.hip / mcubes.hip:
+ *   TSDF_TOUCH_STRIDE 4          blocks are allocated from the depth pixels on a stride-4 lattice, each marking the blocks
+ *                                that overlap [p - sdf_trunc, p + sdf_trunc] (p: the pixel's back-projected point)
+ *   TSDF_PIXEL_ROUND 0.5         a voxel reads pixel ((int)(fx x/z + cx + 0.5), (int)(fy y/z + cy + 0.5))
+ *   TSDF_BORDER 1e-4             ... only when 1e-4 <= u_f < W - 1e-4 (same for v_f)
+ *   tsdf_ray_multiplier()        sdf = (d - z) * sqrt(1 + ((u-cx)/fx)^2 + ((v-cy)/fy)^2)  (distance along the ray)
+ *   MC_SKIP_WEIGHT0              a cube with a corner of weight 0 (or in an unallocated block) produces nothing
+ * A depth pixel is valid when 0 < d <= depth_trunc and (mask == NULL or mask != 0).
+ *
+ * Host arrays: intrinsics_host = {fx, fy, cx, cy}; w2c_host = row-major 4x4 world-to-camera (column-vector convention,
+ * p_cam = w2c p_world: the TRANSPOSE of the rasterizer's viewmatrix).  depth f32 [H,W], rgb f32 [3,H,W] (clipped to
+ * [0,1] and truncated to uint8 inside), mask uint8 [H,W] or NULL. */
+#define GSR_TSDF_BLOCK_CAP (1LL << 28)   /* most blocks in a grid (the grid alone is 1 GiB at the cap) */
+
+typedef struct GsrTsdfVolume {
+    float voxel_size, sdf_trunc;
+    int32_t block_lo[3], block_hi[3];   /* block AABB, hi exclusive; hi == lo on an axis: an empty grid */
+    int32_t* block_index;               /* device int32 [n_blocks]; the caller fills it with -1 before the first touch */
+    float* pool;                        /* device f32 [5][pool_blocks][4096] */
+    int64_t pool_blocks;                /* capacity of the pool (slots); integrate needs pool_blocks >= n_alloc */
+    int64_t n_alloc;                    /* slots in use; advanced by gsr_tsdf_touch */
+    int32_t n_views;                    /* touches so far; advanced by gsr_tsdf_touch */
+    void* workspace;                    /* device, gsr_tsdf_sizes' bytes; ZERO-filled by the caller before the first touch */
+    size_t workspace_bytes;
+} GsrTsdfVolume;
+
+/* Checks voxel_size, sdf_trunc and the block AABB (GSR_E_INVALID; over GSR_TSDF_BLOCK_CAP blocks: GSR_E_UNSUPPORTED, with a
+ * message that names voxel_size and depth_trunc) and gives the grid's block count and the workspace size.  Host only.
+ * slot_block_offset (may be NULL): byte offset in the workspace of the slot -> linear block id map, int32 [n_blocks] in slot
+ * order.  A caller that loads a volume itself (no touch) fills block_index, that map and n_alloc consistently. */
+int32_t gsr_tsdf_sizes(const GsrTsdfVolume* vol, int64_t* n_blocks, size_t* workspace_bytes, size_t* slot_block_offset);
+
+/* One view, first half: marks the blocks its valid depth touches (pixels on the stride-4 lattice), gives the new ones
+ * pool slots and lists this view's touched blocks in the workspace.  ONE stream synchronisation (reads back the counts):
+ * on return vol->n_alloc and vol->n_views are advanced and *n_touched is the list's length; the caller then grows the pool
+ * to n_alloc slots (zero-filled) before gsr_tsdf_integrate.  A touched block outside the AABB fails the call with
+ * GSR_E_INVALID and changes nothing (no block is dropped silently).  An empty grid launches nothing. */
+int32_t gsr_tsdf_touch(GsrTsdfVolume* vol, const float* depth, const uint8_t* mask, int32_t H, int32_t W,
+                       const float* intrinsics_host, const float* w2c_host, float depth_trunc, int64_t* n_touched,
+                       gsr_stream_t stream);
+
+/* One view, second half: updates every voxel of the n_touched blocks listed by the preceding gsr_tsdf_touch (same view,
+ * same arguments).  Per voxel, z = camera depth of the centre (skip if <= 0), the pixel is found as above, skip if invalid,
+ * sdf as above, skip unless sdf > -sdf_trunc; t = min(1, sdf / sdf_trunc); tsdf = (tsdf w + t) / (w + 1), colour likewise
+ * with rgb8, w += 1.  One thread per voxel, no atomics: bitwise reproducible. */
+int32_t gsr_tsdf_integrate(const GsrTsdfVolume* vol, const float* depth, const uint8_t* mask, const float* rgb, int32_t H,
+                           int32_t W, const float* intrinsics_host, const float* w2c_host, float depth_trunc,
+                           int64_t n_touched, gsr_stream_t stream);
+
+/* Marching cubes over the allocated blocks.  Cube (x,y,z) has its corners at voxels +{0,1}^3, read across block borders
+ * through the grid; case bit i set when tsdf_i < 0 (gaussmart_amd/csrc/mc_tables.h, generated by scripts/gen_mc_tables.py).
+ * Each voxel owns its +x, +y, +z edges: one vertex per crossing edge that a produced cube uses (welded, none unreferenced),
+ * at p0 + |f0| / (|f0| + |f1|) voxel_size along the edge, colour (c0 |f1| + c1 |f0|) / (|f0| + |f1|) / 255.  Triangle normals
+ * (v1-v0)x(v2-v0) point toward positive tsdf.
+ *   gsr_mcubes_count: cube codes and per-block counts, scans, and ONE stream synchronisation to read the two totals;
+ *   gsr_mcubes_emit : vertices f32 [n_verts,3], colours f32 [n_verts,3], triangles int32 [n_tris,3] (same workspace,
+ *                     nothing else enqueued on it in between).
+ * No allocated block: nothing is launched and both totals are 0.  Totals above 2^31 - 1 vertices (int32 indices) or 2^32 - 1
+ * triangles (32-bit offsets): GSR_E_UNSUPPORTED from gsr_mcubes_count, and gsr_mcubes_emit writes nothing. */
+size_t gsr_mcubes_workspace_bytes(int64_t n_alloc);
+int32_t gsr_mcubes_count(const GsrTsdfVolume* vol, void* ws, size_t ws_bytes, int64_t* n_verts, int64_t* n_tris,
+                         gsr_stream_t stream);
+int32_t gsr_mcubes_emit(const GsrTsdfVolume* vol, void* ws, size_t ws_bytes, float* verts, float* colors, int32_t* tris,
+                        gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only

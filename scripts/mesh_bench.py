@@ -1,0 +1,92 @@
+"""Developer probe: time each part of the bounded mesh export (gaussmart_amd.mesh) on a unit-sphere surfel scene at the DTU
+flags (--voxel_size 0.004 --sdf_trunc 0.016 --depth_trunc 3.0, depth_ratio 1): rendering the views, the block AABB,
+TSDF touch + integrate, marching cubes and post-processing.  Prints one JSON line.
+
+    python scripts/mesh_bench.py [--surfels 300000] [--views 49] [--width 1600] [--height 1200]
+"""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def fib(n):
+    i = np.arange(n) + 0.5
+    phi = np.arccos(1 - 2 * i / n)
+    th = np.pi * (1 + 5 ** 0.5) * i
+    return np.stack([np.cos(th) * np.sin(phi), np.sin(th) * np.sin(phi), np.cos(phi)], 1)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--surfels", type=int, default=300_000)
+    ap.add_argument("--views", type=int, default=49)
+    ap.add_argument("--width", type=int, default=1600)
+    ap.add_argument("--height", type=int, default=1200)
+    ap.add_argument("--voxel_size", type=float, default=0.004)
+    ap.add_argument("--sdf_trunc", type=float, default=0.016)
+    ap.add_argument("--depth_trunc", type=float, default=3.0)
+    ap.add_argument("--repeats", type=int, default=2)
+    args = ap.parse_args()
+    from gaussmart_amd.camera import look_at_camera
+    from gaussmart_amd.gaussian_model import GaussianModel
+    from gaussmart_amd.gaussian_renderer import render
+    from gaussmart_amd.mesh import GaussianExtractor, camera_intrinsics, post_process_mesh
+    from gaussmart_amd.params import PipelineParams
+    from gaussmart_amd.tsdf import TSDFVolume
+    dev = torch.device("cuda", 0)
+    n = args.surfels
+    p = fib(n)
+    z = np.array([0.0, 0.0, 1.0])
+    axis = np.cross(z, p)
+    s = np.linalg.norm(axis, axis=1, keepdims=True)
+    ang = np.arctan2(s[:, 0], p @ z)
+    axis = np.where(s > 1e-9, axis / np.maximum(s, 1e-12), np.array([1.0, 0, 0]))
+    q = np.concatenate([np.cos(ang / 2)[:, None], axis * np.sin(ang / 2)[:, None]], 1)
+    spacing = math.sqrt(4 * math.pi / n)
+    params = dict(xyz=torch.tensor(p), features_dc=torch.zeros(n, 1, 3), features_rest=torch.zeros(n, 15, 3),
+                  scaling=torch.full((n, 2), math.log(0.8 * spacing)), rotation=torch.tensor(q),
+                  opacity=torch.full((n, 1), math.log(0.99 / 0.01)))
+    g = GaussianModel(3, device=dev)
+    g.create_from_params({k: v.float().to(dev).contiguous() for k, v in params.items()})
+    g.active_sh_degree = 0
+    cams = []
+    for i, d in enumerate(fib(args.views)):
+        up = (0, 0, 1) if abs(d[2]) < 0.95 else (0, 1, 0)
+        cams.append(look_at_camera(2.5 * d, (0, 0, 0), up, math.radians(50), args.width, args.height, device=dev, uid=i))
+    ex = GaussianExtractor(g, render, PipelineParams(depth_ratio=1.0), bg_color=[0, 0, 0])
+    sync = torch.cuda.synchronize
+    res = {}
+    for rep in range(args.repeats):
+        sync(); t0 = time.perf_counter()
+        ex.reconstruction(cams)
+        sync(); t1 = time.perf_counter()
+        aabb = ex.block_aabb(args.voxel_size, args.sdf_trunc, args.depth_trunc)
+        sync(); t2 = time.perf_counter()
+        vol = TSDFVolume(args.voxel_size, args.sdf_trunc, aabb, device=dev)
+        touched = [vol.integrate(ex._masked_depth(i, True), ex.rgbmaps[i], camera_intrinsics(c), c.world_view_transform.T,
+                                 args.depth_trunc) for i, c in enumerate(cams)]
+        sync(); t3 = time.perf_counter()
+        mesh = vol.extract_triangle_mesh()
+        sync(); t4 = time.perf_counter()
+        post = post_process_mesh(mesh, 1)
+        t5 = time.perf_counter()
+        res = {"surfels": n, "views": args.views, "width": args.width, "height": args.height,
+               "voxel_size": args.voxel_size, "sdf_trunc": args.sdf_trunc, "depth_trunc": args.depth_trunc,
+               "grid_blocks": vol.n_blocks, "allocated_blocks": vol.n_alloc, "mean_touched_per_view": float(np.mean(touched)),
+               "vertices": len(mesh.vertices), "triangles": len(mesh.triangles), "post_vertices": len(post.vertices),
+               "render_ms": 1e3 * (t1 - t0), "aabb_ms": 1e3 * (t2 - t1), "touch_integrate_ms": 1e3 * (t3 - t2),
+               "marching_cubes_ms": 1e3 * (t4 - t3), "post_process_ms": 1e3 * (t5 - t4),
+               "integrate_plus_extract_ms": 1e3 * (t4 - t2), "repeat": rep}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,215 @@
+"""Mesh export without a device: the generated marching-cubes table, the float64 TSDF restatement (tests/tsdf_ref.py), PLY
+round trip, post_process_mesh, the bounding sphere against the reference's render_utils, and argument rejection of the
+TSDF / marching-cubes C ABI."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import ROOT, GOLDEN
+from gaussmart_amd import _lib
+from gaussmart_amd.mesh import TriangleMesh, post_process_mesh, focus_point_fn, GaussianExtractor
+import tsdf_ref
+
+T = tsdf_ref.mc_table()
+TABLE = T.build_table()
+
+
+def test_generator_reproduces_committed_header():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "gen_mc_tables.py"), "--check"], capture_output=True,
+                       text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    with open(os.path.join(ROOT, "gaussmart_amd", "csrc", "mc_tables.h")) as f:
+        assert f.read() == T.render_header(TABLE)
+
+
+def _crossing(case, e):
+    c0, c1, _ = T.EDGES[e]
+    return ((case >> c0) & 1) != ((case >> c1) & 1)
+
+
+def test_table_vertices_on_crossing_edges():
+    assert len(TABLE) == 256 and TABLE[0] == [] and TABLE[255] == []
+    for case, tris in enumerate(TABLE):
+        used = {e for t in tris for e in t}
+        assert all(_crossing(case, e) for e in used), case
+        # every crossing edge carries a vertex
+        assert used == {e for e in range(12) if _crossing(case, e)}, case
+        assert len(tris) <= T.MAX_TRIS
+
+
+def test_table_complement_reverses_winding():
+    checked = 0
+    for case in range(256):
+        if any(T.is_ambiguous_face(case, f) for f in T.FACES):
+            continue
+        a = {tuple(t) for t in TABLE[case]}
+        b = {(t[0], t[2], t[1]) for t in TABLE[case ^ 0xFF]}
+        canon = lambda s: {min((t, t[1:] + t[:1], t[2:] + t[:2])) for t in s}
+        assert canon(a) == canon(b), case
+        checked += 1
+    assert checked > 100
+
+
+def test_random_sign_fields_glue_to_closed_surfaces():
+    rng = np.random.default_rng(0)
+    for trial in range(200):
+        n = 6
+        f = np.where(rng.random((n, n, n)) < 0.5, -1.0, 1.0)
+        f[0], f[-1], f[:, 0], f[:, -1], f[:, :, 0], f[:, :, -1] = 1, 1, 1, 1, 1, 1   # closed: positive border
+        verts, tris, _, _ = tsdf_ref.mc_dense(f, np.ones_like(f))
+        if len(tris) == 0:
+            continue
+        e = np.sort(np.concatenate([tris[:, [0, 1]], tris[:, [1, 2]], tris[:, [2, 0]]]), axis=1)
+        _, counts = np.unique(e, axis=0, return_counts=True)
+        assert (counts == 2).all(), f"trial {trial}: edge used {counts.max()} times"
+        # consistent orientation: every directed edge appears once
+        d = np.concatenate([tris[:, [0, 1]], tris[:, [1, 2]], tris[:, [2, 0]]])
+        assert len(np.unique(d, axis=0)) == len(d), trial
+
+
+def test_reference_flat_wall():
+    W, H = 64, 48
+    intr = (50.0, 50.0, (W - 1) / 2, (H - 1) / 2)
+    vs, st, wall = 0.05, 0.2, 2.0
+    vol = tsdf_ref.RefVolume(vs, st)
+    depth = torch.full((1, H, W), wall, dtype=torch.float64)
+    rgb = torch.full((3, H, W), (100 + 0.5) / 255, dtype=torch.float64)
+    w2c = torch.eye(4, dtype=torch.float64)
+    touched = vol.touch(depth, intr, w2c, 5.0)
+    assert touched
+    vol.integrate(depth, rgb, intr, w2c, 5.0, touched=touched)
+    checked = 0
+    for bb, s in vol.blocks.items():
+        l = np.arange(16 ** 3)
+        g = np.array(bb)[None] * 16 + np.stack([l % 16, (l // 16) % 16, l // 256], 1)
+        exp = tsdf_ref.flat_wall_expected((g + 0.5) * vs, intr, wall, st, W, H)
+        upd = s[1].numpy() > 0
+        assert np.array_equal(upd, ~np.isnan(exp)), bb
+        assert np.abs(s[0].numpy()[upd] - exp[upd]).max(initial=0) < 1e-12
+        assert (s[2:5].numpy()[:, upd] == 100).all()
+        checked += upd.sum()
+    assert checked > 1000
+
+
+def test_ply_round_trip(tmp_path):
+    rng = np.random.default_rng(1)
+    m = TriangleMesh(rng.normal(size=(50, 3)).astype(np.float32), rng.integers(0, 50, (80, 3)).astype(np.int32),
+                     (rng.integers(0, 256, (50, 3)) / 255.0).astype(np.float32))
+    p = str(tmp_path / "m.ply")
+    m.write_ply(p)
+    r = TriangleMesh.read_ply(p)
+    assert np.array_equal(r.vertices, m.vertices) and np.array_equal(r.triangles, m.triangles)
+    assert np.abs(r.vertex_colors - m.vertex_colors).max() < 1e-6
+    head = open(p, "rb").read(400)
+    assert b"binary_little_endian" in head and b"property list uchar int vertex_indices" in head
+    e = TriangleMesh()
+    e.write_ply(p)
+    assert len(TriangleMesh.read_ply(p).triangles) == 0
+
+
+def _strip(n_tris, offset):
+    """A triangle strip of n_tris triangles (edge-connected), vertex indices from offset."""
+    n_v = n_tris + 2
+    v = np.stack([np.arange(n_v) // 2, np.arange(n_v) % 2, np.zeros(n_v)], 1).astype(np.float32) + [0, 0, offset]
+    t = np.array([[i, i + 1, i + 2] for i in range(n_tris)]) + offset
+    return v, t
+
+
+def test_post_process_mesh_clusters():
+    parts = [_strip(n, o) for n, o in ((10, 0), (60, 12), (500, 74))]
+    verts = np.concatenate([p[0] for p in parts])
+    tris = np.concatenate([p[1] for p in parts])
+    m = TriangleMesh(verts, tris, np.zeros_like(verts))
+    one = post_process_mesh(m, 1)
+    assert len(one.triangles) == 500 and len(one.vertices) == 502
+    assert one.triangles.max() == 501
+    three = post_process_mesh(m, 3)   # 3rd largest is 10 < 50: the floor of 50 keeps 60 and 500
+    assert len(three.triangles) == 560 and len(three.vertices) == 62 + 502
+    many = post_process_mesh(m, 50)   # fewer clusters than asked: clamped (the reference raises IndexError)
+    assert len(many.triangles) == 560
+
+
+def test_focus_point_and_radius_match_reference():
+    g = np.load(os.path.join(GOLDEN, "render_utils.npz"))
+    k = 0
+    while f"c2ws_{k}" in g:
+        c2ws = g[f"c2ws_{k}"]
+        poses = c2ws[:, :3, :] @ np.diag([1, -1, -1, 1])
+        c = focus_point_fn(poses)
+        assert np.abs(c - g[f"center_{k}"]).max() < 1e-10
+        cams = [type("Cam", (), {"world_view_transform": torch.from_numpy(np.linalg.inv(m).T.copy())})() for m in c2ws]
+        ex = GaussianExtractor.__new__(GaussianExtractor)
+        ex.viewpoint_stack = cams
+        ex.estimate_bounding_sphere()
+        assert abs(ex.radius - float(g[f"radius_{k}"])) < 1e-9
+        k += 1
+    assert k == 3
+
+
+def _vol(**kw):
+    v = _lib.GsrTsdfVolume()
+    v.voxel_size, v.sdf_trunc = kw.get("voxel_size", 0.01), kw.get("sdf_trunc", 0.05)
+    v.block_lo[:] = kw.get("lo", (0, 0, 0))
+    v.block_hi[:] = kw.get("hi", (4, 4, 4))
+    return v
+
+
+@pytest.mark.parametrize("kw,rc,msg", [
+    (dict(voxel_size=0.0), _lib.GsrError, "voxel_size must be > 0"),
+    (dict(voxel_size=-1.0), _lib.GsrError, "voxel_size must be > 0"),
+    (dict(sdf_trunc=0.0), _lib.GsrError, "sdf_trunc must be > 0"),
+    (dict(lo=(0, 5, 0), hi=(4, 4, 4)), _lib.GsrError, "inverted"),
+    (dict(lo=(-1000, -1000, -1000), hi=(1000, 1000, 1000)), _lib.GsrError, "voxel_size"),
+])
+def test_abi_rejects_bad_volume(kw, rc, msg):
+    L = _lib.lib()
+    v = _vol(**kw)
+    n, ws = C.c_int64(), C.c_size_t()
+    code = L.gsr_tsdf_sizes(C.byref(v), C.byref(n), C.byref(ws), None)
+    err = L.gsr_last_error().decode()
+    over_cap = "lo" in kw and kw["lo"][0] == -1000
+    assert code == (-4 if over_cap else -1), (code, err)
+    assert msg in err
+    if over_cap:
+        assert "depth_trunc" in err and "voxel_size" in err
+    # the per-view entry points run the same checks before any device work
+    intr = (C.c_float * 4)(100, 100, 10, 10)
+    M = (C.c_float * 16)(*np.eye(4).reshape(-1).tolist())
+    nt = C.c_int64()
+    assert L.gsr_tsdf_touch(C.byref(v), None, None, 8, 8, intr, M, 1.0, C.byref(nt), None) == code
+    nv, ntr = C.c_int64(), C.c_int64()
+    assert L.gsr_mcubes_count(C.byref(v), None, 0, C.byref(nv), C.byref(ntr), None) == code
+
+
+def test_abi_rejects_empty_image_and_sizes_a_good_volume():
+    L = _lib.lib()
+    v = _vol()
+    n, ws, off = C.c_int64(), C.c_size_t(), C.c_size_t()
+    assert L.gsr_tsdf_sizes(C.byref(v), C.byref(n), C.byref(ws), C.byref(off)) == 0 and n.value == 64 and ws.value > 64 * 16
+    # the slot -> block map lies inside the workspace, past the header, and clear of its end
+    assert off.value >= 256 and off.value % 4 == 0 and off.value + 4 * 64 <= ws.value
+    intr = (C.c_float * 4)(100, 100, 10, 10)
+    M = (C.c_float * 16)(*np.eye(4).reshape(-1).tolist())
+    nt = C.c_int64()
+    for H, W in ((0, 8), (8, 0), (-1, 8)):
+        assert L.gsr_tsdf_touch(C.byref(v), C.c_void_p(16), None, H, W, intr, M, 1.0, C.byref(nt), None) == -1
+        assert "empty image" in L.gsr_last_error().decode()
+        assert L.gsr_tsdf_integrate(C.byref(v), C.c_void_p(16), None, C.c_void_p(16), H, W, intr, M, 1.0, 0, None) == -1
+        assert "empty image" in L.gsr_last_error().decode()
+    # an empty grid: nothing to do, nothing launched
+    e = _vol(lo=(2, 2, 2), hi=(2, 5, 5))
+    assert L.gsr_tsdf_sizes(C.byref(e), C.byref(n), C.byref(ws), None) == 0 and n.value == 0
+    assert L.gsr_tsdf_touch(C.byref(e), C.c_void_p(16), None, 8, 8, intr, M, 1.0, C.byref(nt), None) == 0 and nt.value == 0
+    nv, ntr = C.c_int64(), C.c_int64()
+    assert L.gsr_mcubes_count(C.byref(e), None, 0, C.byref(nv), C.byref(ntr), None) == 0 and nv.value == ntr.value == 0
+
+
+def test_unbounded_is_not_implemented():
+    ex = GaussianExtractor.__new__(GaussianExtractor)
+    with pytest.raises(NotImplementedError, match="follow-up"):
+        ex.extract_mesh_unbounded()
