@@ -106,25 +106,44 @@ class TSDFVolume:
         return n_touched.value
 
     @classmethod
-    def from_dense(cls, voxel_size, sdf_trunc, tsdf, weight, colour=None, device=None):
-        """A volume holding a dense field [X,Y,Z] whose voxel (0, 0, 0) is grid voxel (0, 0, 0); colour [X,Y,Z,3] on the
-        0..255 scale.  Every block of the field is allocated (slots in grid order); voxels beyond it keep weight 0."""
+    def from_dense(cls, voxel_size, sdf_trunc, tsdf, weight, colour=None, device=None, block_lo=(0, 0, 0), blocks=None,
+                   slot_order=None):
+        """A volume holding a dense field [X,Y,Z] whose voxel (0, 0, 0) is grid voxel 16 * block_lo (the block AABB is
+        block_lo + [0, ceil(X/16)) x ...); colour [X,Y,Z,3] on the 0..255 scale.  Voxels beyond the field keep weight 0.
+        blocks: bool [ceil(X/16), ceil(Y/16), ceil(Z/16)], the blocks to allocate (None: all); the others stay unallocated.
+        slot_order: a permutation of the allocated blocks' grid-order ranks, slot s holding the block of rank
+        slot_order[s] (None: slots in grid order).  A test and loading aid: fusion never builds a volume this way."""
         tsdf = torch.as_tensor(tsdf, dtype=torch.float32)
         X, Y, Z = tsdf.shape
         dims = [-(-s // BLOCK) for s in (X, Y, Z)]
-        vol = cls(voxel_size, sdf_trunc, ([0, 0, 0], dims), device=device)
-        n = vol.n_blocks
+        lo = [int(v) for v in block_lo]
+        vol = cls(voxel_size, sdf_trunc, (lo, [l + d for l, d in zip(lo, dims)]), device=device)
         pad = torch.zeros((5, dims[0] * BLOCK, dims[1] * BLOCK, dims[2] * BLOCK), dtype=torch.float32)
         pad[0, :X, :Y, :Z] = tsdf
         pad[1, :X, :Y, :Z] = torch.as_tensor(weight, dtype=torch.float32)
         if colour is not None:
             pad[2:5, :X, :Y, :Z] = torch.as_tensor(colour, dtype=torch.float32).permute(3, 0, 1, 2)
-        # [5, bx, 16, by, 16, bz, 16] -> [5, bz, by, bx, z, y, x] -> [5, slot, 4096]
+        # [5, bx, 16, by, 16, bz, 16] -> [5, bz, by, bx, z, y, x] -> [5, linear block id, 4096]
         pad = pad.reshape(5, dims[0], BLOCK, dims[1], BLOCK, dims[2], BLOCK).permute(0, 5, 3, 1, 6, 4, 2)
+        pad = pad.reshape(5, vol.n_blocks, BLOCK ** 3)
+        if blocks is None:
+            ids = torch.arange(vol.n_blocks, dtype=torch.int64)
+        else:
+            sel = torch.as_tensor(np.asarray(blocks, dtype=bool))
+            if tuple(sel.shape) != tuple(dims):
+                raise ValueError(f"blocks must be {dims}, got {list(sel.shape)}")
+            ids = torch.nonzero(sel.permute(2, 1, 0).reshape(-1)).flatten()   # linear ids (x fastest), grid order
+        n = len(ids)
+        if slot_order is not None:
+            order = torch.as_tensor(np.asarray(slot_order, dtype=np.int64))
+            if not torch.equal(torch.sort(order).values, torch.arange(n)):
+                raise ValueError(f"slot_order must be a permutation of range({n})")
+            ids = ids[order]
         vol._grow_pool(n)
-        vol.pool[:, :n] = pad.reshape(5, n, BLOCK ** 3).to(vol.device)
-        vol.block_index.copy_(torch.arange(n, dtype=torch.int32, device=vol.device))
-        vol._slot_block().copy_(torch.arange(n, dtype=torch.int32, device=vol.device))
+        vol.pool[:, :n] = pad[:, ids].to(vol.device)
+        ids = ids.to(torch.int32).to(vol.device)
+        vol.block_index[ids.long()] = torch.arange(n, dtype=torch.int32, device=vol.device)
+        vol._slot_block()[:n] = ids
         vol._v.n_alloc = n
         return vol
 

@@ -213,3 +213,44 @@ def test_unbounded_is_not_implemented():
     ex = GaussianExtractor.__new__(GaussianExtractor)
     with pytest.raises(NotImplementedError, match="follow-up"):
         ex.extract_mesh_unbounded()
+
+
+def test_from_dense_layouts():
+    """TSDFVolume.from_dense builds its host-side layout on any device: with default arguments every block in grid order
+    (the layout the marching-cubes parity tests were written against); with block_lo, blocks and slot_order a sparse,
+    shuffled volume whose maps agree and whose voxels() are the field's."""
+    from gaussmart_amd.tsdf import TSDFVolume
+    rng = np.random.default_rng(0)
+    f = rng.normal(size=(20, 33, 16)).astype(np.float32)
+    w = rng.random(f.shape).astype(np.float32)
+    col = rng.integers(0, 256, f.shape + (3,)).astype(np.float32)
+    vol = TSDFVolume.from_dense(0.01, 0.05, f, w, col, device="cpu")
+    dims, n = [2, 3, 1], 6
+    pad = np.zeros((5, 32, 48, 16), np.float32)
+    pad[0, :20, :33], pad[1, :20, :33], pad[2:5, :20, :33] = f, w, col.transpose(3, 0, 1, 2)
+    grid_order = pad.reshape(5, 2, 16, 3, 16, 1, 16).transpose(0, 5, 3, 1, 6, 4, 2).reshape(5, n, 4096)
+    assert (list(vol.block_lo), list(vol.block_hi), vol.n_alloc) == ([0, 0, 0], dims, n)
+    assert vol.pool.shape == (5, 64, 4096) and vol.pool[:, :n].numpy().tobytes() == grid_order.tobytes()
+    assert not vol.pool[:, n:].any()
+    assert vol.block_index.tolist() == list(range(n)) and vol._slot_block().tolist() == list(range(n))
+
+    blocks = np.array([[[True], [False], [True]], [[False], [True], [True]]])
+    order = [3, 0, 2, 1]
+    sv = TSDFVolume.from_dense(0.01, 0.05, f, w, col, device="cpu", block_lo=(-2, 5, -1), blocks=blocks, slot_order=order)
+    assert (list(sv.block_lo), list(sv.block_hi), sv.n_alloc) == ([-2, 5, -1], [0, 8, 0], 4)
+    ids = [b for b in range(n) if blocks[b % 2, b // 2, 0]]   # linear ids, x fastest
+    slot_block = sv._slot_block()[:4].tolist()
+    assert slot_block == [ids[o] for o in order]
+    bi = sv.block_index.tolist()
+    assert [bi[b] for b in slot_block] == list(range(4)) and sorted(b for b in range(n) if bi[b] < 0) == [1, 2]
+    g, t, wt, c = (a.numpy() for a in sv.voxels())
+    g = g - 16 * np.array([-2, 5, -1])
+    assert sorted({tuple(b) for b in (g[::4096] // 16).tolist()}) == sorted((b % 2, b // 2, 0) for b in ids)
+    inside = (g < np.array(f.shape)).all(1)
+    gi = tuple(g[inside].T)
+    assert np.array_equal(t[inside], f[gi]) and np.array_equal(wt[inside], w[gi]) and np.array_equal(c[inside], col[gi])
+    assert not wt[~inside].any()
+    with pytest.raises(ValueError, match="permutation"):
+        TSDFVolume.from_dense(0.01, 0.05, f, w, device="cpu", blocks=blocks, slot_order=[0, 1, 1, 2])
+    with pytest.raises(ValueError, match="blocks must be"):
+        TSDFVolume.from_dense(0.01, 0.05, f, w, device="cpu", blocks=np.ones((2, 2, 1), bool))

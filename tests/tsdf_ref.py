@@ -32,6 +32,7 @@ class RefVolume:
 
     def touch(self, depth, intr, w2c, depth_trunc, mask=None):
         fx, fy, cx, cy = (float(v) for v in intr)
+        depth_trunc = float(np.float32(depth_trunc))   # the library takes depth_trunc as a float: 0 < d <= it is exact
         d = torch.as_tensor(depth, dtype=torch.float64).reshape(depth.shape[-2:])
         H, W = d.shape
         vv, uu = torch.meshgrid(torch.arange(0, H, STRIDE, dtype=torch.float64), torch.arange(0, W, STRIDE, dtype=torch.float64),
@@ -94,6 +95,7 @@ class RefVolume:
 
     def integrate(self, depth, rgb, intr, w2c, depth_trunc, mask=None, touched=None):
         fx, fy, cx, cy = (float(v) for v in intr)
+        depth_trunc = float(np.float32(depth_trunc))
         d = torch.as_tensor(depth, dtype=torch.float64).reshape(depth.shape[-2:])
         H, W = d.shape
         col = torch.as_tensor(rgb, dtype=torch.float64).reshape(3, H, W)
@@ -137,7 +139,7 @@ class RefVolume:
         ok_v = at(u, step(vf, v))[0]
         ok_uv = at(step(uf, u), step(vf, v))[0]   # near both boundaries: the diagonal neighbour is a candidate too
         unstable = (z > 0) & ((near_u & (ok | ok_u)) | (near_v & (ok | ok_v)) | (near_u & near_v & ok_uv) | (((sdf + self.st).abs() < 1e-6) & inside) |
-                              (((dv - depth_trunc).abs() < 1e-6) & inside) | ((uf - (W - BORDER)).abs() < 1e-4) |
+                              ((uf - (W - BORDER)).abs() < 1e-4) |
                               ((vf - (H - BORDER)).abs() < 1e-4) | ((uf - BORDER).abs() < 1e-4) | ((vf - BORDER).abs() < 1e-4))
         for i, bb in enumerate(blocks):
             s = self.blocks[bb]
