@@ -96,12 +96,11 @@ class _Objective(torch.autograd.Function):
             scale = g_total.detach().float().reshape(1).contiguous()
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             dimg = torch.empty_like(img)
-            from .rasterizer import row_scan_job_alive
-            job = getattr(ctx, "row_scan_job", None)
-            ctx.row_scan_job = None
+            from .rasterizer import row_scan_job_usable
+            job, ctx.row_scan_job = ctx.row_scan_job, None
             # the second half may only be enqueued while the rasterizer's backward has not run (afterwards the job's
             # buffers are back in the pool), and on the stream the first half was ordered on
-            if not row_scan_job_alive(job) or job._stream != torch.cuda.current_stream(dev).cuda_stream:
+            if not row_scan_job_usable(job, torch.cuda.current_stream(dev).cuda_stream):
                 job = None
             deferred, ctx.deferred = ctx.deferred, None
             if ctx.use_reg:       # first: with a deferred value its launch also leaves the regularizer's forward sums

@@ -156,7 +156,7 @@ class _Allocator:
         self.color_stream = color_stream        # torch stream on which the SH parameters will be ready (or None)
         self.stream = torch.cuda.current_stream(device).cuda_stream
         self.kept = _Lease()        # geom / binning / image: travel with the autograd node
-        self.scratch = _Lease()     # released by done()
+        self.scratch = _Lease()     # released by finish()
         self.cb = _lib.ALLOC_FN(self._alloc)
 
     def _alloc(self, _ctx, which, nbytes):
@@ -183,9 +183,17 @@ class _Allocator:
             self.error = e
             return 0
 
-    def done(self):
-        """The library call has returned: its scratch may be reused by the next call on this stream."""
+    def finish(self, rc):
+        """The library call has returned `rc`: its scratch may be reused by the next call on this stream, a colour
+        hook the library never reached runs now, and a failure is raised (a failed call keeps no buffers)."""
         self.scratch.release()
+        if self.before_color is not None:       # the library returned before announcing the colour pass
+            self.before_color()
+        if rc != 0:
+            self.kept.release()
+            if self.error is not None:
+                raise self.error
+            _lib.check(rc)
 
 
 # Set to True to backpropagate through one forward more than once (retain_graph=True): the buffers the
@@ -198,13 +206,6 @@ def _check_lease(ctx):
     if ctx.lease.released:
         raise _lib.GsrError("the buffers saved by this forward were recycled after its first backward; set "
                             "gaussmart_amd.rasterizer.KEEP_BUFFERS_AFTER_BACKWARD = True to backpropagate twice")
-
-
-def _finish_lease(ctx):
-    # the autograd node often outlives backward() by several iterations (reference cycles through
-    # retain_grad hooks are only broken by the cyclic GC), so the lease is returned here
-    if not KEEP_BUFFERS_AFTER_BACKWARD:
-        ctx.lease.release()
 
 
 class ColorGradRecord:
@@ -259,35 +260,56 @@ class RasterState:
         return rec
 
 
-# Row-scan side job (include/gsr.h: GsrRowScanJob): the raw forward describes the scan its backward starts with and keeps
-# the description ON ITS AUTOGRAD NODE; the fused objective, whose kernels run between the forward and the backward, finds
-# it through the grad_fn of the image it was handed -- so a job only ever rides with an objective of the image THAT forward
-# produced -- and carries the scan in extra workgroups of its own launches.  The job holds the forward's buffer lease until
-# the rasterizer's backward has consumed it; that backward marks it dead, so a kernel that would write into BINNING after
-# the buffers went back to the pool (an objective whose backward runs later, or twice) is never launched.
-# GSR_ROW_SCAN_RIDE=0 switches the hand-over off.
+# GSR_ROW_SCAN_RIDE=0 switches the row-scan hand-over (_RowScanJob) off.
 _ROW_SCAN_RIDE = __import__("os").environ.get("GSR_ROW_SCAN_RIDE", "1") != "0"
 # a backward that receives no gradient for allmap says so (GSR_FLAG_NO_SURFACE_GRAD); GSR_NO_SURFACE_FAST_PATH=0: A/B aid
 _NO_SURFACE_FAST_PATH = __import__("os").environ.get("GSR_NO_SURFACE_FAST_PATH", "1") != "0"
 
 
+class _RowScanJob(_lib.GsrRowScanJob):
+    """Row-scan side job (include/gsr.h: GsrRowScanJob): the raw forward describes the scan its backward starts with and
+    keeps the description ON ITS AUTOGRAD NODE; the fused objective, whose kernels run between the forward and the
+    backward, finds it through the grad_fn of the image it was handed -- so a job only ever rides with an objective of the
+    image THAT forward produced -- and carries the scan in extra workgroups of its own launches.  The job holds the
+    forward's buffer lease until the rasterizer's backward has retired it, so a kernel that would write into BINNING after
+    the buffers went back to the pool (an objective whose backward runs later, or twice) is never launched.  The hand-over
+    is ordered by the forward's stream and nothing else: on any other stream the job is not usable.  The protocol is the
+    functions below: the objective goes through them and reads none of the job's state itself."""
+
+    def __init__(self, lease, stream):
+        super().__init__()
+        self._lease = lease         # keeps BINNING out of the pool while anybody may still write into it
+        self._stream = stream       # handle of the stream the forward ran on
+        self._taken = self._dead = False
+
+
+def row_scan_job_alive(job):
+    """False once the rasterizer's backward has retired the job (its buffers may be back in the pool)."""
+    return job is not None and not job._dead
+
+
+def row_scan_job_usable(job, stream):
+    """A half of `job` may be enqueued on `stream` (a stream handle): alive, and on the stream it was ordered on."""
+    return row_scan_job_alive(job) and job._stream == stream
+
+
 def take_row_scan_job(image):
     """The row-scan job of the forward that produced `image` (one of its outputs, not a tensor derived from them), for a
     caller about to launch kernels on the CURRENT stream -- None if that forward offered none, if somebody already took
-    it, if its backward already ran, or if the forward ran on another stream (the hand-over relies on stream order and
-    nothing else)."""
+    it, if its backward already ran, or if the forward ran on another stream.  Handed out once."""
     job = getattr(getattr(image, "grad_fn", None), "row_scan_job", None)
-    if job is None or job._taken or job._dead:
-        return None
-    if job._stream != torch.cuda.current_stream(image.device).cuda_stream:
+    if job is None or job._taken or not row_scan_job_usable(job, torch.cuda.current_stream(image.device).cuda_stream):
         return None
     job._taken = True
     return job
 
 
-def row_scan_job_alive(job):
-    """False once the rasterizer's backward has consumed the job (its buffers may be back in the pool)."""
-    return job is not None and not job._dead
+def _retire_row_scan_job(job, stream):
+    """The rasterizer's backward on `stream` is about to run: nobody may enqueue a half of `job` any more (its buffers go
+    back to the pool after that backward).  -> whether that backward may still use it."""
+    usable = row_scan_job_usable(job, stream)
+    job._dead, job._lease = True, None
+    return usable
 
 
 def release_workspace():
@@ -315,118 +337,138 @@ def _make_view(rs: GaussianRasterizationSettings, sh_coeffs: int, flags: int, de
     return v, (bg, vm, pm, cp)
 
 
+def _pack_reference(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
+    """The reference signature's inputs as contiguous float32 tensors, and the GsrGaussians pointing at them (the caller
+    keeps the tensors alive while the library may read them) -> (tensors, gaussians, channels, sh_coeffs)."""
+    device = means3D.device
+    N = means3D.shape[0]
+    tensors = [_f32c(t, name, device) for t, name in
+               ((means3D, "means3D"), (sh, "shs"), (colors_precomp, "colors_precomp"), (opacities, "opacities"),
+                (scales, "scales"), (rotations, "rotations"), (cov3Ds_precomp, "cov3D_precomp"))]
+    sh, colors_precomp = tensors[1], tensors[2]
+    channels = 3
+    if colors_precomp is not None:
+        # [N,3] RGB, or a wide per-pixel payload [N,C] with C = 4, 8, ... 64 (semantic / feature splatting)
+        if colors_precomp.dim() != 2 or colors_precomp.shape[0] != N:
+            raise _lib.GsrError("colors_precomp must be [N,C]")
+        channels = int(colors_precomp.shape[1])
+    g = _lib.GsrGaussians(N, *[_ptr(t) for t in tensors], None)
+    return tensors, g, channels, sh.shape[1] if sh is not None else 0
+
+
+def _pack_raw(xyz, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, color_cache=None):
+    """The raw signature's inputs (GSR_FLAG_RAW_PARAMS: split SH storage, the optional colour cache in the colors_precomp
+    slot) as contiguous float32 tensors, and the GsrGaussians pointing at them -> (tensors, gaussians, sh_coeffs)."""
+    device = xyz.device
+    N = xyz.shape[0]
+    xyz, f_dc, f_rest = _f32c(xyz, "xyz", device), _f32c(f_dc, "features_dc", device), _f32c(f_rest, "features_rest", device)
+    opacity_raw, scaling_raw = _f32c(opacity_raw, "opacity", device), _f32c(scaling_raw, "scaling", device)
+    rotation_raw = _f32c(rotation_raw, "rotation", device)
+    if f_dc.dim() != 3 or f_dc.shape[1] != 1 or f_rest.dim() != 3 or f_rest.shape[0] != N:
+        raise ValueError("features_dc must be [N,1,3] and features_rest [N,K-1,3]")
+    if color_cache is not None and (color_cache.numel() != 13 * N or color_cache.dtype != torch.float32
+                                    or color_cache.device != device):
+        raise ValueError("color_cache must be float32 [13 N] on the parameters' device")
+    rest = f_rest if f_rest.shape[1] > 0 else None
+    g = _lib.GsrGaussians(N, _ptr(xyz), _ptr(f_dc), _ptr(color_cache), _ptr(opacity_raw), _ptr(scaling_raw),
+                          _ptr(rotation_raw), None, _ptr(rest))
+    return (xyz, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw), g, 1 + f_rest.shape[1]
+
+
+def _forward(rs, g, sh_coeffs, flags, channels, device, before_color=None, color_stream=None):
+    """ONE gsr_forward call -> (color [C,H,W], radii, allmap [7,H,W], num_rendered, allocator, the view's keep tuple).
+    The allocator's `kept` lease holds the geom / binning / image buffers (alloc.buffers) a backward needs."""
+    if device.type != "cuda":
+        raise _lib.GsrError("GaussianRasterizer needs tensors on a HIP device (torch 'cuda'); there is no CPU path")
+    L = _lib.lib()
+    H, W = int(rs.image_height), int(rs.image_width)
+    with torch.cuda.device(device):
+        view, keep = _make_view(rs, sh_coeffs, flags, device, channels)
+        color = torch.empty((channels, H, W), dtype=torch.float32, device=device)
+        allmap = torch.empty((7, H, W), dtype=torch.float32, device=device)
+        radii = torch.empty((g.count,), dtype=torch.int32, device=device)
+        out = _lib.GsrForwardOut(color.data_ptr(), allmap.data_ptr(), radii.data_ptr(), 0, None, None, None)
+        alloc = _Allocator(device, before_color, color_stream)
+        rc = L.gsr_forward(C.byref(view), C.byref(g), C.byref(out), alloc.cb, None, C.c_void_p(alloc.stream))
+        alloc.finish(rc)
+    return color, radii, allmap, int(out.num_rendered), alloc, keep
+
+
+def _keep_for_backward(ctx, rs, g, sh_coeffs, flags, channels, num_rendered, alloc, keep):
+    """What the backward call reuses of its forward; -> the geom / binning / image buffers, for save_for_backward.  The
+    GsrGaussians points at the input tensors the Function saves; the lease goes back to the pool with this node."""
+    ctx.raster_settings, ctx.gaussians, ctx.sh_coeffs, ctx.flags, ctx.channels = rs, g, sh_coeffs, flags, channels
+    ctx.num_rendered, ctx.lease, ctx.view_keep = num_rendered, alloc.kept, keep
+    ctx.set_materialize_grads(False)     # no zero tensors for the unused radii / image gradients
+    return [alloc.buffers[k] for k in (_lib.GSR_BUF_GEOM, _lib.GSR_BUF_BINNING, _lib.GSR_BUF_IMAGE)]
+
+
+def _grad_images(ctx, grad_color, grad_allmap, device):
+    """-> (grad_color, grad_allmap, flags of the backward).  An output nobody differentiated gets the cached zero image.
+    When nothing was differentiated through allmap (lambda_normal = lambda_dist = 0, or the first 7,000 iterations) the
+    backward is told so (GSR_FLAG_NO_SURFACE_GRAD); a GSR_FLAG_COLOR_ONLY forward kept no surface state and always is."""
+    rs = ctx.raster_settings
+    H, W = int(rs.image_height), int(rs.image_width)
+    flags = ctx.flags
+    if grad_allmap is None and (_NO_SURFACE_FAST_PATH or flags & _lib.GSR_FLAG_COLOR_ONLY):
+        flags |= _lib.GSR_FLAG_NO_SURFACE_GRAD
+    grad_color = _zero_image(ctx.channels, H, W, device) if grad_color is None else _f32c(grad_color, "grad_color", device)
+    grad_allmap = _zero_image(7, H, W, device) if grad_allmap is None else _f32c(grad_allmap, "grad_allmap", device)
+    return grad_color, grad_allmap, flags
+
+
+def _backward(ctx, flags, grad_color, grad_allmap, grads, buffers, job=None):
+    """ONE backward call on what the forward kept, filling `grads`: gsr_backward_with_job if the forward's row-scan job
+    is still usable on this stream, else gsr_backward.  The job is retired either way; the forward's buffers go back
+    to the pool afterwards."""
+    L = _lib.lib()
+    radii, geom, binning, image = buffers
+    device = radii.device
+    with torch.cuda.device(device):
+        view, keep = _make_view(ctx.raster_settings, ctx.sh_coeffs, flags, device, ctx.channels, ctx.view_keep)
+        alloc = _Allocator(device)
+        args = (C.byref(view), C.byref(ctx.gaussians), ctx.num_rendered, _ptr(radii), _ptr(geom), _ptr(binning),
+                _ptr(image), _ptr(grad_color), _ptr(grad_allmap), C.byref(grads))
+        if job is not None and _retire_row_scan_job(job, alloc.stream):
+            rc = L.gsr_backward_with_job(*args, C.byref(job), alloc.cb, None, C.c_void_p(alloc.stream))
+            STATS["row_scans_carried"] += int(job.stage == 2)
+        else:
+            rc = L.gsr_backward(*args, alloc.cb, None, C.c_void_p(alloc.stream))
+        alloc.finish(rc)
+    # the autograd node often outlives backward() by several iterations (reference cycles through
+    # retain_grad hooks are only broken by the cyclic GC), so the lease is returned here
+    if not KEEP_BUFFERS_AFTER_BACKWARD:
+        ctx.lease.release()
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                 cov3Ds_precomp, raster_settings, flags):
-        L = _lib.lib()
-        device = means3D.device
-        if device.type != "cuda":
-            raise _lib.GsrError("GaussianRasterizer needs tensors on a HIP device (torch 'cuda'); "
-                                "there is no CPU path")
-        rs = raster_settings
-        N = means3D.shape[0]
-        H, W = int(rs.image_height), int(rs.image_width)
-        means3D = _f32c(means3D, "means3D", device)
-        sh = _f32c(sh, "shs", device)
-        colors_precomp = _f32c(colors_precomp, "colors_precomp", device)
-        opacities = _f32c(opacities, "opacities", device)
-        scales = _f32c(scales, "scales", device)
-        rotations = _f32c(rotations, "rotations", device)
-        cov3Ds_precomp = _f32c(cov3Ds_precomp, "cov3D_precomp", device)
-        channels = 3
-        if colors_precomp is not None:
-            # [N,3] RGB, or a wide per-pixel payload [N,C] with C = 4, 8, ... 64 (semantic / feature splatting)
-            if colors_precomp.dim() != 2 or colors_precomp.shape[0] != N:
-                raise _lib.GsrError("colors_precomp must be [N,C]")
-            channels = int(colors_precomp.shape[1])
-        sh_coeffs = sh.shape[1] if sh is not None else 0
-
-        with torch.cuda.device(device):
-            view, keep = _make_view(rs, sh_coeffs, flags, device, channels)
-            g = _lib.GsrGaussians(N, _ptr(means3D), _ptr(sh), _ptr(colors_precomp), _ptr(opacities),
-                                  _ptr(scales), _ptr(rotations), _ptr(cov3Ds_precomp), None)
-            color = torch.empty((channels, H, W), dtype=torch.float32, device=device)
-            allmap = torch.empty((7, H, W), dtype=torch.float32, device=device)
-            radii = torch.empty((N,), dtype=torch.int32, device=device)
-            out = _lib.GsrForwardOut(color.data_ptr(), allmap.data_ptr(), radii.data_ptr(), 0, None, None, None)
-            alloc = _Allocator(device)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            rc = L.gsr_forward(C.byref(view), C.byref(g), C.byref(out), alloc.cb, None, C.c_void_p(stream))
-            alloc.done()
-            if rc != 0 and alloc.error is not None:
-                raise alloc.error
-            _lib.check(rc)
-
-        ctx.lease = alloc.kept          # geom / binning / image go back to the pool with this node
-        ctx.channels = channels
-        ctx.raster_settings = rs
-        ctx.flags = flags
-        ctx.num_rendered = int(out.num_rendered)
-        ctx.view_keep = keep
-        ctx.set_materialize_grads(False)     # no zero tensors for the unused radii / image gradients
-        ctx.none_mask = (sh is None, colors_precomp is None, scales is None, cov3Ds_precomp is None)
-        geom = alloc.buffers[_lib.GSR_BUF_GEOM]
-        binning = alloc.buffers[_lib.GSR_BUF_BINNING]
-        image = alloc.buffers[_lib.GSR_BUF_IMAGE]
-        empty = torch.empty(0, device=device)
-        ctx.save_for_backward(means3D, sh if sh is not None else empty,
-                              colors_precomp if colors_precomp is not None else empty, opacities,
-                              scales if scales is not None else empty,
-                              rotations if rotations is not None else empty,
-                              cov3Ds_precomp if cov3Ds_precomp is not None else empty,
-                              radii, geom, binning, image)
+        tensors, g, channels, sh_coeffs = _pack_reference(means3D, sh, colors_precomp, opacities, scales, rotations,
+                                                          cov3Ds_precomp)
+        color, radii, allmap, num_rendered, alloc, keep = _forward(raster_settings, g, sh_coeffs, flags, channels,
+                                                                   means3D.device)
+        buffers = _keep_for_backward(ctx, raster_settings, g, sh_coeffs, flags, channels, num_rendered, alloc, keep)
+        ctx.save_for_backward(*tensors, radii, *buffers)        # (an absent input is saved as None)
         ctx.mark_non_differentiable(radii)
         return color, radii, allmap
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, grad_allmap):
-        L = _lib.lib()
         _check_lease(ctx)
-        (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, radii, geom,
-         binning, image) = ctx.saved_tensors
-        no_sh, no_col, no_sr, no_cov = ctx.none_mask
-        sh = None if no_sh else sh
-        colors_precomp = None if no_col else colors_precomp
-        scales = None if no_sr else scales
-        rotations = None if no_sr else rotations
-        cov3Ds_precomp = None if no_cov else cov3Ds_precomp
-        rs = ctx.raster_settings
+        means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, *buffers = ctx.saved_tensors
         device = means3D.device
         N = means3D.shape[0]
-        H, W = int(rs.image_height), int(rs.image_width)
-        grad_color = _f32c(grad_color, "grad_color", device) if grad_color is not None else \
-            _zero_image(ctx.channels, H, W, device)
-        # nothing was differentiated through allmap (e.g. lambda_normal = lambda_dist = 0): the backward is told so
-        bwd_flags = ctx.flags | (_lib.GSR_FLAG_NO_SURFACE_GRAD if (grad_allmap is None and _NO_SURFACE_FAST_PATH) else 0)
-        grad_allmap = _f32c(grad_allmap, "grad_allmap", device) if grad_allmap is not None else \
-            _zero_image(7, H, W, device)
-
-        with torch.cuda.device(device):
-            view, keep = _make_view(rs, sh.shape[1] if sh is not None else 0, bwd_flags, device, ctx.channels, ctx.view_keep)
-            g = _lib.GsrGaussians(N, _ptr(means3D), _ptr(sh), _ptr(colors_precomp), _ptr(opacities),
-                                  _ptr(scales), _ptr(rotations), _ptr(cov3Ds_precomp), None)
-            d_means3D = torch.empty_like(means3D)
-            d_means2D = torch.empty((N, 3), dtype=torch.float32, device=device)
-            d_opac = torch.empty_like(opacities)
-            d_sh = torch.empty_like(sh) if sh is not None else None
-            d_col = torch.empty_like(colors_precomp) if colors_precomp is not None else None
-            d_scales = torch.empty_like(scales) if scales is not None else None
-            d_rot = torch.empty_like(rotations) if rotations is not None else None
-            d_cov = torch.empty_like(cov3Ds_precomp) if cov3Ds_precomp is not None else None
-            grads = _lib.GsrGrads(_ptr(d_means3D), _ptr(d_means2D), _ptr(d_opac), _ptr(d_sh), _ptr(d_col),
-                                  _ptr(d_scales), _ptr(d_rot), _ptr(d_cov), None)
-            alloc = _Allocator(device)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            rc = L.gsr_backward(C.byref(view), C.byref(g), ctx.num_rendered, _ptr(radii), _ptr(geom),
-                                _ptr(binning), _ptr(image), _ptr(grad_color), _ptr(grad_allmap),
-                                C.byref(grads), alloc.cb, None, C.c_void_p(stream))
-            alloc.done()
-            if rc != 0 and alloc.error is not None:
-                raise alloc.error
-            _lib.check(rc)
-        del keep
-        _finish_lease(ctx)
+        grad_color, grad_allmap, flags = _grad_images(ctx, grad_color, grad_allmap, device)
+        d_means3D = torch.empty_like(means3D)
+        d_means2D = torch.empty((N, 3), dtype=torch.float32, device=device)
+        d_opac = torch.empty_like(opacities)
+        d_sh, d_col, d_scales, d_rot, d_cov = [torch.empty_like(t) if t is not None else None
+                                               for t in (sh, colors_precomp, scales, rotations, cov3Ds_precomp)]
+        grads = _lib.GsrGrads(_ptr(d_means3D), _ptr(d_means2D), _ptr(d_opac), _ptr(d_sh), _ptr(d_col),
+                              _ptr(d_scales), _ptr(d_rot), _ptr(d_cov), None)
+        _backward(ctx, flags, grad_color, grad_allmap, grads, buffers)
         return (d_means3D, d_means2D, d_sh, d_col, d_opac, d_scales, d_rot, d_cov, None, None)
 
 
@@ -439,27 +481,15 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, means2D, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, raster_settings, flags,
                 color_cache=None, state=None, color_only=False, no_dist_median=False):
-        L = _lib.lib()
         device = xyz.device
-        if device.type != "cuda":
-            raise _lib.GsrError("GaussianRasterizer needs tensors on a HIP device (torch 'cuda'); there is no CPU path")
         rs = raster_settings
-        N = xyz.shape[0]
-        H, W = int(rs.image_height), int(rs.image_width)
-        xyz, f_dc, f_rest = _f32c(xyz, "xyz", device), _f32c(f_dc, "features_dc", device), _f32c(f_rest, "features_rest", device)
-        opacity_raw, scaling_raw = _f32c(opacity_raw, "opacity", device), _f32c(scaling_raw, "scaling", device)
-        rotation_raw = _f32c(rotation_raw, "rotation", device)
-        if f_dc.dim() != 3 or f_dc.shape[1] != 1 or f_rest.dim() != 3 or f_rest.shape[0] != N:
-            raise ValueError("features_dc must be [N,1,3] and features_rest [N,K-1,3]")
-        M = 1 + f_rest.shape[1]
+        tensors, g, M = _pack_raw(xyz, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, color_cache)
         flags = int(flags) | _lib.GSR_FLAG_RAW_PARAMS
         if color_only:                    # the caller does not consume allmap (no regularizer active): not accumulated, not written
             flags |= _lib.GSR_FLAG_COLOR_ONLY
         elif no_dist_median:              # ... or not its distortion / median-depth channels (lambda_dist = 0, depth_ratio = 0)
             flags |= _lib.GSR_FLAG_NO_DIST_MEDIAN
         if color_cache is not None:       # the SH colour of this view was left by the optimiser step (FusedAdam.color_cache)
-            if color_cache.numel() != 13 * N or color_cache.dtype != torch.float32 or color_cache.device != device:
-                raise ValueError("color_cache must be float32 [13 N] on the parameters' device")
             flags |= _lib.GSR_FLAG_COLOR_CACHED
         pending = state.pop_pending() if state is not None else None
         hook = color_stream = None
@@ -469,43 +499,17 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             if color_stream is not None and color_stream == torch.cuda.current_stream(device):
                 color_stream = None
             hook = lambda: torch.cuda.current_stream(device).wait_event(pending_event)
-        rest = f_rest if f_rest.shape[1] > 0 else None
-        with torch.cuda.device(device):
-            view, keep = _make_view(rs, M, flags, device)
-            g = _lib.GsrGaussians(N, _ptr(xyz), _ptr(f_dc), _ptr(color_cache), _ptr(opacity_raw), _ptr(scaling_raw),
-                                  _ptr(rotation_raw), None, _ptr(rest) if rest is not None else None)
-            color = torch.empty((3, H, W), dtype=torch.float32, device=device)
-            allmap = torch.empty((7, H, W), dtype=torch.float32, device=device)
-            radii = torch.empty((N,), dtype=torch.int32, device=device)
-            out = _lib.GsrForwardOut(color.data_ptr(), allmap.data_ptr(), radii.data_ptr(), 0, None, None, None)
-            alloc = _Allocator(device, before_color=hook, color_stream=color_stream)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            rc = L.gsr_forward(C.byref(view), C.byref(g), C.byref(out), alloc.cb, None, C.c_void_p(stream))
-            alloc.done()
-            if alloc.before_color is not None:       # the library returned before announcing the colour pass
-                alloc.before_color()
-            if rc != 0 and alloc.error is not None:
-                raise alloc.error
-            _lib.check(rc)
-        ctx.lease = alloc.kept
-        ctx.raster_settings, ctx.flags, ctx.num_rendered, ctx.M = rs, flags & ~_lib.GSR_FLAG_DEFER_COLOR, int(out.num_rendered), M
-        ctx.view_keep = keep
+        color, radii, allmap, num_rendered, alloc, keep = _forward(rs, g, M, flags, 3, device, hook, color_stream)
+        buffers = _keep_for_backward(ctx, rs, g, M, flags & ~_lib.GSR_FLAG_DEFER_COLOR, 3, num_rendered, alloc, keep)
         ctx.color_cache = color_cache        # (the backward reads d(rgb)/d(dir) from it)
         ctx.state = state                    # (the backward leaves the factored SH gradient there)
         ctx.row_scan_job = None
-        if _ROW_SCAN_RIDE and int(out.num_rendered) > 0:
-            job = _lib.GsrRowScanJob()
-            _lib.check(L.gsr_row_scan_job(C.c_void_p(alloc.buffers[_lib.GSR_BUF_BINNING].data_ptr()), int(out.num_rendered),
-                                          W, H, C.byref(job)))
-            job._lease = alloc.kept            # keeps BINNING out of the pool while anybody may still write into it
-            job._stream = stream               # the hand-over is ordered by this stream and nothing else
-            job._taken = job._dead = False
+        if _ROW_SCAN_RIDE and num_rendered > 0:
+            job = _RowScanJob(alloc.kept, alloc.stream)
+            _lib.check(_lib.lib().gsr_row_scan_job(C.c_void_p(buffers[1].data_ptr()), num_rendered,
+                                                   int(rs.image_width), int(rs.image_height), C.byref(job)))
             ctx.row_scan_job = job             # found by the objective through image.grad_fn (take_row_scan_job)
-        ctx.set_materialize_grads(False)     # no zero tensors for the unused radii / image gradients
-        ctx.save_for_backward(xyz, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, radii,
-                              alloc.buffers[_lib.GSR_BUF_GEOM], alloc.buffers[_lib.GSR_BUF_BINNING],
-                              alloc.buffers[_lib.GSR_BUF_IMAGE])
-        del keep
+        ctx.save_for_backward(*tensors, radii, *buffers)
         if color_only:
             ctx.mark_non_differentiable(radii, allmap)       # (allmap was not written: rasterize_gaussians_raw hands back None)
         else:
@@ -514,77 +518,39 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, grad_allmap):
-        L = _lib.lib()
         _check_lease(ctx)
-        xyz, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, radii, geom, binning, image = ctx.saved_tensors
-        if ctx.flags & _lib.GSR_FLAG_COLOR_ONLY:
-            grad_allmap = None
-        rs = ctx.raster_settings
+        xyz, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, *buffers = ctx.saved_tensors
         device = xyz.device
         N = xyz.shape[0]
-        H, W = int(rs.image_height), int(rs.image_width)
-        grad_color = _f32c(grad_color, "grad_color", device) if grad_color is not None else _zero_image(3, H, W, device)
-        # nothing was differentiated through allmap (the first 7,000 iterations, or lambda_normal = lambda_dist = 0)
-        bwd_flags = ctx.flags | (_lib.GSR_FLAG_NO_SURFACE_GRAD if (grad_allmap is None and (
-            _NO_SURFACE_FAST_PATH or ctx.flags & _lib.GSR_FLAG_COLOR_ONLY)) else 0)
-        grad_allmap = _f32c(grad_allmap, "grad_allmap", device) if grad_allmap is not None else _zero_image(7, H, W, device)
-        rest = f_rest if f_rest.shape[1] > 0 else None
-        with torch.cuda.device(device):
-            view, keep = _make_view(rs, ctx.M, bwd_flags, device, 3, ctx.view_keep)
-            g = _lib.GsrGaussians(N, _ptr(xyz), _ptr(f_dc), _ptr(ctx.color_cache), _ptr(opacity_raw), _ptr(scaling_raw),
-                                  _ptr(rotation_raw), None, _ptr(rest) if rest is not None else None)
-            # ONE buffer for the six parameter gradients, [xyz | f_dc | opacity | scaling | rotation | f_rest]: the
-            # data-parallel step all-reduces it as a whole (or as "geometry + dc" / "rest" halves) without copies
-            d_2d = torch.empty((N, 3), dtype=torch.float32, device=device)
-            factored = bool(ctx.flags & _lib.GSR_FLAG_FACTORED_SH_GRAD)
-            srcs = (xyz, opacity_raw, scaling_raw, rotation_raw) if factored else \
-                (xyz, f_dc, opacity_raw, scaling_raw, rotation_raw, f_rest)
-            offs, total = [], 0
-            for t in srcs:                       # every segment starts 16-byte aligned (K8 stores float4)
-                offs.append(total)
-                total += _round_up(t.numel(), 4)
-            if factored:
-                # [xyz | opacity | scaling | rotation | colour gradient [N,3] + camera position]: 13 floats per Gaussian
-                n_head = total
-                flat = torch.empty(n_head + 3 * N + 4, dtype=torch.float32, device=device)
-                d_xyz, d_op, d_sc, d_rot = [flat[o:o + t.numel()].view_as(t) for o, t in zip(offs, srcs)]
-                d_dc = d_rest = None
-                record = flat[n_head:]
-                grads = _lib.GsrGrads(_ptr(d_xyz), _ptr(d_2d), _ptr(d_op), None, _ptr(record), _ptr(d_sc), _ptr(d_rot),
-                                      None, None)
-            else:
-                flat = torch.empty(total, dtype=torch.float32, device=device)
-                d_xyz, d_dc, d_op, d_sc, d_rot, d_rest = [flat[o:o + t.numel()].view_as(t) for o, t in zip(offs, srcs)]
-                grads = _lib.GsrGrads(_ptr(d_xyz), _ptr(d_2d), _ptr(d_op), _ptr(d_dc), None, _ptr(d_sc), _ptr(d_rot), None,
-                                      _ptr(d_rest) if rest is not None else None)
-            alloc = _Allocator(device)
-            stream = torch.cuda.current_stream(device).cuda_stream
-            job = getattr(ctx, "row_scan_job", None)
-            if job is not None:
-                # whatever happens below, nobody may enqueue a half of this job any more: after this backward the buffers
-                # go back to the pool (an objective holding the job checks row_scan_job_alive before it launches)
-                usable = not job._dead and job._stream == stream      # else: not the stream the hand-over was ordered by
-                job._dead = True
-                job._lease = None
-                if not usable:
-                    job = None
-            if job is not None:
-                rc = L.gsr_backward_with_job(C.byref(view), C.byref(g), ctx.num_rendered, _ptr(radii), _ptr(geom),
-                                             _ptr(binning), _ptr(image), _ptr(grad_color), _ptr(grad_allmap), C.byref(grads),
-                                             C.byref(job), alloc.cb, None, C.c_void_p(stream))
-                STATS["row_scans_carried"] += int(job.stage == 2)
-            else:
-                rc = L.gsr_backward(C.byref(view), C.byref(g), ctx.num_rendered, _ptr(radii), _ptr(geom), _ptr(binning),
-                                    _ptr(image), _ptr(grad_color), _ptr(grad_allmap), C.byref(grads), alloc.cb, None,
-                                    C.c_void_p(stream))
-            alloc.done()
-            if rc != 0 and alloc.error is not None:
-                raise alloc.error
-            _lib.check(rc)
-        del keep
-        _finish_lease(ctx)
+        grad_color, grad_allmap, flags = _grad_images(ctx, grad_color, grad_allmap, device)
+        # ONE buffer for the six parameter gradients, [xyz | f_dc | opacity | scaling | rotation | f_rest]: the
+        # data-parallel step all-reduces it as a whole (or as "geometry + dc" / "rest" halves) without copies
+        d_2d = torch.empty((N, 3), dtype=torch.float32, device=device)
+        factored = bool(ctx.flags & _lib.GSR_FLAG_FACTORED_SH_GRAD)
+        srcs = (xyz, opacity_raw, scaling_raw, rotation_raw) if factored else \
+            (xyz, f_dc, opacity_raw, scaling_raw, rotation_raw, f_rest)
+        offs, total = [], 0
+        for t in srcs:                       # every segment starts 16-byte aligned (K8 stores float4)
+            offs.append(total)
+            total += _round_up(t.numel(), 4)
         if factored:
-            ctx.state.color_grad = ColorGradRecord(flat, flat[:n_head], record, N, ctx.M, rs.sh_degree, xyz)
+            # [xyz | opacity | scaling | rotation | colour gradient [N,3] + camera position]: 13 floats per Gaussian
+            n_head = total
+            flat = torch.empty(n_head + 3 * N + 4, dtype=torch.float32, device=device)
+            d_xyz, d_op, d_sc, d_rot = [flat[o:o + t.numel()].view_as(t) for o, t in zip(offs, srcs)]
+            d_dc = d_rest = None
+            record = flat[n_head:]
+            grads = _lib.GsrGrads(_ptr(d_xyz), _ptr(d_2d), _ptr(d_op), None, _ptr(record), _ptr(d_sc), _ptr(d_rot),
+                                  None, None)
+        else:
+            flat = torch.empty(total, dtype=torch.float32, device=device)
+            d_xyz, d_dc, d_op, d_sc, d_rot, d_rest = [flat[o:o + t.numel()].view_as(t) for o, t in zip(offs, srcs)]
+            grads = _lib.GsrGrads(_ptr(d_xyz), _ptr(d_2d), _ptr(d_op), _ptr(d_dc), None, _ptr(d_sc), _ptr(d_rot), None,
+                                  _ptr(d_rest) if f_rest.shape[1] > 0 else None)
+        _backward(ctx, flags, grad_color, grad_allmap, grads, buffers, ctx.row_scan_job)
+        if factored:
+            ctx.state.color_grad = ColorGradRecord(flat, flat[:n_head], record, N, ctx.sh_coeffs,
+                                                   ctx.raster_settings.sh_degree, xyz)
         return d_xyz, d_2d, d_dc, d_rest, d_op, d_sc, d_rot, None, None, None, None, None, None
 
 
@@ -592,30 +558,12 @@ def _wants_grad(*tensors):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
-def _forward_only(device, rs, flags, sh_coeffs, gaussians_args, N):
+def _forward_only(rs, g, sh_coeffs, flags, device):
     """Inference path (render.py / view.py / GaussianExtractor under torch.no_grad(): utils/mesh_utils.py:100-123,
     view.py:15-31): GSR_FLAG_FORWARD_ONLY -- no touch words, no per-pixel state, no autograd node, and every library
     buffer goes back to the pool as soon as the call has been enqueued (stream-ordered reuse)."""
-    L = _lib.lib()
-    if device.type != "cuda":
-        raise _lib.GsrError("GaussianRasterizer needs tensors on a HIP device (torch 'cuda'); there is no CPU path")
-    H, W = int(rs.image_height), int(rs.image_width)
-    with torch.cuda.device(device):
-        view, keep = _make_view(rs, sh_coeffs, int(flags) | _lib.GSR_FLAG_FORWARD_ONLY, device)
-        g = _lib.GsrGaussians(N, *[_ptr(a) for a in gaussians_args])
-        color = torch.empty((3, H, W), dtype=torch.float32, device=device)
-        allmap = torch.empty((7, H, W), dtype=torch.float32, device=device)
-        radii = torch.empty((N,), dtype=torch.int32, device=device)
-        out = _lib.GsrForwardOut(color.data_ptr(), allmap.data_ptr(), radii.data_ptr(), 0, None, None, None)
-        alloc = _Allocator(device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        rc = L.gsr_forward(C.byref(view), C.byref(g), C.byref(out), alloc.cb, None, C.c_void_p(stream))
-        alloc.done()
-        alloc.kept.release()
-        if rc != 0 and alloc.error is not None:
-            raise alloc.error
-        _lib.check(rc)
-    del keep
+    color, radii, allmap, _, alloc, _ = _forward(rs, g, sh_coeffs, int(flags) | _lib.GSR_FLAG_FORWARD_ONLY, 3, device)
+    alloc.kept.release()
     return color, radii, allmap
 
 
@@ -636,17 +584,11 @@ def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_ra
     if factored_sh_grad and state is None:
         raise ValueError("factored_sh_grad needs state=RasterState(): the backward leaves its colour-gradient record there")
     if not _wants_grad(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw):
-        device = xyz.device
         if state is not None:
-            state.wait_pending(device)
-        args = [_f32c(t, n, device) for t, n in ((xyz, "xyz"), (features_dc, "features_dc"), (None, ""), (opacity_raw, "opacity"),
-                                                 (scaling_raw, "scaling"), (rotation_raw, "rotation"), (None, ""))]
-        rest = _f32c(features_rest, "features_rest", device)
-        if args[1].dim() != 3 or args[1].shape[1] != 1 or rest.dim() != 3 or rest.shape[0] != xyz.shape[0]:
-            raise ValueError("features_dc must be [N,1,3] and features_rest [N,K-1,3]")
-        args.append(rest if rest.shape[1] > 0 else None)
-        return _forward_only(device, raster_settings, int(flags) | _lib.GSR_FLAG_RAW_PARAMS, 1 + rest.shape[1], args,
-                             xyz.shape[0])
+            state.wait_pending(xyz.device)
+        # (`inputs`: the tensors g points at, kept alive until the call has been enqueued)
+        inputs, g, M = _pack_raw(xyz, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw)
+        return _forward_only(raster_settings, g, M, int(flags) | _lib.GSR_FLAG_RAW_PARAMS, xyz.device)
     if factored_sh_grad:
         flags |= _lib.GSR_FLAG_FACTORED_SH_GRAD
     color, radii, allmap = _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
@@ -658,19 +600,13 @@ def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_ra
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
                         cov3Ds_precomp, raster_settings, flags=None):
+    flags = DEFAULT_FLAGS if flags is None else flags
     wide = colors_precomp is not None and colors_precomp.dim() == 2 and colors_precomp.shape[1] != 3
     if not wide and not _wants_grad(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp):
-        device = means3D.device
-        args = [_f32c(t, n, device) for t, n in ((means3D, "means3D"), (sh, "shs"), (colors_precomp, "colors_precomp"),
-                                                 (opacities, "opacities"), (scales, "scales"), (rotations, "rotations"),
-                                                 (cov3Ds_precomp, "cov3D_precomp"))] + [None]
-        if args[2] is not None and (args[2].dim() != 2 or args[2].shape[0] != means3D.shape[0]):
-            raise _lib.GsrError("colors_precomp must be [N,C]")
-        return _forward_only(device, raster_settings, DEFAULT_FLAGS if flags is None else flags,
-                             sh.shape[1] if sh is not None else 0, args, means3D.shape[0])
+        inputs, g, _, sh_coeffs = _pack_reference(means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp)
+        return _forward_only(raster_settings, g, sh_coeffs, flags, means3D.device)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales,
-                                     rotations, cov3Ds_precomp, raster_settings,
-                                     DEFAULT_FLAGS if flags is None else flags)
+                                     rotations, cov3Ds_precomp, raster_settings, flags)
 
 
 class GaussianRasterizer(nn.Module):
@@ -701,30 +637,15 @@ def rasterize_debug(means3D, opacities, shs=None, colors_precomp=None, scales=No
                     cov3D_precomp=None, *, raster_settings, flags=None):
     """Forward only, returning the operator outputs AND typed views of every saved buffer field
     (include/gsr.h: gsr_buffer_field).  Used by the parity tests; no autograd."""
-    L = _lib.lib()
     device = means3D.device
     rs = raster_settings
-    flags = DEFAULT_FLAGS if flags is None else flags
-    N = means3D.shape[0]
+    inputs, g, channels, sh_coeffs = _pack_reference(means3D, shs, colors_precomp, opacities, scales, rotations,
+                                                     cov3D_precomp)
+    color, radii, allmap, D, alloc, _ = _forward(rs, g, sh_coeffs, DEFAULT_FLAGS if flags is None else flags, channels,
+                                                 device)
+    torch.cuda.synchronize(device)
+    N = g.count
     H, W = int(rs.image_height), int(rs.image_width)
-    args = [_f32c(t, n, device) for t, n in ((means3D, "means3D"), (shs, "shs"), (colors_precomp, "colors"),
-                                             (opacities, "opacities"), (scales, "scales"),
-                                             (rotations, "rotations"), (cov3D_precomp, "cov3D"))]
-    with torch.cuda.device(device), torch.no_grad():
-        view, keep = _make_view(rs, args[1].shape[1] if args[1] is not None else 0, flags, device)
-        g = _lib.GsrGaussians(N, *[_ptr(a) for a in args], None)
-        color = torch.empty((3, H, W), dtype=torch.float32, device=device)
-        allmap = torch.empty((7, H, W), dtype=torch.float32, device=device)
-        radii = torch.empty((N,), dtype=torch.int32, device=device)
-        out = _lib.GsrForwardOut(color.data_ptr(), allmap.data_ptr(), radii.data_ptr(), 0, None, None, None)
-        alloc = _Allocator(device)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        rc = L.gsr_forward(C.byref(view), C.byref(g), C.byref(out), alloc.cb, None, C.c_void_p(stream))
-        if rc != 0 and alloc.error is not None:
-            raise alloc.error
-        _lib.check(rc)
-        torch.cuda.synchronize(device)
-    D = int(out.num_rendered)
     # the views below alias pooled buffers: the lease keeps them out of the pool while `res` lives
     res = dict(color=color, allmap=allmap, radii=radii, num_rendered=D, _lease=alloc.kept)
     spec = {
@@ -739,16 +660,10 @@ def rasterize_debug(means3D, opacities, shs=None, colors_precomp=None, scales=No
     for which, fields in spec.items():
         buf = alloc.buffers[which]
         for name, dt, shape in fields:
-            try:
-                off, nbytes = _lib.buffer_field(which, name, N, D, W, H)
-            except _lib.GsrError:
-                if name not in ("covered", "touch", "row_count"):   # (an older library build, loaded through GSR_LIB_PATH for an A/B run)
-                    raise
-                continue
+            off, nbytes = _lib.buffer_field(which, name, N, D, W, H)
             res[name] = buf[off:off + nbytes].view(dt).reshape(shape) if nbytes else \
                 torch.empty(0, dtype=dt, device=device).reshape([s if s >= 0 else 0 for s in shape])
     # first emission index of every Gaussian (depth rank r = order^-1): offs is indexed by rank
     res["inst_begin"] = torch.zeros(N, dtype=torch.int32, device=device)
     res["inst_begin"][res["order"].long()] = res["offs"][:N]
-    del keep
     return res

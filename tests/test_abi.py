@@ -56,8 +56,14 @@ def test_operators_have_no_cpu_path():
     rs = hip_settings(cam, device="cpu")
     assert isinstance(rs, GaussianRasterizationSettings)
     rast = GaussianRasterizer(rs)
-    with pytest.raises(_lib.GsrError, match="no CPU path"):
-        rast(a["means3D"], torch.zeros(10, 3), a["opacities"], shs=a["shs"], scales=a["scales"], rotations=a["rotations"])
+    from gaussmart_amd.rasterizer import rasterize_gaussians_raw
+    for grad in (False, True):        # the forward-only path and the autograd path of both signatures
+        with pytest.raises(_lib.GsrError, match="no CPU path"):
+            rast(a["means3D"].clone().requires_grad_(grad), torch.zeros(10, 3), a["opacities"], shs=a["shs"],
+                 scales=a["scales"], rotations=a["rotations"])
+        with pytest.raises(_lib.GsrError, match="no CPU path"):
+            rasterize_gaussians_raw(p["xyz"].clone().requires_grad_(grad), torch.zeros(10, 3), p["features_dc"],
+                                    p["features_rest"], p["opacity"], p["scaling"], p["rotation"], rs)
     with pytest.raises(_lib.GsrError, match="no CPU path"):
         distCUDA2(a["means3D"])
     with pytest.raises(Exception, match="SHs or precomputed colors"):

@@ -47,6 +47,15 @@ def test_row_scan_job_is_found_through_the_image_and_retired(monkeypatch):
     dead = types.SimpleNamespace(_taken=False, _dead=True, _stream=1234)
     assert R.take_row_scan_job(image_with(dead)) is None
     assert R.row_scan_job_alive(job) and not R.row_scan_job_alive(dead) and not R.row_scan_job_alive(None)
+    # the objective's check before its second half: alive and on the stream the job was ordered on
+    assert R.row_scan_job_usable(job, 1234) and not R.row_scan_job_usable(job, 99)
+    assert not R.row_scan_job_usable(dead, 1234) and not R.row_scan_job_usable(None, 1234)
+    # the rasterizer's backward retires the job whether it can use it or not, and lets its lease go
+    real = R._RowScanJob("lease", 1234)
+    assert R.take_row_scan_job(image_with(real)) is real and real.stage == 0
+    assert not R._retire_row_scan_job(real, 99) and real._dead and real._lease is None
+    assert not R.row_scan_job_usable(real, 1234) and R.take_row_scan_job(image_with(real)) is None
+    assert R._retire_row_scan_job(job, 1234) and not R.row_scan_job_alive(job)
 
 
 def test_factored_gradient_needs_a_state_and_cpu_tensors_are_refused():
