@@ -19,7 +19,7 @@ sys.path.insert(0, ROOT)
 
 
 def main():
-    os.environ.setdefault("FARM_WORKERS", sys.argv[1] if len(sys.argv) > 1 else "6")
+    os.environ.setdefault("FARM_WORKERS", sys.argv[1] if len(sys.argv) > 1 else "4")
     import oracle_farm as F
     # importing the test modules registers their cases
     import test_gpu_rasterizer, test_gpu_deep_lists, test_gpu_wide_payload  # noqa: F401

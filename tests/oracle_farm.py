@@ -119,6 +119,7 @@ def summarize(gh, go, n, rows=None, d=None, trim=0):
     return dict(normwise=(float(dk[trim]) if dk.numel() else 0.0) / max(sc, 1e-30),
                 trimmed_max=(float(dk[0]) if dk.numel() and trim else 0.0) / max(sc, 1e-30),
                 median=float(rel[sel].median()) if sel.any() else 0.0,
+                p90=float(rel[sel].quantile(0.90)) if sel.any() else 0.0,
                 p99=float(rel[sel].quantile(0.99)) if sel.any() else 0.0, active=int(sel.sum()))
 
 
@@ -138,8 +139,9 @@ def _oracle_once(sp, a, cam, bg, wc, wa, dtype):
     return g, c.detach().double(), am.detach().double(), r, S
 
 
-def run_case(sp):
-    """The oracle side of one case -> dict of NumPy arrays / plain numbers (picklable)."""
+def run_case(sp, keep32=False):
+    """The oracle side of one case -> dict of NumPy arrays / plain numbers (picklable).  keep32: also hand back the fp32
+    oracle's gradients themselves ("grads32"), for a caller that lets them stand in for the HIP side."""
     torch.set_num_threads(int(os.environ.get("FARM_TORCH_THREADS", "1")))
     from oracle import surfel_ref as O
     a, cam, bg, wc, wa = build_inputs(sp)
@@ -155,6 +157,8 @@ def run_case(sp):
     if sp["want32"]:
         out["d32"] = {k: (g32[k] - go[k]).abs().reshape(n, -1).amax(1).numpy().copy() for k in go}
         out["stats32"] = {k: summarize(g32[k], go[k], n) for k in go}
+        if keep32:
+            out["grads32"] = {k: v.numpy().copy() for k, v in g32.items()}
     lens = (L["ranges"][:, 1].astype(np.int64) - L["ranges"][:, 0].astype(np.int64))
     out["lists"] = dict(mean=float(lens.mean()), max=int(lens.max()), walked=int(L["n_contrib"][0].max()),
                         mean_depth=float(L["n_contrib"][0].double().mean()))
@@ -180,6 +184,9 @@ def _worker(sp):
         return {"error": f"{type(e).__name__}: {e}\n{traceback.format_exc()}"}
 
 
+MAX_WORKERS = 4      # see Farm.start: the processes-per-card limit of the GPU boxes
+
+
 class Farm:
     def __init__(self):
         self.specs, self.costs, self.futures, self.cache, self.done = {}, {}, {}, {}, {}
@@ -195,6 +202,9 @@ class Farm:
     def start(self, keys=None):
         keys = [k for k in (self.specs if keys is None else keys) if k in self.specs and k not in self.futures]
         workers = int(os.environ.get("FARM_WORKERS", "-1"))
+        assert workers <= MAX_WORKERS, (
+            f"FARM_WORKERS={workers}: at most {MAX_WORKERS} oracle workers -- every worker opens the GPU's device files at its "
+            f"first backward(), and the processes-per-card limit of the GPU boxes is six (the test process, {MAX_WORKERS} workers, one spare)")
         if workers < 0:
             try:
                 cores = len(os.sched_getaffinity(0))
@@ -204,7 +214,7 @@ class Farm:
             # opens the device files even for CPU-only work (no environment variable prevents it: measured,
             # scripts/dev_farm_probe.py), and the GPU boxes allow six processes on the card at once -- the test process,
             # four workers, one spare.  Tests that start GPU ranks of their own call FARM.drain() first.
-            workers = max(1, min(4, cores - 3, len(keys)))
+            workers = max(1, min(MAX_WORKERS, cores - 3, len(keys)))
         if workers == 0 or not keys:
             return 0
         try:
@@ -299,57 +309,149 @@ def check_against_committed_checksums(key, res, rtol=1e-6):
 #     normwise<= K_TAIL * normwise_fp32 + 2e-4     and <= CAP_NORMWISE
 # (round 3 asserted fixed bars -- normwise < 1e-3, p99 < 2e-3 -- and the shipped build passed one of them by 4 %.)
 # These bars hold on the DECISION-STABLE rows: Gaussians that blend into no pixel holding a decision with a relative margin
-# below 1e-3 (the oracle names them; radii that round differently count too).  On the others one flipped decision moves a
-# row by a finite amount whatever the arithmetic (round 4's second seed of the 2k scene: a flip HIP takes and the fp32
-# oracle does not moved one `means3D` row by 1.3e-3 of the scale): those rows only have to stay under FLIP_CAP, and at most
-# max(2, 0.2 %) of them may exceed FLIP_BIG.  The norm-wise figure is a MAXIMUM over ~2,000 rows: it leaves out the worst row per
-# thousand (at least one), which is held to FLIP_CAP instead -- the oracle's margin test at 1e-3 cannot name every pair an
+# below 1e-3 (the oracle names them; radii that round differently count too).  On the others -- the FLIP-SENSITIVE rows,
+# 21-37 % of a case -- one flipped decision moves a row by a finite amount whatever the arithmetic (round 4's second seed
+# of the 2k scene: a flip HIP takes and the fp32 oracle does not moved one `means3D` row by 1.3e-3 of the scale).  That only
+# touches their extreme tail: in bulk they are no noisier than the stable rows (fp32 oracle vs fp64, every tensor of every
+# case of tests/golden/oracle_flip_levels.json: the median of the flip-sensitive rows is <= 6.2e-6 and their p90 <= 4.0e-5,
+# the level of the stable rows of the same tensor and far below the 1e-4 cap).  So they carry relative bars of their own,
+# against the fp32 oracle's statistics over the SAME rows, with the factors and floors of the stable rows:
+#     flip median <= 1e-4  and  <= K_MED * flip_median_fp32 + 1e-6       (at least FLIP_MIN_MEDIAN such rows carry gradient)
+#     flip p90    <= K_TAIL * flip_p90_fp32 + 2e-4                       (at least FLIP_MIN_P90 of them: a quantile of a
+#                                                                         handful of rows is a single row)
+#     below FLIP_MIN_MEDIAN rows: every one of them <= FLIP_BIG of the scale
+# and above the p90 the flips themselves: every flip-sensitive row stays under FLIP_CAP of the scale, and at most
+# max(2, 0.2 %) of them may exceed FLIP_BIG.  Every row of a case is thus in exactly one of two populations, each with
+# relative bars; no row is only capped.  (Before: a relative error of 1e-3 on EVERY flip-sensitive row of every tensor -- ten
+# times north_star's figure on a fifth of all Gaussians -- passed; tests/test_host_logic.py:
+# test_gradient_bars_notice_a_subtly_wrong_kernel.)
+# The norm-wise figure is a MAXIMUM over ~2,000 rows: it leaves out the worst row per thousand (at least one), which is
+# held to FLIP_CAP instead -- the oracle's margin test at 1e-3 cannot name every pair an
 # fp32 implementation with fast reciprocals / exponentials can flip (measured over 40 (case, tensor) entries: the kernels'
 # median and p99 errors are 0.8-1.05 x the fp32 oracle's, the maxima within 1.2 x, except ONE row of one scene at 8.8 x).
+#
+# FLIP_CAP is taken from the reference, not guessed: how far ONE flip moves a row is set by the scene, not by the arithmetic,
+# so the yardstick is the largest error / scale the fp32 oracle itself shows on a flip-sensitive row over all registered
+# cases that have an fp32 pass (tests/golden/oracle_flip_levels.json, written by tests/golden/make_oracle_flip_levels.py),
+# times 2 because HIP takes its OWN set of flips from the same population of near-threshold pairs, and never above the
+# 2e-2 it replaces:
+#     FLIP_CAP = min(2e-2, 2 * FLIP_LEVEL_MAX) = min(2e-2, 2 * 3.885e-3) = 7.77e-3      (random2k-s0-flags0 `scales`;
+#     over the 29 cases and 172 (case, tensor) entries of the file)
 def TRIM(n_rows):
     return max(1, n_rows // 1000)
 
 
+FLIP_LEVELS = os.path.join(ROOT, "tests", "golden", "oracle_flip_levels.json")
+
+
+def flip_level_max(path=FLIP_LEVELS):
+    """-> (largest fp32-oracle error / scale on a flip-sensitive row in the committed file, "case tensor" it belongs to)."""
+    levels = json.load(open(path))
+    return max((t["flip_max"], f"{case} {k}") for case, ts in levels.items() for k, t in ts.items())
+
+
 K_MED, K_TAIL = 3.0, 4.0
 CAP_P99, CAP_NORMWISE = 5e-3, 1e-2
-FLIP_CAP, FLIP_BIG = 2e-2, 2e-3
+FLIP_LEVEL_MAX = flip_level_max()[0]
+FLIP_CAP, FLIP_BIG = min(2e-2, 2.0 * FLIP_LEVEL_MAX), 2e-3
+FLIP_MIN_MEDIAN, FLIP_MIN_P90 = 10, 50
 REPORT = []      # rows (case, tensor, hip stats, fp32-oracle stats, worst bar usage): printed at session end, kept under profiles/
 
 
+def flip_sensitive_rows(res, radii_h):
+    """bool [N]: Gaussians that blend into a pixel holding a decision with margin < 1e-3 (the oracle names them), or whose
+    radius does not round the same way in all three evaluations (`radii_h`: the side under test).  The others are the
+    decision-stable rows."""
+    radii = torch.as_tensor(res["radii"])
+    return torch.as_tensor(res["sens"][1e-3][0]) | torch.as_tensor(res["ext_margin_small"]) | \
+        (torch.as_tensor(radii_h) != radii) | (torch.as_tensor(res["radii32"]) != radii)
+
+
+def compare_case(res, gh, radii_h):
+    """The side under test (gradients `gh` by name as float64, radii `radii_h`) against the oracle result `res` of a case
+    with an fp32 pass -> (stats, stats32, flips), what check_gradient_bars takes: per tensor the statistics of `gh` and of
+    the fp32 oracle over the decision-stable rows, and over the flip-sensitive rows
+        max / big / rows: largest error / scale, how many exceed FLIP_BIG, how many rows there are;
+        active, active_max: how many of them carry gradient, the largest error / scale among those;
+        median, p90 and median32, p90_32, max32: per-row relative error of `gh` and of the fp32 oracle over the same rows.
+    Pure CPU: the GPU parity tests and the CPU sensitivity test of the bars both come through here."""
+    sens = flip_sensitive_rows(res, radii_h)
+    stable = ~sens
+    n, trim = int(sens.numel()), TRIM(int(stable.sum()))
+    stats, stats32, flips = {}, {}, {}
+    for k in gh:
+        go, d32 = torch.as_tensor(res["grads"][k]), torch.as_tensor(res["d32"][k])
+        stats[k] = summarize(gh[k], go, n, rows=stable, trim=trim)
+        stats32[k] = summarize(None, go, n, rows=stable, d=d32, trim=trim)
+        fh, f32 = summarize(gh[k], go, n, rows=sens), summarize(None, go, n, rows=sens, d=d32)
+        d = (gh[k] - go).abs().reshape(n, -1).amax(1)
+        sc = max(float(go.abs().max()), 1e-30)
+        act = sens & (go.reshape(n, -1).abs().amax(1) > 1e-4 * sc)
+        flips[k] = dict(max=float(d[sens].max()) / sc if sens.any() else 0.0, big=int((d[sens] > FLIP_BIG * sc).sum()),
+                        rows=int(sens.sum()), active=fh["active"], active_max=float(d[act].max()) / sc if act.any() else 0.0,
+                        median=fh["median"], p90=fh["p90"], median32=f32["median"], p90_32=f32["p90"], max32=f32["normwise"])
+    return stats, stats32, flips
+
+
 def check_gradient_bars(case, hip_stats, f32_stats, tensors=None, flips=None):
-    """Asserts the bars above for every tensor (statistics over the decision-stable rows) and records the measured figures;
-    `flips`: per tensor (largest error / scale on the flip-sensitive rows, how many of them exceed FLIP_BIG, how many there
-    are).  Returns the worst fraction of a bar used."""
+    """Asserts the bars above for every tensor and records the measured figures.  hip_stats / f32_stats: statistics over the
+    decision-stable rows; `flips`: per tensor the figures of the flip-sensitive rows (compare_case).  Returns the worst
+    fraction of a bar used."""
     worst = 0.0
     for k, s in hip_stats.items():
         if tensors is not None and k not in tensors:
             continue
         r = f32_stats[k]
-        if flips is not None and k in flips:
-            f_max, f_big, f_n = flips[k]
-            assert f_max <= FLIP_CAP, f"{case}: {k}: a flip-sensitive row is off by {f_max:.2e} of the scale"
-            assert f_big <= max(2, f_n // 500), f"{case}: {k}: {f_big} of {f_n} flip-sensitive rows beyond {FLIP_BIG:g}"
-            s = dict(s, flip_rows=f_n, flip_max=f_max, flip_big=f_big)
-        assert s.get("trimmed_max", 0.0) <= FLIP_CAP, f"{case}: {k}: a decision-stable row is off by {s['trimmed_max']:.2e} of the scale"
         bars = dict(median=min(1e-4, K_MED * r["median"] + 1e-6),
                     p99=min(CAP_P99, K_TAIL * r["p99"] + 2e-4),
                     normwise=min(CAP_NORMWISE, K_TAIL * r["normwise"] + 2e-4))
         used = {m: s[m] / bars[m] for m in bars}
+        failed = []
+        if flips is not None and k in flips:
+            f = flips[k]
+            s = dict(s, flip_rows=f["rows"], flip_max=f["max"], flip_big=f["big"], flip=f)
+            if f["max"] > FLIP_CAP:
+                failed.append(f"a flip-sensitive row is off by {f['max']:.2e} of the scale (cap {FLIP_CAP:.2e})")
+            if f["big"] > max(2, f["rows"] // 500):
+                failed.append(f"{f['big']} of {f['rows']} flip-sensitive rows beyond {FLIP_BIG:g}")
+            used["flip_cap"] = f["max"] / FLIP_CAP
+            fbars = {}
+            if f["active"] >= FLIP_MIN_MEDIAN:
+                fbars["median"] = (min(1e-4, K_MED * f["median32"] + 1e-6), f["median32"])
+            elif f["active_max"] > FLIP_BIG:
+                failed.append(f"only {f['active']} flip-sensitive rows carry gradient and one is off by {f['active_max']:.2e} "
+                              f"of the scale (each must stay under {FLIP_BIG:g})")
+            if f["active"] >= FLIP_MIN_P90:
+                fbars["p90"] = (K_TAIL * f["p90_32"] + 2e-4, f["p90_32"])
+            for m, (bar, ref) in fbars.items():
+                used["flip_" + m] = f[m] / bar
+                if f[m] > bar:
+                    failed.append(f"flip-sensitive rows: {m} {f[m]:.3e} exceeds its bar {bar:.3e} (fp32 oracle on the same "
+                                  f"{f['active']} rows: {ref:.3e})")
+        if s.get("trimmed_max", 0.0) > FLIP_CAP:
+            failed.append(f"a decision-stable row is off by {s['trimmed_max']:.2e} of the scale (cap {FLIP_CAP:.2e})")
+        for m in bars:
+            if s[m] > bars[m]:
+                failed.append(f"{m} {s[m]:.3e} exceeds its bar {bars[m]:.3e} (fp32 oracle on the same scene: {r[m]:.3e})")
         REPORT.append((case, k, s, r, used))
         worst = max(worst, max(used.values()))
-        for m in bars:
-            assert s[m] <= bars[m], (f"{case}: {k} {m} {s[m]:.3e} exceeds its bar {bars[m]:.3e} "
-                                     f"(fp32 oracle on the same scene: {r[m]:.3e})")
+        assert not failed, f"{case}: {k}: " + "; ".join(failed)
     return worst
 
 
 def format_report():
     lines = ["case | tensor | decision-stable rows, HIP vs fp64: normwise median p99 | same rows, fp32 oracle vs fp64: normwise "
-             "median p99 | worst bar usage | flip-sensitive rows: count, largest error / scale, how many beyond 2e-3"]
+             "median p99 | worst bar usage | flip-sensitive rows: count, largest error / scale, how many beyond 2e-3 | worst stable "
+             "row(s) left out of normwise | flip-sensitive rows that carry gradient: count; HIP median p90; fp32 oracle median p90 "
+             f"max; usage of the flip median bar, of the flip p90 bar, of the cap (largest HIP flip row / FLIP_CAP = {FLIP_CAP:.2e})"]
     for case, k, s, r, used in REPORT:
+        f = s.get("flip")
+        u = lambda m: f"{used[m]:.2f}" if m in used else "-"
         lines.append(f"{case} | {k} | {s['normwise']:.2e} {s['median']:.2e} {s['p99']:.2e} | "
                      f"{r['normwise']:.2e} {r['median']:.2e} {r['p99']:.2e} | "
                      f"{max(used.values()):.2f} ({max(used, key=used.get)}) | "
                      + (f"{s['flip_rows']} {s['flip_max']:.2e} {s['flip_big']}" if "flip_rows" in s else "-")
-                     + f" | worst stable row(s) left out of normwise: {s.get('trimmed_max', 0.0):.2e}")
+                     + f" | worst stable row(s) left out of normwise: {s.get('trimmed_max', 0.0):.2e}"
+                     + (f" | {f['active']}; {f['median']:.2e} {f['p90']:.2e}; {f['median32']:.2e} {f['p90_32']:.2e} {f['max32']:.2e}; "
+                        f"{u('flip_median')} {u('flip_p90')} {u('flip_cap')}" if f is not None else " | -"))
     return "\n".join(lines)

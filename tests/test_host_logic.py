@@ -93,6 +93,84 @@ def test_oracle_farm_case_in_process_and_bar_arithmetic():
     assert st["normwise"] == 0.0 and math.isclose(st["trimmed_max"], 0.5, rel_tol=1e-6)
 
 
+def test_gradient_bars_notice_a_subtly_wrong_kernel(monkeypatch):
+    """What the gradient bars would let through, measured with the oracle evaluated in fp32 standing in for the HIP side,
+    through the same compare_case + check_gradient_bars the GPU parity tests use.  (a) Unchanged, it passes.  (b) With every
+    flip-sensitive row of every tensor scaled by 1.001 -- a relative error of 1e-3, ten times north_star's figure, on a fifth
+    of all Gaussians -- it is rejected (the bars before the flip-row median / p90 let it pass with a worst usage of 0.32).
+    (c) With one threshold constant of the walk wrong on the fp32 side only, it is rejected by at least one of the two cases."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_farm as F
+    import test_gpu_rasterizer as TR
+    from oracle import surfel_ref as O
+    cases = (TR.SH_SCALE_ROT[0], TR.CLAMP[3])
+    assert cases == ("facing2k-s0-flags3", "clamp500-s3-flags3")
+    wrong = dict(ALPHA_MAX=0.985, T_EPS=1.2e-4, ALPHA_MIN=1 / 255.5, FILTER_INV_SQUARE=2.02, NEAR_N=0.25)
+    true = {name: getattr(O, name) for name in wrong}
+    threads = torch.get_num_threads()
+    try:
+        cores = len(os.sched_getaffinity(0))
+    except AttributeError:
+        cores = os.cpu_count() or 2
+    monkeypatch.setenv("FARM_TORCH_THREADS", str(max(1, min(12, cores))))
+
+    def rejected(case, gh, radii_h, res):
+        stats, stats32, flips = F.compare_case(res, gh, radii_h)
+        try:
+            F.check_gradient_bars(case, stats, stats32, flips=flips)
+        except AssertionError as e:
+            return str(e)
+        return None
+
+    try:
+        caught = {name: [] for name in wrong}
+        for case in cases:
+            sp = F.FARM.specs[case]
+            res = F.run_case(sp, keep32=True)
+            F.check_against_committed_checksums(case, res)
+            g32 = {k: torch.from_numpy(v) for k, v in res["grads32"].items()}
+            sens = F.flip_sensitive_rows(res, res["radii32"])
+            assert 100 <= int(sens.sum()) <= sp["n"] // 2
+            # (a) the fp32 oracle is inside every bar, with room
+            stats, stats32, flips = F.compare_case(res, g32, res["radii32"])
+            assert F.check_gradient_bars(case, stats, stats32, flips=flips) < 0.5
+            # (b) a relative error of 1e-3 on the flip-sensitive rows alone
+            scaled = {k: torch.where(sens.reshape([-1] + [1] * (v.dim() - 1)), v * 1.001, v) for k, v in g32.items()}
+            why = rejected(case, scaled, res["radii32"], res)
+            assert why is not None and "flip-sensitive rows: median" in why, (case, why)
+            # (c) one wrong constant in the fp32 evaluation; the fp64 side (res) keeps the true ones
+            a, cam, bg, wc, wa = F.build_inputs(sp)
+            for name, value in wrong.items():
+                setattr(O, name, value)
+                try:
+                    g_bad, _, _, r_bad, _ = F._oracle_once(sp, a, cam, bg, wc, wa, torch.float32)
+                finally:
+                    setattr(O, name, true[name])
+                why = rejected(case, g_bad, r_bad, res)
+                if why is not None:
+                    caught[name].append(f"{case}: {why}")
+        for name in wrong:
+            assert caught[name], f"{name} = {wrong[name]} passes the gradient bars of both cases"
+    finally:
+        for name, value in true.items():
+            setattr(O, name, value)
+        torch.set_num_threads(threads)
+        del F.REPORT[:]
+
+
+def test_farm_refuses_more_workers_than_the_card_allows(monkeypatch):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_farm as F
+    farm = F.Farm()
+    farm.register("tiny", F.spec("facing", 8, 16, 16, 0))
+    monkeypatch.setenv("FARM_WORKERS", "5")
+    with pytest.raises(AssertionError, match="processes-per-card"):
+        farm.start()
+    assert farm.pool is None and not farm.futures
+    monkeypatch.setenv("FARM_WORKERS", "0")
+    assert farm.start() == 0
+
+
 def test_committed_oracle_checksums_cover_every_registered_case():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import json
@@ -103,6 +181,30 @@ def test_committed_oracle_checksums_cover_every_registered_case():
     for key, sums in want.items():
         for k, (s, sa) in sums.items():
             assert math.isfinite(s) and math.isfinite(sa) and sa >= 0.0, (key, k)   # (precomputed T + colours: dL/dmeans3D = 0)
+
+
+def test_committed_flip_levels_cover_every_case_with_an_fp32_pass_and_set_the_cap():
+    """tests/golden/oracle_flip_levels.json (written by tests/golden/make_oracle_flip_levels.py) holds the fp32 oracle's own
+    error levels for every registered case with an fp32 pass, every tensor of it; FLIP_CAP is twice the file's largest
+    flip-row figure and not above the 2e-2 it replaced."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import json
+    import oracle_farm as F
+    import test_gpu_rasterizer, test_gpu_deep_lists, test_gpu_wide_payload      # noqa: F401  (register the cases)
+    levels = json.load(open(F.FLIP_LEVELS))
+    want = {k for k, sp in F.FARM.specs.items() if sp["want32"]}
+    assert set(levels) == want, sorted(set(levels) ^ want)
+    checksums = json.load(open(F.CHECKSUMS))
+    largest = 0.0
+    for key, tensors in levels.items():
+        assert set(tensors) == set(checksums[key]), key
+        for k, t in tensors.items():
+            assert t["flip_rows"] + t["stable_rows"] == F.FARM.specs[key]["n"], (key, k)
+            for m in ("flip_max", "flip_median", "flip_p90", "stable_max", "stable_median", "stable_p90"):
+                assert math.isfinite(t[m]) and t[m] >= 0.0, (key, k, m)
+            largest = max(largest, t["flip_max"])
+    assert F.flip_level_max()[0] == largest == F.FLIP_LEVEL_MAX
+    assert F.FLIP_CAP == min(2e-2, 2.0 * largest) and F.FLIP_BIG < F.FLIP_CAP <= 2e-2
 
 
 def test_trainer_asks_the_forward_for_the_channels_the_objective_reads(monkeypatch):
