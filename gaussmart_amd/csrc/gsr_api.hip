@@ -441,6 +441,10 @@ extern "C" int32_t gsr_backward_with_job(const GsrView* view, const GsrGaussians
         gsr_set_error("%zu instances: gradient-row slots would overflow 32 bits", n_inst);
         return GSR_E_UNSUPPORTED;
     }
+    if (n_inst >= (size_t(1) << 28)) {   // render_bwd packs a tile-list position and a touch nibble into one word
+        gsr_set_error("%zu instances: tile-list positions would overflow 28 bits", n_inst);
+        return GSR_E_UNSUPPORTED;
+    }
     const bool wide = view->channels != 3;
     const size_t row_bytes_each = size_t(GSR_GROW_MAIN + (wide ? 0 : GSR_GROW_XY)) * 4 + (wide ? size_t(view->channels) * 4 : 0);
     const size_t sums_bytes = gsr_align(size_t(N > 0 ? N : 1) * GSR_GROW_FLOATS * 4);

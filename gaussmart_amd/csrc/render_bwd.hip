@@ -8,9 +8,14 @@
 // a tile's workgroup owns an 8x8 pixel quad and never synchronises with the other three; each DPP row of
 // 16 lanes owns one 4x4 pixel block of that quad and walks ITS OWN list:
 //   * the wave starts at the deepest list entry ANY OF ITS 64 PIXELS reached (quad-level, not tile-level)
-//     and walks the (tile, depth)-ordered list backwards, 64 entries per batch: ids two batches ahead, touch
-//     words and row slots one batch ahead, the 80-byte records gathered by id at the start of their batch (lane l
-//     fetches entry l) and staged in the wave's private LDS slice;
+//     and walks the (tile, depth)-ordered list backwards.  A SCAN FRONT reads only the touch words, 64 list
+//     positions per chunk (coalesced, two chunks in flight), and appends the positions whose nibble for THIS quad
+//     is non-zero to a small wave-private ring in LDS (ballot + mbcnt prefix, deep -> shallow).  A batch is the
+//     next 64 RING entries, not 64 consecutive list entries: only entries the forward blended into this quad are
+//     followed (inst_row -> slot_off), gathered and staged -- at 1M/1080p that is 0.30x the records and 0.33x the
+//     batches of consecutive batching, and full batches cost 7 % fewer iterations (scripts/model_k7_batches.py).
+//     Ids and emission indices run two batches ahead, row slots one batch ahead, the 80-byte records are gathered by
+//     id at the start of their batch (lane l fetches ring entry l) and staged in the wave's private LDS slice;
 //   * the forward left 4 bits per (instance, quad): "blended into >= 1 pixel of block g".  Four ballots
 //     turn them into one 64-bit to-do mask PER BLOCK; every iteration each row takes the deepest entry
 //     of its own mask, so the wave needs max_g |list_g| iterations instead of |union of the lists|
@@ -57,6 +62,8 @@ extern "C" int gsr_probe_read_stamps_bwd(void* dst, size_t bytes) {
 // ds_read_b128 per iteration instead of five (the fifth was worth 4 % of the kernel: DESIGN.md section 4, probe 8).  The
 // entry's first gradient row and its touch nibble share the sixteenth word: row + popcount of the touch bits of the quads
 // before this one (28 bits; the launcher falls back to the general kernel beyond 2^28 rows) | this quad's nibble << 28.
+// The entry's list position (the general record carries it beside the nibble) has no room in those sixteen words: it sits in
+// a 64-word array beside the records and costs one ds_read_b32 per iteration next to the four ds_read_b128.
 // Same arithmetic in the same order for everything that is not multiplied by one of those zeros, so the gradients equal the
 // general kernel's fed with a zero dL/dallmap bit for bit (tests/test_gpu_rasterizer.py).
 template <int PROBE = 0, bool NOSURF = false>
@@ -69,10 +76,18 @@ __global__ void __launch_bounds__(RB_BLOCK, NOSURF ? 8 : RB_MIN_WAVES) render_bw
     if (PROBE == 6 && p.W < 0) s_probe_pad[threadIdx.x] = 1.f;
     constexpr int RS = NOSURF ? 4 : 5;          // float4 parts of a staged record
     __shared__ float4 s_rec_all[RB_WAVES][64 * RS];
+    // the scan front's ring: list position | this quad's touch nibble << 28, and the number of gradient rows the entry has
+    // in the quads before this one (0..12)
+    __shared__ uint32_t s_ring_all[RB_WAVES][RB_RING];
+    __shared__ uint8_t s_rcnt_all[RB_WAVES][RB_RING];
+    __shared__ uint32_t s_pos_all[NOSURF ? RB_WAVES : 1][NOSURF ? 64 : 1];   // NOSURF: list position of staged entry j
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     float4* s_rec = s_rec_all[wave];
+    uint32_t* s_ring = s_ring_all[wave];
+    uint8_t* s_rcnt = s_rcnt_all[wave];
+    uint32_t* s_pos = s_pos_all[NOSURF ? wave : 0];
     // XCD-aware tile order: workgroups are dealt round-robin to the 8 XCDs (each with its own L2), so workgroup b
     // takes tile (b % 8) * per_xcd + b / 8 -- every XCD owns one contiguous band of tiles, and the records shared by
     // neighbouring tiles are fetched into ONE L2 instead of several
@@ -82,8 +97,8 @@ __global__ void __launch_bounds__(RB_BLOCK, NOSURF ? 8 : RB_MIN_WAVES) render_bw
     const int tile_y = tile_lin / p.gx, tile_x = tile_lin - tile_y * p.gx;
     const int qx0 = tile_x * GSR_TILE + (wave & 1) * 8, qy0 = tile_y * GSR_TILE + (wave >> 1) * 8;
     const int grp = lane >> 4, l16 = lane & 15;   // DPP row = 4x4 pixel block, same mapping as render_fwd
-    const uint32_t below_mask = ((1u << (8 * wave + grp)) - 1u) & 0x0F0F0F0Fu;   // touch bits of the blocks before mine
-    const uint32_t quads_below_mask = ((1u << (8 * wave)) - 1u) & 0x0F0F0F0Fu;   // ... of the quads before mine (NOSURF)
+    const uint32_t below_mask = ((1u << grp) - 1u) << 28;   // nibble bits (bits 28..31 of a staged word) of the blocks before mine in this quad
+    const uint32_t quads_below_mask = ((1u << (8 * wave)) - 1u) & 0x0F0F0F0Fu;   // ... of the quads before mine
     const uint32_t pick_shift = (uint32_t)grp * 16u;   // where this row's pick sits in the packed 64-bit scalar
     const int pxi = qx0 + (grp & 1) * 4 + (l16 & 3), pyi = qy0 + (grp >> 1) * 4 + (l16 >> 2);
     const bool inside = pxi < p.W && pyi < p.H;
@@ -145,53 +160,111 @@ __global__ void __launch_bounds__(RB_BLOCK, NOSURF ? 8 : RB_MIN_WAVES) render_bw
 
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 pf0, pf1, pf2, pf3, pf4;
-    uint32_t pf_touch = 0;   // named (not an array): keeps the prefetch in VGPRs, not scratch
-    uint32_t pf_slot = 0;    // first gradient row of the prefetched entry (slot_off[emission index]: a dependent load, so
-                             // the emission indices run two batches ahead like the ids)
-    int hi = max_contrib;
-    // ids and emission indices run two batches ahead of the replay, the per-entry words one batch ahead
-    uint32_t ids_cur, ids_nxt, rows_nxt;
+    uint32_t pf_slot = 0;    // named (not an array): keeps the prefetch in VGPRs, not scratch.  slot_off[emission index] of the
+                             // prefetched entry: a dependent load, so the emission indices run two batches ahead
+
+    // ---- scan front.  List positions [0, sc) are still to scan.  The ring holds, from r_base on: the `nb` entries of the
+    // current batch (until they are staged), the `nb_nxt` entries of the next one, and up to 64 entries that wait for the
+    // batch after that, up to r_tail -- never more than 128 (all of this is wave-uniform).  tw0 / tw1 hold the raw touch
+    // words of the next two chunks, lane l <-> position top - 1 - l, so the ring order is the list order backwards.  A fill
+    // stops at exactly 64 waiting entries: a chunk that holds more keeps the rest for the next fill (the lanes already
+    // taken are zeroed), so every batch but a list's last is full.
+    int sc = max_contrib;
+    uint32_t r_base = 0, r_tail = 0;
+    auto load_chunk = [&](int top) -> uint32_t {
+        const int pos = top - 1 - lane;
+        return pos >= 0 ? p.touch[(size_t)r0 + (uint32_t)pos] : 0u;
+    };
+    uint32_t tw0 = load_chunk(sc), tw1 = load_chunk(sc - 64);
+    auto scan_fill = [&](uint32_t held) {      // held: ring entries from r_base on that already belong to a batch
+        while (sc > 0) {
+            const uint32_t need = 64u - (r_tail - r_base - held);
+            if (need == 0u) break;
+            const int pos = sc - 1 - lane;
+            const uint32_t t = pos >= 0 ? rb_defined_touch(tw0, (uint32_t)pos, cov4) : 0u;
+            const uint32_t nib = (t >> (8 * wave)) & 0xFu;
+            const unsigned long long b = __ballot(nib != 0);
+            const uint32_t rank = rb_mbcnt(b), n_set = (uint32_t)__popcll(b);
+            const bool take = nib != 0 && rank < need;
+            if (take) {
+                const uint32_t at = (r_tail + rank) & (uint32_t)(RB_RING - 1);
+                s_ring[at] = (uint32_t)pos | (nib << 28);
+                s_rcnt[at] = (uint8_t)__popc(t & quads_below_mask);
+            }
+            if (n_set <= need) {
+                r_tail += n_set;
+                sc = max(sc - 64, 0);
+                tw0 = tw1; tw1 = load_chunk(sc - 64);
+            } else {
+                r_tail += need;
+                if (take) tw0 = 0u;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+    auto ring_pos = [&](uint32_t first) -> uint32_t {      // list position of ring entry first + lane
+        return s_ring[(first + (uint32_t)lane) & (uint32_t)(RB_RING - 1)] & 0x0FFFFFFFu;
+    };
+    // emission indices run two batches ahead of the replay, ids and row slots one batch ahead
+    uint32_t ids_cur = 0u, rows_nxt = 0u;
+    int nb, nb_nxt;      // entries of the current and of the next batch
     {
-        const int lo = max(0, hi - 64), cnt = hi - lo;
-        ids_cur = lane < cnt ? p.point_list[r0 + lo + lane] : 0u;
-        pf_slot = lane < cnt ? p.slot_off[p.inst_row[r0 + lo + lane]] : 0u;
-        pf_touch = lane < cnt ? rb_defined_touch(p.touch[(size_t)r0 + lo + lane], (uint32_t)(lo + lane), cov4) : 0u;
-        const int lo2 = max(0, lo - 64), cnt2 = lo - lo2;
-        ids_nxt = lane < cnt2 ? p.point_list[r0 + lo2 + lane] : 0u;
-        rows_nxt = lane < cnt2 ? p.inst_row[r0 + lo2 + lane] : 0u;
+        scan_fill(0u);
+        nb = (int)min(64u, r_tail - r_base);
+        if (lane < nb) {
+            const uint32_t pos = ring_pos(r_base);
+            ids_cur = p.point_list[r0 + pos];
+            pf_slot = p.slot_off[p.inst_row[r0 + pos]];
+        }
+        __builtin_amdgcn_wave_barrier();   // the ring reads precede the fill's writes
+        scan_fill((uint32_t)nb);
+        nb_nxt = (int)min(64u, r_tail - r_base - (uint32_t)nb);
+        if (lane < nb_nxt) rows_nxt = p.inst_row[r0 + ring_pos(r_base + (uint32_t)nb)];
     }
 
-    while (hi > 0) {
-        const int lo = max(0, hi - 64), nb = hi - lo;
+    while (nb > 0) {
         // The records of THIS batch are gathered here, not a batch ahead: holding the next batch's 20 registers per lane
         // through the replay cost two waves per SIMD (92 VGPRs, 5 waves -> 72, 7 waves), and seven waves hide the gather's
-        // latency better than the prefetch did (K7 0.660 -> 0.640 ms same-box).  The ids, the touch
-        // words and the row slots -- five registers -- still run ahead.
+        // latency better than the prefetch did (K7 0.660 -> 0.640 ms same-box).  The ids, the row
+        // slots, the emission indices and the scan front's two chunks -- five registers -- still run ahead; the ring words
+        // wait in LDS.
         GSR_GATHER5(ids_cur, nb);
-        const uint32_t touch_of_lane = pf_touch;      // 4 bytes (one per quad) x 4 bits (one per 4x4 block): blended there?
-        // first gradient row of staged entry `lane` (its rows are dense, in (quad, block) order of the set bits)
-        const uint32_t slot_of_lane = pf_slot;
+        uint32_t pk_of_lane = 0u;      // list position | this quad's nibble (one bit per 4x4 block: blended there?) << 28
+        // first gradient row of staged entry `lane` IN THIS QUAD (its rows are dense, in (quad, block) order of the set bits)
+        uint32_t slot_of_lane = 0u;
+        if (lane < nb) {
+            const uint32_t at = (r_base + (uint32_t)lane) & (uint32_t)(RB_RING - 1);
+            pk_of_lane = s_ring[at];
+            slot_of_lane = pf_slot + s_rcnt[at];
+        }
         // the record's two cull-rect words mean nothing to the backward: the staged copy carries the entry's first row
-        // and its touch word there instead, so a block that picks entry j reads them with the record (they used to come
-        // through two ds_bpermute per iteration)
-        if (NOSURF) {   // [Tu Tv.x | Tv.yz Tw.xy | Tw.z xy opacity | rgb (first row up to this quad | this quad's nibble << 28)]
-            const uint32_t packed = (slot_of_lane + (uint32_t)__popc(touch_of_lane & quads_below_mask)) |
-                                    (((touch_of_lane >> (8 * wave)) & 0xFu) << 28);
+        // and its position | nibble word there instead, so a block that picks entry j reads them with the record (they used
+        // to come through two ds_bpermute per iteration)
+        if (NOSURF) {   // [Tu Tv.x | Tv.yz Tw.xy | Tw.z xy opacity | rgb (first row in this quad | this quad's nibble << 28)]
+            const uint32_t packed = slot_of_lane | (pk_of_lane & 0xF0000000u);
             s_rec[lane * RS] = pf0; s_rec[lane * RS + 1] = pf1;
             s_rec[lane * RS + 2] = make_float4(pf2.x, pf2.y, pf2.z, pf3.z);
             s_rec[lane * RS + 3] = make_float4(pf3.w, pf4.x, pf4.y, __uint_as_float(packed));
+            s_pos[lane] = pk_of_lane & 0x0FFFFFFFu;
         } else {
             s_rec[lane * 5] = pf0; s_rec[lane * 5 + 1] = pf1; s_rec[lane * 5 + 2] = pf2; s_rec[lane * 5 + 3] = pf3;
-            s_rec[lane * 5 + 4] = make_float4(pf4.x, pf4.y, __uint_as_float(slot_of_lane), __uint_as_float(touch_of_lane));
+            s_rec[lane * 5 + 4] = make_float4(pf4.x, pf4.y, __uint_as_float(slot_of_lane), __uint_as_float(pk_of_lane));
         }
-        {   // prefetch the next (shallower) batch
-            const int hi2 = lo, lo2 = max(0, hi2 - 64), cnt = hi2 - lo2;
-            pf_slot = lane < cnt ? p.slot_off[rows_nxt] : 0u;
-            pf_touch = lane < cnt ? rb_defined_touch(p.touch[(size_t)r0 + lo2 + lane], (uint32_t)(lo2 + lane), cov4) : 0u;
-            ids_cur = ids_nxt;
-            const int lo3 = max(0, lo2 - 64), cnt3 = lo2 - lo3;
-            ids_nxt = lane < cnt3 ? p.point_list[r0 + lo3 + lane] : 0u;
-            rows_nxt = lane < cnt3 ? p.inst_row[r0 + lo3 + lane] : 0u;
+        int nb_nn;
+        {   // prefetch: ids and row slots of the next (shallower) batch; this batch leaves the ring; refill; emission
+            // indices of the batch after the next
+            pf_slot = 0u; ids_cur = 0u;
+            if (lane < nb_nxt) {
+                ids_cur = p.point_list[r0 + ring_pos(r_base + (uint32_t)nb)];
+                pf_slot = p.slot_off[rows_nxt];
+            }
+            r_base += (uint32_t)nb;
+            __builtin_amdgcn_wave_barrier();   // the ring reads precede the fill's writes
+            scan_fill((uint32_t)nb_nxt);
+            nb_nn = (int)min(64u, r_tail - r_base - (uint32_t)nb_nxt);
+            rows_nxt = 0u;
+            if (lane < nb_nn) rows_nxt = p.inst_row[r0 + ring_pos(r_base + (uint32_t)nb_nxt)];
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -199,13 +272,14 @@ __global__ void __launch_bounds__(RB_BLOCK, NOSURF ? 8 : RB_MIN_WAVES) render_bw
         // only the splats the forward blended into >= 1 pixel of a block carry any gradient there: one to-do
         // mask per 4x4 block (= DPP row), held by all 16 lanes of the row
         // (the four masks live in SGPRs: picking and clearing bits is scalar work, the vector unit only selects)
-        // (the masks are kept BIT-REVERSED: the deepest entry of a block is then the lowest set bit, which s_ff1 finds
-        // and reports as -1 on an empty mask by itself -- two scalar instructions per block and iteration)
+        // (the ring is ordered deep -> shallow, so staged entry 0 is the batch's deepest: the deepest entry of a block is the
+        // lowest set bit of its mask, which s_ff1 finds and reports as -1 on an empty mask by itself -- two scalar
+        // instructions per block and iteration)
         unsigned long long m0, m1, m2, m3;
         {
-            const uint32_t t = lane < nb ? (touch_of_lane >> (8 * wave)) & 0xFu : 0u;
-            m0 = __builtin_bitreverse64(__ballot((t & 1u) != 0)); m1 = __builtin_bitreverse64(__ballot((t & 2u) != 0));
-            m2 = __builtin_bitreverse64(__ballot((t & 4u) != 0)); m3 = __builtin_bitreverse64(__ballot((t & 8u) != 0));
+            const uint32_t t = lane < nb ? pk_of_lane >> 28 : 0u;
+            m0 = __ballot((t & 1u) != 0); m1 = __ballot((t & 2u) != 0);
+            m2 = __ballot((t & 4u) != 0); m3 = __ballot((t & 8u) != 0);
         }
         float probe_v = pxf; uint32_t probe_s = (uint32_t)__builtin_amdgcn_readfirstlane(nb);
         for (;;) {
@@ -214,10 +288,9 @@ __global__ void __launch_bounds__(RB_BLOCK, NOSURF ? 8 : RB_MIN_WAVES) render_bw
             const uint32_t p01 = rb_pack16(r0_, r1_), p23 = rb_pack16(r2_, r3_);
             if ((p01 & p23) == 0xFFFFFFFFu) break;                  // all four masks were empty
             const unsigned long long picks = ((unsigned long long)p23 << 32) | p01;
-            const int jrev = (int)(short)(picks >> pick_shift);     // this row's pick in reversed numbering; -1: none
-            const bool has = jrev >= 0;
-            const int j = (63 - jrev) & 63;
-            const int cidx = lo + j;                            // 0-based position in the tile list
+            const int pick = (int)(short)(picks >> pick_shift);     // this row's pick; -1: none
+            const bool has = pick >= 0;
+            const int j = max(pick, 0);                             // (a row without a pick reads entry 0 and drops the result)
             const float4 a0 = s_rec[j * RS + 0], a1 = PROBE == 8 ? a0 : s_rec[j * RS + 1], a2 = s_rec[j * RS + 2];
             const float4 a3 = s_rec[j * RS + 3];     // general: [n.y n.z opacity r]; NOSURF: [r g b packed row | nibble]
             const float opa = NOSURF ? a2.w : a3.z;
@@ -233,23 +306,28 @@ __global__ void __launch_bounds__(RB_BLOCK, NOSURF ? 8 : RB_MIN_WAVES) render_bw
 #pragma unroll
                 for (int q = 0; q < 8; ++q) asm volatile("s_add_u32 %0, %0, 1" : "+s"(probe_s) : : "scc");
             }
+            // first gradient row in this quad, this quad's touch nibble and the 0-based position in the tile list of this
+            // row's entry (staged with the record)
+            uint32_t rec_slot, rec_touch;      // (rec_touch: the nibble sits in bits 28..31, the rest is not looked at)
+            int cidx;
+            float4 a4;
+            if (NOSURF) {
+                rec_touch = __float_as_uint(a3.w);
+                rec_slot = rec_touch & 0x0FFFFFFFu;
+                cidx = (int)s_pos[j];
+                a4 = make_float4(a3.y, a3.z, 0.f, 0.f);
+            } else {
+                a4 = s_rec[j * 5 + 4];
+                rec_touch = __float_as_uint(a4.w);
+                rec_slot = __float_as_uint(a4.z);
+                cidx = (int)(rec_touch & 0x0FFFFFFFu);
+            }
             GsrPair pr;
             const bool ok = gsr_pair_eval(pxf, pyf, a0, a1, a2, opa, pr);
             const bool active = has && cidx < last_contributor && ok;
             float gT[9];
             float gxy0, gxy1, gn0, gn1, gn2, gopa, gc0, gc1, gc2;
-            uint32_t rec_slot, rec_touch;   // first gradient row and touch word of this row's entry (staged with the record)
             {
-                float4 a4;
-                if (NOSURF) {
-                    const uint32_t packed = __float_as_uint(a3.w);
-                    rec_slot = packed & 0x0FFFFFFFu;               // (already counts the quads before this one)
-                    rec_touch = (packed >> 28) << (8 * wave);      // this quad's nibble, where below_mask looks for it
-                    a4 = make_float4(a3.y, a3.z, 0.f, 0.f);
-                } else {
-                    a4 = s_rec[j * 5 + 4];
-                    rec_slot = __float_as_uint(a4.z); rec_touch = __float_as_uint(a4.w);
-                }
                 const float alpha = active ? pr.alpha : 0.f, G = active ? pr.G : 0.f, c_d = active ? pr.depth : 1.f;
                 const float sx = active ? pr.sx : 0.f, sy = active ? pr.sy : 0.f, inv_pz = active ? pr.inv_pz : 0.f;
                 const float one_m_alpha = 1.0f - alpha;
@@ -339,7 +417,7 @@ __global__ void __launch_bounds__(RB_BLOCK, NOSURF ? 8 : RB_MIN_WAVES) render_bw
                 const float xy = row_sum2(gxy0, gxy1, l16);
                 // every row whose to-do bit was set writes its slot (zeros if no pixel turned out active), so
                 // the reduction never reads a row that was not written
-                // (NOSURF: rec_slot already counts the quads before this one and rec_touch holds this quad's nibble only)
+                // (rec_slot already counts the quads before this one and rec_touch holds this quad's nibble only)
                 const size_t slot = (size_t)rec_slot + __popc(rec_touch & below_mask);
                 if (has) {
                     p.grad_rows[slot * RB_ROW + l16] = tot;                   // one aligned 64-byte store per row
@@ -350,7 +428,7 @@ __global__ void __launch_bounds__(RB_BLOCK, NOSURF ? 8 : RB_MIN_WAVES) render_bw
         if (PROBE == 1 && probe_v == 1.2345f) T += 1.f;
         if (PROBE == 4 && probe_s == 0x7fffffffu) T += 1.f;
         __builtin_amdgcn_wave_barrier();   // all reads of this batch precede the next batch's LDS writes
-        hi = lo;
+        nb = nb_nxt; nb_nxt = nb_nn;
     }
 #ifdef GSR_DEV_PROBES
     if (PROBE == 7) {

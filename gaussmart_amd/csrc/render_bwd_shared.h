@@ -22,6 +22,9 @@
 #define RB_BLOCK 256
 #define RB_WAVES 4
 #define RB_ROW GSR_GROW_MAIN   // 16 floats: one aligned 64-byte store per block and entry
+// render_bwd.hip: entries of a wave's ring of touched list positions: the 64 of the batch being staged or of the next
+// one, and the 64 the scan front keeps waiting (5 bytes each: 2.5 KB per workgroup)
+#define RB_RING 128
 
 struct RenderBwdParams {
     int W, H, gx, n_tiles, per_xcd;
@@ -48,6 +51,11 @@ __device__ __forceinline__ uint32_t rb_pack16(int lo, int hi) {
     uint32_t r;
     asm("s_pack_ll_b32_b16 %0, %1, %2" : "=s"(r) : "s"(lo), "s"(hi));
     return r;
+}
+
+// number of set bits of a ballot below this lane
+__device__ __forceinline__ uint32_t rb_mbcnt(unsigned long long b) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
 }
 
 // First gradient row of every depth rank, row_begin[r] = slot_off[offs[r]] (r = 0..N): reduce_rows, the next kernel on the
