@@ -29,10 +29,9 @@
 //     HBM sees plain streaming stores instead of ~18 atomics per pixel-splat pair.
 #include <stdlib.h>
 #include "gsr_common.h"
-#include "pair_eval.h"
 #include "wave_reduce.h"
 
-#include "render_bwd_shared.h"
+#include "rb_replay.h"
 
 #ifndef RB_MIN_WAVES
 #define RB_MIN_WAVES 6   // <= 80 VGPRs.  Round 2's kernel needed 72 (seven waves per SIMD); with the two-array rows and the
@@ -43,8 +42,8 @@
 #endif
 // (Wide per-pixel payloads have their own kernel: render_bwd_wide.hip.)
 // PROBE (developer builds only: make PROBES=1, scripts/dev_probe.py): 1 = eight more dependent VALU per iteration,
-// 4 = eight more dependent SALU, 3 = no row store (WRONG gradients: it exists to time the loop), 6 = 20 KB more LDS per
-// workgroup (fewer waves per SIMD), 8 = four LDS reads of the record instead of five (WRONG gradients).
+// 4 = eight more dependent SALU, 6 = 20 KB more LDS per workgroup (fewer waves per SIMD), 8 = four LDS reads of the record
+// instead of five (WRONG gradients).
 #ifdef GSR_DEV_PROBES
 // PROBE 7 (round 4): every wave leaves its lifetime on the shader clock (s_memtime) and on the 100 MHz s_memrealtime
 // clock: their ratio is the clock the chip holds under this kernel (scripts/dev_clock_probe.py).
@@ -88,75 +87,35 @@ __global__ void __launch_bounds__(RB_BLOCK, NOSURF ? 8 : RB_MIN_WAVES) render_bw
     uint32_t* s_ring = s_ring_all[wave];
     uint8_t* s_rcnt = s_rcnt_all[wave];
     uint32_t* s_pos = s_pos_all[NOSURF ? wave : 0];
-    // XCD-aware tile order: workgroups are dealt round-robin to the 8 XCDs (each with its own L2), so workgroup b
-    // takes tile (b % 8) * per_xcd + b / 8 -- every XCD owns one contiguous band of tiles, and the records shared by
-    // neighbouring tiles are fetched into ONE L2 instead of several
-    const int tile_lin = (int)(blockIdx.x & 7u) * p.per_xcd + (int)(blockIdx.x >> 3);
+    // (the prologue and the per-pair backward are rb_replay.h's statement macros over these locals)
+    const int tile_lin = RB_TILE_OF_WORKGROUP();
     rb_row_begin_job(p);
     if (tile_lin >= p.n_tiles) return;
-    const int tile_y = tile_lin / p.gx, tile_x = tile_lin - tile_y * p.gx;
-    const int qx0 = tile_x * GSR_TILE + (wave & 1) * 8, qy0 = tile_y * GSR_TILE + (wave >> 1) * 8;
-    const int grp = lane >> 4, l16 = lane & 15;   // DPP row = 4x4 pixel block, same mapping as render_fwd
+    RB_QUAD_ORIGIN();
+    const int grp = lane >> 4, l16 = lane & 15;   // DPP row = 4x4 pixel block
     const uint32_t below_mask = ((1u << grp) - 1u) << 28;   // nibble bits (bits 28..31 of a staged word) of the blocks before mine in this quad
     const uint32_t quads_below_mask = ((1u << (8 * wave)) - 1u) & 0x0F0F0F0Fu;   // ... of the quads before mine
     const uint32_t pick_shift = (uint32_t)grp * 16u;   // where this row's pick sits in the packed 64-bit scalar
-    const int pxi = qx0 + (grp & 1) * 4 + (l16 & 3), pyi = qy0 + (grp >> 1) * 4 + (l16 >> 2);
-    const bool inside = pxi < p.W && pyi < p.H;
-    const float pxf = (float)pxi, pyf = (float)pyi;
-    const int pix_id = pyi * p.W + pxi;
-    const int HW = p.W * p.H;
+    RB_PIXEL();
 
-    const uint32_t tile = (uint32_t)(tile_y * p.gx + tile_x);
+    const uint32_t tile = (uint32_t)tile_lin;
     const uint32_t r0 = p.ranges[2 * tile];
     // the forward wrote quad w's touch byte of a list entry only below covered[w] (wave-uniform)
     const uint4 cov4 = *reinterpret_cast<const uint4*>(p.covered + 4 * tile);
 
-    // the deepest list entry any pixel of THIS QUAD reached
-    const int last_contributor = inside ? (int)p.n_contrib[pix_id] : 0;
-    int max_contrib = last_contributor;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) max_contrib = max(max_contrib, __shfl_xor(max_contrib, d, 64));
-    max_contrib = __builtin_amdgcn_readfirstlane(max_contrib);
+    RB_QUAD_DEPTH();
     if (max_contrib == 0) return;
 
-    const bool clamp_pass = (p.flags & GSR_FLAG_CLAMP_PASSTHROUGH) != 0;
-    const bool filter_depth_quirk = (p.flags & GSR_FLAG_FILTER_DEPTH_GRAD) != 0;
-
-    // per-pixel state saved by the forward
-    const float T_final = inside ? p.final_T[pix_id] : 0.f;
-    const float final_D = (!NOSURF && inside) ? p.final_T[pix_id + HW] : 0.f;       // sum m w
-    const float final_D2 = (!NOSURF && inside) ? p.final_T[pix_id + 2 * HW] : 0.f;  // sum m^2 w
-    const float final_A = 1.0f - T_final;
-    const int median_contributor = (!NOSURF && inside) ? (int)p.n_contrib[pix_id + HW] : 0;
-
-    // A pixel nothing was blended into takes no part in the reference's backward (its loop over contributors is empty), so
-    // whatever gradient arrives for it must not be read: the replay below is branch-free -- an idle lane contributes
-    // 0 * (its pixel's gradient) to the 16-lane sums -- and the reference's OWN objective sends NaN to exactly these pixels
-    // (gaussian_renderer/__init__.py:131-132: depth / alpha with alpha = 0, nan_to_num on the value only).
-    const bool lit = inside && last_contributor > 0;
+    RB_PIXEL_STATE();
     float dL_dpix0 = 0.f, dL_dpix1 = 0.f, dL_dpix2 = 0.f;
-    float dL_ddepth = 0.f, dL_daccum = 0.f, dL_dreg = 0.f, dL_dmedian = 0.f;
-    float dL_dn0 = 0.f, dL_dn1 = 0.f, dL_dn2 = 0.f;
     if (lit) { dL_dpix0 = p.dL_dcolor[pix_id]; dL_dpix1 = p.dL_dcolor[pix_id + HW]; dL_dpix2 = p.dL_dcolor[pix_id + 2 * HW]; }
-    if (!NOSURF && lit) {
-        dL_ddepth = p.dL_dallmap[pix_id + 0 * HW];
-        dL_daccum = p.dL_dallmap[pix_id + 1 * HW];
-        dL_dn0 = p.dL_dallmap[pix_id + 2 * HW];
-        dL_dn1 = p.dL_dallmap[pix_id + 3 * HW];
-        dL_dn2 = p.dL_dallmap[pix_id + 4 * HW];
-        dL_dmedian = p.dL_dallmap[pix_id + 5 * HW];
-        dL_dreg = p.dL_dallmap[pix_id + 6 * HW];
-    }
+    RB_ALLMAP_GRADS();
     const float bg_dot_dpixel = p.bg[0] * dL_dpix0 + p.bg[1] * dL_dpix1 + p.bg[2] * dL_dpix2;
 
-    // (GSR_FLAG_NO_DIST_MEDIAN: the forward returned channels 5 and 6 as constants -- gradients sent to them are ignored)
     const bool dm_live = !NOSURF && (p.flags & (uint32_t)GSR_FLAG_NO_DIST_MEDIAN) == 0;
-    const bool quad_has_dist = dm_live && __any(dL_dreg != 0.f), quad_has_median = dm_live && __any(dL_dmedian != 0.f);   // wave-uniform
-    const bool quad_has_surf = !NOSURF && __any(dL_ddepth != 0.f || dL_daccum != 0.f || dL_dn0 != 0.f || dL_dn1 != 0.f || dL_dn2 != 0.f);
+    RB_QUAD_FLAGS();
 
-    // running state of the back-to-front recursion
-    float T = T_final;
-    float last_alpha = 0.f, last_q = 0.f, acc_q = 0.f, last_dL_dT = 0.f;
+    RB_STATE_BEGIN();
 
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 pf0, pf1, pf2, pf3, pf4;
@@ -294,10 +253,6 @@ __global__ void __launch_bounds__(RB_BLOCK, NOSURF ? 8 : RB_MIN_WAVES) render_bw
             const float4 a0 = s_rec[j * RS + 0], a1 = PROBE == 8 ? a0 : s_rec[j * RS + 1], a2 = s_rec[j * RS + 2];
             const float4 a3 = s_rec[j * RS + 3];     // general: [n.y n.z opacity r]; NOSURF: [r g b packed row | nibble]
             const float opa = NOSURF ? a2.w : a3.z;
-            // Branch-free: EVERY lane runs the gradient math (masked-off lanes would cost the same issue slots),
-            // and a lane that does not blend this splat gets alpha = G = 0 and harmless finite geometry, which
-            // makes all 18 of its partial derivatives exact zeros and leaves its recursion state untouched
-            // (T / (1 - 0) = T; the suffix sums advance by a zero-weight term).
             if (PROBE == 1) {
 #pragma unroll
                 for (int q = 0; q < 8; ++q) asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(probe_v));
@@ -328,85 +283,16 @@ __global__ void __launch_bounds__(RB_BLOCK, NOSURF ? 8 : RB_MIN_WAVES) render_bw
             float gT[9];
             float gxy0, gxy1, gn0, gn1, gn2, gopa, gc0, gc1, gc2;
             {
-                const float alpha = active ? pr.alpha : 0.f, G = active ? pr.G : 0.f, c_d = active ? pr.depth : 1.f;
-                const float sx = active ? pr.sx : 0.f, sy = active ? pr.sy : 0.f, inv_pz = active ? pr.inv_pz : 0.f;
-                const float one_m_alpha = 1.0f - alpha;
-                const float inv_oma = gsr_rcp(one_m_alpha);
-                T = T * inv_oma;
-                const float w = alpha * T;
-
-                // colour, expected depth, alpha and normal share one suffix recursion:
-                //   q_i = c_i . dL/dC + z_i dL/dD + 1 dL/dA + n_i . dL/dN
+                RB_BLEND();
+                // q of the suffix recursion: surface + colour, from 0
                 const float c0 = NOSURF ? a3.x : a3.w, c1 = a4.x, c2 = a4.y;
                 const float n0 = a2.w, n1 = a3.x, n2 = a3.y;    // (only read when quad_has_surf)
-                // (the surface channels -- depth, alpha, normal -- carry no gradient before the regularizers switch on)
                 float q = 0.f;
                 if (quad_has_surf) q = c_d * dL_ddepth + dL_daccum + n0 * dL_dn0 + n1 * dL_dn1 + n2 * dL_dn2;
                 q += c0 * dL_dpix0 + c1 * dL_dpix1 + c2 * dL_dpix2;
-                acc_q = last_alpha * last_q + (1.f - last_alpha) * acc_q;
-                last_q = q;
-                float dL_dalpha = q - acc_q;
+                RB_SUFFIX();
                 gc0 = w * dL_dpix0; gc1 = w * dL_dpix1; gc2 = w * dL_dpix2;
-                gn0 = 0.f; gn1 = 0.f; gn2 = 0.f;
-                if (quad_has_surf) { gn0 = w * dL_dn0; gn1 = w * dL_dn1; gn2 = w * dL_dn2; }
-
-                // median depth and distortion: skipped (wave-uniformly) when the whole quad receives no gradient on that
-                // channel -- the reference's defaults (depth_ratio = 0, lambda_dist = 0) make both identically zero, and
-                // every term below is a multiple of it
-                float dL_dz = NOSURF ? 0.f : w * dL_ddepth;
-                if (quad_has_median && active && cidx == median_contributor - 1) dL_dz += dL_dmedian;
-                if (quad_has_dist) {
-                    float dmd_dd;
-                    const float m_d = gsr_depth_map(c_d, dmd_dd);
-                    const float dL_dweight = (final_D2 + m_d * m_d * final_A - 2.f * m_d * final_D) * dL_dreg;
-                    dL_dalpha += dL_dweight - last_dL_dT;
-                    last_dL_dT = dL_dweight * alpha + one_m_alpha * last_dL_dT;
-                    dL_dz += 2.0f * w * (m_d * final_A - final_D) * dL_dreg * dmd_dd;
-                }
-
-                dL_dalpha *= T;
-                last_alpha = alpha;
-                // alpha also scales how much background shows through
-                dL_dalpha -= T_final * inv_oma * bg_dot_dpixel;
-
-                // alpha = min(0.99, opa * G)
-                const float dL_daraw = (clamp_pass || pr.araw <= GSR_ALPHA_MAX) ? dL_dalpha : 0.f;
-                const float dL_dG = opa * dL_daraw;
-                gopa = G * dL_daraw;
-
-                const float Twx = a1.z, Twy = a1.w;
-                if (pr.use3d) {
-                    const float dL_dsx = NOSURF ? dL_dG * (-G * sx) : dL_dG * (-G * sx) + dL_dz * Twx;
-                    const float dL_dsy = NOSURF ? dL_dG * (-G * sy) : dL_dG * (-G * sy) + dL_dz * Twy;
-                    float dpx = dL_dsx * inv_pz, dpy = dL_dsy * inv_pz;
-                    if (__builtin_expect(pr.tiny_any, 0)) {       // (pair_eval.h: a denormal p.z; the empty asm keeps this a BRANCH -- if-converted it cost
-                        asm volatile("");                         //  three vector instructions on every pair, +3.7 % of K7's issue)
-                        const float zs = pr.tiny ? GSR_TINY_PZ_SCALE : 1.f; dpx *= zs; dpy *= zs;
-                    }
-                    const float dpz = -(dpx * sx + dpy * sy);
-                    // dL/dTu = -dL/dk = dL/dp x l ;  dL/dTv = -dL/dl = k x dL/dp
-                    const float ux = dpy * pr.lz - dpz * pr.ly, uy = dpz * pr.lx - dpx * pr.lz, uz = dpx * pr.ly - dpy * pr.lx;
-                    const float vx = pr.ky * dpz - pr.kz * dpy, vy = pr.kz * dpx - pr.kx * dpz, vz = pr.kx * dpy - pr.ky * dpx;
-                    gT[0] = ux; gT[1] = uy; gT[2] = uz;
-                    gT[3] = vx; gT[4] = vy; gT[5] = vz;
-                    if (NOSURF) {      // (the general form with dL_dz = +0: 0 * s - a - b == -a - b up to the sign of a zero)
-                        gT[6] = 0.f - pxf * ux - pyf * vx;
-                        gT[7] = 0.f - pxf * uy - pyf * vy;
-                        gT[8] = 0.f - pxf * uz - pyf * vz;
-                    } else {
-                        gT[6] = dL_dz * sx - pxf * ux - pyf * vx;
-                        gT[7] = dL_dz * sy - pxf * uy - pyf * vy;
-                        gT[8] = dL_dz - pxf * uz - pyf * vz;
-                    }
-                    gxy0 = 0.f; gxy1 = 0.f;
-                } else {
-                    gxy0 = dL_dG * (-G * GSR_FILTER_INV_SQUARE * pr.dx);
-                    gxy1 = dL_dG * (-G * GSR_FILTER_INV_SQUARE * pr.dy);
-                    gT[0] = 0.f; gT[1] = 0.f; gT[2] = 0.f; gT[3] = 0.f; gT[4] = 0.f; gT[5] = 0.f;
-                    gT[6] = (!NOSURF && filter_depth_quirk) ? sx * dL_dz : 0.f;
-                    gT[7] = (!NOSURF && filter_depth_quirk) ? sy * dL_dz : 0.f;
-                    gT[8] = dL_dz;
-                }
+                RB_PARTIALS();
             }
 
             // block-level sums (16 lanes), stored by the lanes that end up holding them (row layout GSR_GR_*)
@@ -546,7 +432,6 @@ int gsr_launch_render_bwd(const GsrView& v, const uint32_t* ranges, const uint32
         const char* e = getenv("GSR_K7_PROBE");   // re-read per launch
         switch (e ? atoi(e) : 0) {
             case 1: hipLaunchKernelGGL((render_bwd_kernel<1>), grid, block, 0, s, p); break;
-            case 3: hipLaunchKernelGGL((render_bwd_kernel<3>), grid, block, 0, s, p); break;
             case 4: hipLaunchKernelGGL((render_bwd_kernel<4>), grid, block, 0, s, p); break;
             case 6: hipLaunchKernelGGL((render_bwd_kernel<6>), grid, block, 0, s, p); break;
             case 7: hipLaunchKernelGGL((render_bwd_kernel<7>), grid, block, 0, s, p); break;

@@ -16,9 +16,6 @@
         }                                                                                            \
     } while (0)
 
-#define RF_BLOCK 256
-#define RF_WAVES 4
-
 #define RB_BLOCK 256
 #define RB_WAVES 4
 #define RB_ROW GSR_GROW_MAIN   // 16 floats: one aligned 64-byte store per block and entry

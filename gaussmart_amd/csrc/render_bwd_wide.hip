@@ -17,11 +17,9 @@
 //      wave through LDS), D[t][ch] leaves straight for the feature rows.
 // Exact f32 (one fma per product, fixed order): deterministic, parity tests as for the scalar form
 // (tests/test_gpu_wide_payload.py).  Lane maps of the instruction: scripts/microbench/mfma_layout.hip.
-#include <stdlib.h>
 #include "gsr_common.h"
-#include "pair_eval.h"
 #include "wave_reduce.h"
-#include "render_bwd_shared.h"
+#include "rb_replay.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -40,56 +38,29 @@ __device__ __forceinline__ void render_bwd_wide_tile(const RenderBwdParams& p) {
     int (*s_win)[16] = s_win_all[wave];
     uint32_t (*s_slot)[16] = s_slot_all[wave];
     float (*s_q)[16][16] = s_q_all[wave];
-    const int tile_lin = (int)(blockIdx.x & 7u) * p.per_xcd + (int)(blockIdx.x >> 3);   // XCD-aware tile order (render_bwd.hip)
+    // (the prologue and the per-pair backward are rb_replay.h's statement macros over these locals, in the general form)
+    constexpr bool NOSURF = false;
+    const int tile_lin = RB_TILE_OF_WORKGROUP();
     if (tile_lin >= p.n_tiles) return;
-    const int tile_y = tile_lin / p.gx, tile_x = tile_lin - tile_y * p.gx;
-    const int qx0 = tile_x * GSR_TILE + (wave & 1) * 8, qy0 = tile_y * GSR_TILE + (wave >> 1) * 8;
+    RB_QUAD_ORIGIN();
     const int grp = lane >> 4, l16 = lane & 15;   // DPP row = 4x4 pixel block
     const uint32_t below_mask = ((1u << (8 * wave + grp)) - 1u) & 0x0F0F0F0Fu;   // touch bits of the blocks before mine
-    const int pxi = qx0 + (grp & 1) * 4 + (l16 & 3), pyi = qy0 + (grp >> 1) * 4 + (l16 >> 2);
-    const bool inside = pxi < p.W && pyi < p.H;
-    const float pxf = (float)pxi, pyf = (float)pyi;
-    const int pix_id = pyi * p.W + pxi;
-    const int HW = p.W * p.H;
+    RB_PIXEL();
 
-    const uint32_t tile = (uint32_t)(tile_y * p.gx + tile_x);
+    const uint32_t tile = (uint32_t)tile_lin;
     const uint32_t r0 = p.ranges[2 * tile];
     const uint4 cov4 = *reinterpret_cast<const uint4*>(p.covered + 4 * tile);
 
-    const int last_contributor = inside ? (int)p.n_contrib[pix_id] : 0;
-    int max_contrib = last_contributor;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) max_contrib = max(max_contrib, __shfl_xor(max_contrib, d, 64));
-    max_contrib = __builtin_amdgcn_readfirstlane(max_contrib);
+    RB_QUAD_DEPTH();
     if (max_contrib == 0) return;
 
-    const bool clamp_pass = (p.flags & GSR_FLAG_CLAMP_PASSTHROUGH) != 0;
-    const bool filter_depth_quirk = (p.flags & GSR_FLAG_FILTER_DEPTH_GRAD) != 0;
-
-    const float T_final = inside ? p.final_T[pix_id] : 0.f;
-    const float final_D = inside ? p.final_T[pix_id + HW] : 0.f;
-    const float final_D2 = inside ? p.final_T[pix_id + 2 * HW] : 0.f;
-    const float final_A = 1.0f - T_final;
-    const int median_contributor = inside ? (int)p.n_contrib[pix_id + HW] : 0;
-
-    // (a pixel nothing was blended into takes no part, whatever gradient arrives for it: render_bwd.hip)
-    const bool lit = inside && last_contributor > 0;
+    RB_PIXEL_STATE();
     // dL/dpixel of MY pixel, all channels (lane = pixel): the B operand of the Q products
     constexpr int NF = 16 * NM;
     float g[NF];
 #pragma unroll
     for (int k = 0; k < NF; ++k) g[k] = (lit && k < p.C) ? p.dL_dcolor[pix_id + (size_t)k * HW] : 0.f;
-    float dL_ddepth = 0.f, dL_daccum = 0.f, dL_dreg = 0.f, dL_dmedian = 0.f;
-    float dL_dn0 = 0.f, dL_dn1 = 0.f, dL_dn2 = 0.f;
-    if (lit) {
-        dL_ddepth = p.dL_dallmap[pix_id + 0 * HW];
-        dL_daccum = p.dL_dallmap[pix_id + 1 * HW];
-        dL_dn0 = p.dL_dallmap[pix_id + 2 * HW];
-        dL_dn1 = p.dL_dallmap[pix_id + 3 * HW];
-        dL_dn2 = p.dL_dallmap[pix_id + 4 * HW];
-        dL_dmedian = p.dL_dallmap[pix_id + 5 * HW];
-        dL_dreg = p.dL_dallmap[pix_id + 6 * HW];
-    }
+    RB_ALLMAP_GRADS();
     float bg_dot_dpixel = 0.f;
 #pragma unroll
     for (int k = 0; k < NF; ++k)
@@ -114,11 +85,10 @@ __device__ __forceinline__ void render_bwd_wide_tile(const RenderBwdParams& p) {
         }
     }
 
-    const bool quad_has_dist = __any(dL_dreg != 0.f), quad_has_median = __any(dL_dmedian != 0.f);   // wave-uniform
-    const bool quad_has_surf = __any(dL_ddepth != 0.f || dL_daccum != 0.f || dL_dn0 != 0.f || dL_dn1 != 0.f || dL_dn2 != 0.f);
+    const bool dm_live = true;   // (GSR_FLAG_NO_DIST_MEDIAN is looked at by the RGB kernels only)
+    RB_QUAD_FLAGS();
 
-    float T = T_final;
-    float last_alpha = 0.f, last_q = 0.f, acc_q = 0.f, last_dL_dT = 0.f;
+    RB_STATE_BEGIN();
 
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 pf0, pf1, pf2, pf3, pf4;
@@ -219,8 +189,9 @@ __device__ __forceinline__ void render_bwd_wide_tile(const RenderBwdParams& p) {
                 const int cidx = lo + j;
                 const float4 a0 = s_rec[j * 5 + 0], a1 = s_rec[j * 5 + 1], a2 = s_rec[j * 5 + 2];
                 const float4 a3 = s_rec[j * 5 + 3];
+                const float opa = a3.z;
                 GsrPair pr;
-                const bool ok = gsr_pair_eval(pxf, pyf, a0, a1, a2, a3.z, pr);
+                const bool ok = gsr_pair_eval(pxf, pyf, a0, a1, a2, opa, pr);
                 const bool active = has && cidx < last_contributor && ok;
                 float gT[9];
                 float gxy0, gxy1, gn0, gn1, gn2, gopa;
@@ -228,67 +199,14 @@ __device__ __forceinline__ void render_bwd_wide_tile(const RenderBwdParams& p) {
                 {
                     const float4 a4 = s_rec[j * 5 + 4];
                     rec_slot = __float_as_uint(a4.z); rec_touch = __float_as_uint(a4.w);
-                    const float alpha = active ? pr.alpha : 0.f, G = active ? pr.G : 0.f, c_d = active ? pr.depth : 1.f;
-                    const float sx = active ? pr.sx : 0.f, sy = active ? pr.sy : 0.f, inv_pz = active ? pr.inv_pz : 0.f;
-                    const float one_m_alpha = 1.0f - alpha;
-                    const float inv_oma = gsr_rcp(one_m_alpha);
-                    T = T * inv_oma;
-                    const float w = alpha * T;
+                    RB_BLEND();
+                    // q of the suffix recursion: colour (from the tile) + surface
                     const float n0 = a2.w, n1 = a3.x, n2 = a3.y;
                     float q = s_q[grp][t][l16];                 // colour term: sum_ch f[ch] dL/dpixel[ch]
                     s_q[grp][t][l16] = w;                       // ... replaced by the A operand of the row products
                     if (quad_has_surf) q += c_d * dL_ddepth + dL_daccum + n0 * dL_dn0 + n1 * dL_dn1 + n2 * dL_dn2;
-                    acc_q = last_alpha * last_q + (1.f - last_alpha) * acc_q;
-                    last_q = q;
-                    float dL_dalpha = q - acc_q;
-                    gn0 = 0.f; gn1 = 0.f; gn2 = 0.f;
-                    if (quad_has_surf) { gn0 = w * dL_dn0; gn1 = w * dL_dn1; gn2 = w * dL_dn2; }
-
-                    float dL_dz = w * dL_ddepth;
-                    if (quad_has_median && active && cidx == median_contributor - 1) dL_dz += dL_dmedian;
-                    if (quad_has_dist) {
-                        float dmd_dd;
-                        const float m_d = gsr_depth_map(c_d, dmd_dd);
-                        const float dL_dweight = (final_D2 + m_d * m_d * final_A - 2.f * m_d * final_D) * dL_dreg;
-                        dL_dalpha += dL_dweight - last_dL_dT;
-                        last_dL_dT = dL_dweight * alpha + one_m_alpha * last_dL_dT;
-                        dL_dz += 2.0f * w * (m_d * final_A - final_D) * dL_dreg * dmd_dd;
-                    }
-
-                    dL_dalpha *= T;
-                    last_alpha = alpha;
-                    dL_dalpha -= T_final * inv_oma * bg_dot_dpixel;
-
-                    const float dL_daraw = (clamp_pass || pr.araw <= GSR_ALPHA_MAX) ? dL_dalpha : 0.f;
-                    const float dL_dG = a3.z * dL_daraw;
-                    gopa = G * dL_daraw;
-
-                    const float Twx = a1.z, Twy = a1.w;
-                    if (pr.use3d) {
-                        const float dL_dsx = dL_dG * (-G * sx) + dL_dz * Twx;
-                        const float dL_dsy = dL_dG * (-G * sy) + dL_dz * Twy;
-                        float dpx = dL_dsx * inv_pz, dpy = dL_dsy * inv_pz;
-                        if (__builtin_expect(pr.tiny_any, 0)) {       // (pair_eval.h: a denormal p.z; the empty asm keeps this a BRANCH -- if-converted it cost
-                            asm volatile("");                         //  three vector instructions on every pair, +3.7 % of K7's issue)
-                            const float zs = pr.tiny ? GSR_TINY_PZ_SCALE : 1.f; dpx *= zs; dpy *= zs;
-                        }
-                        const float dpz = -(dpx * sx + dpy * sy);
-                        const float ux = dpy * pr.lz - dpz * pr.ly, uy = dpz * pr.lx - dpx * pr.lz, uz = dpx * pr.ly - dpy * pr.lx;
-                        const float vx = pr.ky * dpz - pr.kz * dpy, vy = pr.kz * dpx - pr.kx * dpz, vz = pr.kx * dpy - pr.ky * dpx;
-                        gT[0] = ux; gT[1] = uy; gT[2] = uz;
-                        gT[3] = vx; gT[4] = vy; gT[5] = vz;
-                        gT[6] = dL_dz * sx - pxf * ux - pyf * vx;
-                        gT[7] = dL_dz * sy - pxf * uy - pyf * vy;
-                        gT[8] = dL_dz - pxf * uz - pyf * vz;
-                        gxy0 = 0.f; gxy1 = 0.f;
-                    } else {
-                        gxy0 = dL_dG * (-G * GSR_FILTER_INV_SQUARE * pr.dx);
-                        gxy1 = dL_dG * (-G * GSR_FILTER_INV_SQUARE * pr.dy);
-                        gT[0] = 0.f; gT[1] = 0.f; gT[2] = 0.f; gT[3] = 0.f; gT[4] = 0.f; gT[5] = 0.f;
-                        gT[6] = filter_depth_quirk ? sx * dL_dz : 0.f;
-                        gT[7] = filter_depth_quirk ? sy * dL_dz : 0.f;
-                        gT[8] = dL_dz;
-                    }
+                    RB_SUFFIX();
+                    RB_PARTIALS();
                 }
                 // block-level sums of the geometry partials (16 lanes), row layout GSR_GR_*.  A wide payload's colour
                 // gradient lives in the feature rows, so the three colour columns of the row are free: two of them carry
