@@ -11,6 +11,7 @@ import math
 import pytest
 import torch
 
+from adam_ref import _sh_grad_from_record
 from conftest import hip_settings
 
 pytestmark = pytest.mark.gpu
@@ -37,18 +38,6 @@ def _backward(gpu_device, p, cam, factored, deg=3):
     wa = torch.randn(allmap.shape, generator=gen).to(gpu_device) * 0.1
     ((color * wc).sum() + (allmap * wa).sum()).backward()
     return state.take_color_grad(), radii
-
-
-def _sh_grad_from_record(xyz, record, n, deg, coeffs=16):
-    """[N,coeffs,3] = basis(normalize(xyz - campos)) x g, float64."""
-    from gaussmart_amd.sh import sh_basis
-    g = record[:3 * n].view(n, 3).double()
-    campos = record[3 * n:3 * n + 3].double()
-    d = xyz.detach().double() - campos
-    b = sh_basis(deg, d / d.norm(dim=1, keepdim=True))
-    full = torch.zeros(n, coeffs, dtype=torch.float64, device=xyz.device)
-    full[:, :b.shape[1]] = b
-    return full[:, :, None] * g[:, None, :]
 
 
 @pytest.mark.parametrize("deg", [3, 1, 0])
@@ -111,7 +100,9 @@ def test_factored_step_equals_adam_on_explicit_gradients(gpu_device, n, views, d
         # Adam normalises the step to ~lr: compare in units of lr
         assert (a - b).abs().max().item() <= 2e-3 * lr
     for a, b in ((opt.state[f_rest]["exp_avg"], ref.state[r_rest]["exp_avg"]),
-                 (opt.state[f_rest]["exp_avg_sq"], ref.state[r_rest]["exp_avg_sq"])):
+                 (opt.state[f_rest]["exp_avg_sq"], ref.state[r_rest]["exp_avg_sq"]),
+                 (opt.state[f_dc]["exp_avg"], ref.state[r_dc]["exp_avg"]),
+                 (opt.state[f_dc]["exp_avg_sq"], ref.state[r_dc]["exp_avg_sq"])):
         assert (a - b).abs().max().item() <= 1e-5 * b.abs().max().item()
 
 
