@@ -6,7 +6,9 @@
 //   tsdf_scan_*           two exclusive scans of those flags (scan_bodies.h), one launch each half
 //   tsdf_assign_kernel    new blocks get pool slots in grid order, the touched list is compacted
 //   tsdf_integrate_kernel one workgroup per touched block, one thread per voxel column (16 voxels)
+//   tsdf_depth_aabb_kernel running AABB of a view's back-projected valid depth (places the grid before the first touch)
 #include "tsdf_common.h"
+#include "wave_reduce.h"
 
 #include <math.h>
 
@@ -57,6 +59,45 @@ __global__ void __launch_bounds__(256) tsdf_touch_kernel(TsdfGrid g, TsdfCam cam
         for (int y = lo[1]; y <= hi[1]; ++y)
             for (int x = lo[0]; x <= hi[0]; ++x)
                 stamp[x + (int64_t)g.dim[0] * (y + (int64_t)g.dim[1] * z)] = stamp_val;
+}
+
+// Running AABB of the back-projected valid depth (gsr_depth_aabb): floats as order-preserving u32, so that the six running
+// bounds are integer atomics -- exact, and the same whatever the order
+__device__ __forceinline__ uint32_t tsdf_float_key(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+#define TSDF_AABB_MAX_BLOCKS 1024    // grid-stride beyond: a wave folds several pixels per lane before its six atomics
+
+__global__ void __launch_bounds__(256) tsdf_depth_aabb_kernel(TsdfCam cam, const float* __restrict__ depth,
+                                                              const uint8_t* __restrict__ mask, int H, int W,
+                                                              float depth_trunc, uint32_t* __restrict__ bounds) {
+    const int64_t n = (int64_t)H * W, stride = (int64_t)gridDim.x * blockDim.x;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    bool any = false;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float d = depth[i];
+        if (!tsdf_pixel_valid(d, depth_trunc) || (mask && !mask[i])) continue;
+        const int u = (int)(i % W), v = (int)(i / W);
+        const float xc = (u - cam.cx) * d / cam.fx, yc = (v - cam.cy) * d / cam.fy;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const float p = cam.m[4 * r] * xc + cam.m[4 * r + 1] * yc + cam.m[4 * r + 2] * d + cam.m[4 * r + 3];
+            lo[r] = fminf(lo[r], p);
+            hi[r] = fmaxf(hi[r], p);
+        }
+        any = true;
+    }
+    if (!__ballot(any)) return;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const float l = wave_min_f32(lo[r]), h = wave_max_f32(hi[r]);
+        if ((threadIdx.x & 63) == 0) {
+            atomicMin(bounds + r, tsdf_float_key(l));
+            atomicMax(bounds + 3 + r, tsdf_float_key(h));
+        }
+    }
 }
 
 __global__ void __launch_bounds__(256) tsdf_flags_kernel(int64_t n, int stamp_val, const int* __restrict__ stamp,
@@ -318,6 +359,25 @@ extern "C" int32_t gsr_tsdf_integrate(const GsrTsdfVolume* vol, const float* dep
     hipStream_t s = static_cast<hipStream_t>(stream_);
     hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)n_touched), dim3(TSDF_THREADS), 0, s, g, cam, ws.touched,
                        vol->block_index, vol->pool, vol->pool_blocks, depth, mask, rgb, H, W, depth_trunc, vol->sdf_trunc);
+    GSR_LAUNCH_CHECK();
+    return GSR_OK;
+}
+
+extern "C" int32_t gsr_depth_aabb(const float* depth, const uint8_t* mask, int32_t H, int32_t W, const float* intr,
+                                  const float* c2w, float depth_trunc, uint32_t* bounds, gsr_stream_t stream_) {
+    if (H <= 0 || W <= 0) { gsr_set_error("empty image (%d x %d)", H, W); return GSR_E_INVALID; }
+    if (!depth || !intr || !c2w || !bounds) { gsr_set_error("depth, intrinsics, c2w and bounds are required"); return GSR_E_INVALID; }
+    if (!(intr[0] > 0.f) || !(intr[1] > 0.f)) { gsr_set_error("focal lengths must be > 0"); return GSR_E_INVALID; }
+    if (!(depth_trunc > 0.f)) { gsr_set_error("depth_trunc must be > 0 (got %g)", (double)depth_trunc); return GSR_E_INVALID; }
+    double m[12];
+    for (int i = 0; i < 12; ++i) m[i] = c2w[i];
+    const TsdfCam cam = tsdf_cam(intr, m);
+    const int64_t n = (int64_t)H * W;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > TSDF_AABB_MAX_BLOCKS) blocks = TSDF_AABB_MAX_BLOCKS;
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    hipLaunchKernelGGL(tsdf_depth_aabb_kernel, dim3((unsigned)blocks), dim3(256), 0, s, cam, depth, mask, H, W, depth_trunc,
+                       bounds);
     GSR_LAUNCH_CHECK();
     return GSR_OK;
 }

@@ -7,7 +7,14 @@ binary PLY writer / reader that Open3D, trimesh and the reference's evaluation s
     ex.reconstruction(scene.getTrainCameras())
     mesh = ex.extract_mesh_bounded(voxel_size=0.004, sdf_trunc=0.016, depth_trunc=3.0)
     post_process_mesh(mesh, cluster_to_keep=1).write_ply("fuse_post.ply")
+
+The same on the device, from marching cubes to the PLY writer (DeviceTriangleMesh, post_process_mesh_device: the cluster
+filter as kernels, no scipy):
+
+    mesh = ex.extract_mesh_bounded(voxel_size=0.004, sdf_trunc=0.016, depth_trunc=3.0, to_host=False)
+    post_process_mesh_device(mesh, cluster_to_keep=1).write_ply("fuse_post.ply")
 """
+import ctypes as C
 import math
 import os
 from functools import partial
@@ -15,7 +22,8 @@ from functools import partial
 import numpy as np
 import torch
 
-from .tsdf import TSDFVolume, block_aabb_of_points
+from . import _lib
+from .tsdf import DepthBounds, TSDFVolume, block_aabb_of_points
 
 
 class TriangleMesh:
@@ -90,6 +98,90 @@ class TriangleMesh:
             else:
                 raise ValueError(f"{path}: unexpected element {name}")
         return TriangleMesh(verts, tris, cols)
+
+
+class DeviceTriangleMesh:
+    """A TriangleMesh whose arrays are device tensors: vertices f32 [V,3], triangles i32 [F,3], vertex_colors f32 [V,3]."""
+
+    def __init__(self, vertices, triangles, vertex_colors=None):
+        self.vertices = vertices.to(torch.float32).reshape(-1, 3).contiguous()
+        dev = self.vertices.device
+        self.triangles = triangles.to(dev, torch.int32).reshape(-1, 3).contiguous()
+        self.vertex_colors = (torch.zeros_like(self.vertices) if vertex_colors is None
+                              else vertex_colors.to(dev, torch.float32).reshape(-1, 3).contiguous())
+        if self.vertex_colors.shape != self.vertices.shape:
+            raise ValueError(f"vertex_colors must be {list(self.vertices.shape)}, got {list(self.vertex_colors.shape)}")
+
+    @property
+    def device(self):
+        return self.vertices.device
+
+    def __repr__(self):
+        return f"TriangleMesh with {len(self.vertices)} points and {len(self.triangles)} triangles."
+
+    def cpu(self):
+        return TriangleMesh(self.vertices.cpu().numpy(), self.triangles.cpu().numpy(), self.vertex_colors.cpu().numpy())
+
+    def write_ply(self, path):
+        self.cpu().write_ply(path)
+
+
+def mesh_clusters_device(triangles, n_verts):
+    """(labels, cluster_size) int32 [F] device tensors of the device int32 [F,3] triangles: the smallest triangle index of
+    every triangle's edge-connected cluster and that cluster's triangle count (gsr_mesh_clusters).  Only the vertex indices
+    are read, no vertex array: they must lie in [0, n_verts)."""
+    L = _lib.lib()
+    tris = triangles.to(torch.int32).reshape(-1, 3).contiguous()
+    if not tris.is_cuda:
+        raise _lib.GsrError("mesh_clusters_device: triangles must be a device tensor (no CPU path)")
+    F, dev = len(tris), tris.device
+    labels = torch.empty(F, dtype=torch.int32, device=dev)
+    sizes = torch.empty(F, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(1, L.gsr_mesh_clusters_workspace_bytes(F)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(L.gsr_mesh_clusters(C.c_void_p(tris.data_ptr()), F, int(n_verts), C.c_void_p(labels.data_ptr()),
+                                       C.c_void_p(sizes.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), stream))
+    return labels, sizes
+
+
+def post_process_mesh_device(mesh, cluster_to_keep=1000, device=None):
+    """post_process_mesh on the device (gsr_mesh_filter_*: edge sort, union-find, threshold, scans, compaction as kernels):
+    the same arrays, bit for bit, as a DeviceTriangleMesh.  mesh: a DeviceTriangleMesh, or a TriangleMesh with device=."""
+    print(f"post processing the mesh to have {cluster_to_keep} clusterscluster_to_kep")
+    if isinstance(mesh, TriangleMesh):
+        if device is None:
+            raise ValueError("post_process_mesh_device: a host TriangleMesh needs device=")
+        if len(mesh.triangles) and (mesh.triangles.min() < 0 or mesh.triangles.max() >= len(mesh.vertices)):
+            raise ValueError("post_process_mesh_device: a triangle index lies outside the vertex array")
+        mesh = DeviceTriangleMesh(torch.from_numpy(mesh.vertices).to(device), torch.from_numpy(mesh.triangles).to(device),
+                                  torch.from_numpy(mesh.vertex_colors).to(device))
+    if not mesh.vertices.is_cuda:
+        raise _lib.GsrError("post_process_mesh_device: the mesh must live on the device (no CPU path)")
+    L = _lib.lib()
+    dev = mesh.device
+    F, V = len(mesh.triangles), len(mesh.vertices)
+    if F == 0:
+        return DeviceTriangleMesh(torch.zeros((0, 3), device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev),
+                                  torch.zeros((0, 3), device=dev))
+    ws = torch.empty(max(1, L.gsr_mesh_filter_workspace_bytes(F, V)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        nv, nt = C.c_int64(), C.c_int64()
+        tp = C.c_void_p(mesh.triangles.data_ptr())
+        _lib.check(L.gsr_mesh_filter_count(tp, F, V, int(cluster_to_keep), C.c_void_p(ws.data_ptr()), ws.numel(),
+                                           C.byref(nv), C.byref(nt), stream))
+        verts = torch.empty((nv.value, 3), dtype=torch.float32, device=dev)
+        cols = torch.empty((nv.value, 3), dtype=torch.float32, device=dev)
+        tris = torch.empty((nt.value, 3), dtype=torch.int32, device=dev)
+        if nv.value or nt.value:
+            _lib.check(L.gsr_mesh_filter_emit(C.c_void_p(mesh.vertices.data_ptr()), C.c_void_p(mesh.vertex_colors.data_ptr()), tp,
+                                              F, V, C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(verts.data_ptr()),
+                                              C.c_void_p(cols.data_ptr()), C.c_void_p(tris.data_ptr()), stream))
+    out = DeviceTriangleMesh(verts, tris, cols)
+    print(f"num vertices raw {V}")
+    print(f"num vertices post {len(out.vertices)}")
+    return out
 
 
 def post_process_mesh(mesh, cluster_to_keep=1000):
@@ -223,17 +315,40 @@ class GaussianExtractor:
         return block_aabb_of_points(lo, hi, voxel_size, sdf_trunc)
 
     @torch.no_grad()
-    def extract_mesh_bounded(self, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3, mask_backgrond=True):
+    def block_aabb_device(self, voxel_size, sdf_trunc, depth_trunc, mask_backgrond=True):
+        """block_aabb through gsr_depth_aabb: one kernel per view on a running device AABB, ONE host read after the last
+        view (and one for all the camera matrices before the first)."""
+        if not self.viewpoint_stack:
+            return [0, 0, 0], [0, 0, 0]
+        dev = self.depthmaps[0].device
+        w2cs = torch.stack([cam.world_view_transform.T for cam in self.viewpoint_stack]).cpu().double()
+        c2ws = torch.linalg.inv(w2cs).float().numpy()
+        bounds = DepthBounds(dev)
+        for i, cam in enumerate(self.viewpoint_stack):
+            bounds.add(self._masked_depth(i, mask_backgrond), camera_intrinsics(cam), c2ws[i], depth_trunc)
+        ext = bounds.read()
+        if ext is None:
+            return [0, 0, 0], [0, 0, 0]
+        return block_aabb_of_points(ext[0], ext[1], voxel_size, sdf_trunc)
+
+    @torch.no_grad()
+    def extract_mesh_bounded(self, voxel_size=0.004, sdf_trunc=0.02, depth_trunc=3, mask_backgrond=True, aabb="device",
+                             to_host=True):
+        """aabb: "device" (block_aabb_device) or "torch" (block_aabb) -- the AABB only places the grid, the mesh does not
+        depend on which pass found it; to_host=False: a DeviceTriangleMesh."""
+        if aabb not in ("device", "torch"):
+            raise ValueError(f"aabb must be 'device' or 'torch', got {aabb!r}")
         print("Running tsdf volume integration ...")
         print(f"voxel_size: {voxel_size}")
         print(f"sdf_trunc: {sdf_trunc}")
         print(f"depth_truc: {depth_trunc}")
-        aabb = self.block_aabb(voxel_size, sdf_trunc, depth_trunc, mask_backgrond)
+        aabb = (self.block_aabb_device if aabb == "device" else self.block_aabb)(voxel_size, sdf_trunc, depth_trunc,
+                                                                                mask_backgrond)
         volume = TSDFVolume(voxel_size, sdf_trunc, aabb, device=self.gaussians.get_xyz.device)
         for i, cam in enumerate(self.viewpoint_stack):
             volume.integrate(self._masked_depth(i, mask_backgrond), self.rgbmaps[i], camera_intrinsics(cam),
                              cam.world_view_transform.T, depth_trunc)
-        return volume.extract_triangle_mesh()
+        return volume.extract_triangle_mesh(to_host=to_host)
 
     def extract_mesh_unbounded(self, resolution=1024):
         raise NotImplementedError(

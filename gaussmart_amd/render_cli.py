@@ -2,10 +2,12 @@
 
     python -m gaussmart_amd.render_cli -s <scene> -m <model dir> [--iteration -1] [--skip_train] [--skip_test]
         [--skip_mesh] [--voxel_size V] [--depth_trunc D] [--sdf_trunc S] [--num_cluster 50] [--mesh_res 1024]
-        [--depth_ratio R]
+        [--depth_ratio R] [--host_post_process]
 
 Writes MODEL/{train,test}/ours_<it>/{renders,gt,vis} and MODEL/train/ours_<it>/fuse.ply, fuse_post.ply (what the reference's
-scripts/dtu_eval_mesh.py reads).  --unbounded and --render_path are not supported.
+scripts/dtu_eval_mesh.py reads).  The mesh stays on the device from marching cubes to the PLY writer (cluster filter as
+kernels); --host_post_process runs the numpy + scipy filter instead and writes the same bytes.  --unbounded and --render_path
+are not supported.
 """
 import argparse
 import os
@@ -15,7 +17,7 @@ import torch
 
 from .gaussian_model import GaussianModel
 from .gaussian_renderer import render
-from .mesh import GaussianExtractor, post_process_mesh
+from .mesh import GaussianExtractor, post_process_mesh, post_process_mesh_device
 from .params import PipelineParams
 from .scene_io import Scene
 
@@ -41,6 +43,8 @@ def main(argv=None):
     ap.add_argument("--sdf_trunc", default=-1.0, type=float, help="Mesh: truncation value for TSDF")
     ap.add_argument("--num_cluster", default=50, type=int, help="Mesh: number of connected clusters to export")
     ap.add_argument("--unbounded", action="store_true", help="Mesh: using unbounded mode for meshing (not supported)")
+    ap.add_argument("--host_post_process", action="store_true",
+                    help="Mesh: filter the clusters on the host (numpy + scipy) instead of on the device")
     ap.add_argument("--mesh_res", default=1024, type=int, help="Mesh: resolution for unbounded mesh extraction")
     args = ap.parse_args(argv)
     if args.unbounded:
@@ -80,10 +84,14 @@ def main(argv=None):
         depth_trunc = (ex.radius * 2.0) if args.depth_trunc < 0 else args.depth_trunc
         voxel_size = (depth_trunc / args.mesh_res) if args.voxel_size < 0 else args.voxel_size
         sdf_trunc = 5.0 * voxel_size if args.sdf_trunc < 0 else args.sdf_trunc
-        mesh = ex.extract_mesh_bounded(voxel_size=voxel_size, sdf_trunc=sdf_trunc, depth_trunc=depth_trunc)
+        mesh = ex.extract_mesh_bounded(voxel_size=voxel_size, sdf_trunc=sdf_trunc, depth_trunc=depth_trunc, aabb="device",
+                                       to_host=False)
+        if args.host_post_process:
+            mesh = mesh.cpu()
         mesh.write_ply(os.path.join(train_dir, name))
         print("mesh saved at {}".format(os.path.join(train_dir, name)))
-        mesh_post = post_process_mesh(mesh, cluster_to_keep=args.num_cluster)
+        post = post_process_mesh if args.host_post_process else post_process_mesh_device
+        mesh_post = post(mesh, cluster_to_keep=args.num_cluster)
         mesh_post.write_ply(os.path.join(train_dir, name.replace(".ply", "_post.ply")))
         print("mesh post processed saved at {}".format(os.path.join(train_dir, name.replace(".ply", "_post.ply"))))
 

@@ -4,6 +4,7 @@ ScalableTSDFVolume with RGB8 colour (utils/mesh_utils.py:142-167), fusion and ma
     vol = TSDFVolume(voxel_size, sdf_trunc, block_aabb)
     vol.integrate(depth[1,H,W], rgb[3,H,W], (fx, fy, cx, cy), w2c[4,4], depth_trunc, mask=None)   # per view
     mesh = vol.extract_triangle_mesh()                                                            # mesh.TriangleMesh
+    mesh = vol.extract_triangle_mesh(to_host=False)                                               # mesh.DeviceTriangleMesh
 
 block_aabb = (lo, hi): integer block coordinates, hi exclusive; block b holds voxels [16 b, 16 b + 16) and voxel g has its
 centre at (g + 0.5) * voxel_size.  block_aabb_of_points() derives one from the extent of the back-projected depth.
@@ -166,8 +167,10 @@ class TSDFVolume:
         off, n = self._slot_block_offset, self.n_blocks
         return self.workspace[off:off + 4 * n].view(torch.int32)
 
-    def extract_triangle_mesh(self):
-        from .mesh import TriangleMesh
+    def extract_triangle_mesh(self, to_host=True):
+        """Marching cubes over the allocated blocks: a mesh.TriangleMesh (numpy), or with to_host=False a
+        mesh.DeviceTriangleMesh whose arrays stay on the device (no copy)."""
+        from .mesh import DeviceTriangleMesh, TriangleMesh
         L = _lib.lib()
         A = self.n_alloc
         ws = torch.empty(max(1, L.gsr_mcubes_workspace_bytes(A)), dtype=torch.uint8, device=self.device)
@@ -183,4 +186,45 @@ class TSDFVolume:
                 _lib.check(L.gsr_mcubes_emit(C.byref(self._v), C.c_void_p(ws.data_ptr()), ws.numel(),
                                              C.c_void_p(verts.data_ptr()), C.c_void_p(cols.data_ptr()),
                                              C.c_void_p(tris.data_ptr()), stream))
+        if not to_host:
+            return DeviceTriangleMesh(verts, tris, cols)
         return TriangleMesh(verts.cpu().numpy(), tris.cpu().numpy(), cols.cpu().numpy())
+
+
+class DepthBounds:
+    """Running world-space AABB of back-projected valid depth on the device (gsr_depth_aabb): add() enqueues one kernel per
+    view and reads nothing back; read() is the one host read, after the last view."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        # order-preserving u32 keys of floats: (max, max, max, 0, 0, 0) = nothing seen yet
+        self.words = torch.tensor([-1, -1, -1, 0, 0, 0], dtype=torch.int32, device=self.device)
+
+    def add(self, depth, intrinsics, c2w, depth_trunc, mask=None):
+        """depth [1,H,W] / [H,W], intrinsics (fx, fy, cx, cy) or K, c2w [4,4] camera-to-world, mask [H,W] (False: pixel
+        ignored) or None; the tensors must stay alive until the stream has run the kernel (read() waits for it)."""
+        d = depth.detach().to(self.device, torch.float32).contiguous()
+        if d.dim() == 3:
+            d = d[0]
+        H, W = d.shape
+        m = None
+        if mask is not None:
+            m = mask.detach().to(self.device).reshape(H, W).to(torch.uint8).contiguous()
+        intr, M = _intrinsics(intrinsics), _host_floats(c2w, 16, "c2w")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            _lib.check(_lib.lib().gsr_depth_aabb(C.c_void_p(d.data_ptr()), C.c_void_p(m.data_ptr()) if m is not None else None,
+                                                 H, W, intr, M, float(depth_trunc), C.c_void_p(self.words.data_ptr()),
+                                                 C.c_void_p(stream.cuda_stream)))
+            d.record_stream(stream)
+            if m is not None:
+                m.record_stream(stream)
+
+    def read(self):
+        """(lo, hi) float32 [3] each, or None when no pixel was valid."""
+        k = self.words.cpu().numpy().view(np.uint32)
+        if (k[:3] == 0xFFFFFFFF).all() and (k[3:] == 0).all():
+            return None
+        bits = np.where(k & 0x80000000, k ^ np.uint32(0x80000000), ~k).astype(np.uint32)
+        f = bits.view(np.float32)
+        return f[:3].copy(), f[3:].copy()

@@ -34,9 +34,10 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 7   /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
+#define GSR_ABI_VERSION 8   /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
                                 6: gsr_surface_maps_forward / _backward;
-                                7: TSDF fusion and marching cubes (GsrTsdfVolume, gsr_tsdf_*, gsr_mcubes_*) */
+                                7: TSDF fusion and marching cubes (GsrTsdfVolume, gsr_tsdf_*, gsr_mcubes_*);
+                                8: mesh post-processing (gsr_mesh_*) and gsr_depth_aabb */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -466,6 +467,48 @@ int32_t gsr_mcubes_count(const GsrTsdfVolume* vol, void* ws, size_t ws_bytes, in
                          gsr_stream_t stream);
 int32_t gsr_mcubes_emit(const GsrTsdfVolume* vol, void* ws, size_t ws_bytes, float* verts, float* colors, int32_t* tris,
                         gsr_stream_t stream);
+
+/* Running world-space AABB of one view's back-projected valid depth (what places the TSDF grid before the first touch).
+ * A pixel is valid exactly as in gsr_tsdf_touch; its point is pc = ((u - cx) d / fx, (v - cy) d / fy, d), pw = R pc + t in fp32,
+ * with c2w_host the row-major 4x4 camera-to-world matrix (only its first three rows are read).  bounds: device u32 [6] =
+ * (min x, y, z, max x, y, z), floats in the order-preserving encoding  key(f) = bits(f) ^ (bits(f) >> 31 ? 0xffffffff :
+ * 0x80000000); the caller initialises it to (0xffffffff x 3, 0 x 3) and decodes it once after the last view.  Per-wave min /
+ * max, then one integer atomicMin / atomicMax per wave and axis: exact and order-independent.  No synchronisation, no host
+ * read; a view without a valid pixel leaves bounds untouched. */
+int32_t gsr_depth_aabb(const float* depth, const uint8_t* mask, int32_t H, int32_t W, const float* intrinsics_host,
+                       const float* c2w_host, float depth_trunc, uint32_t* bounds, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- mesh export: triangle clusters and the cluster filter
+ * The reference's post_process_mesh (utils/mesh_utils.py:21-42: Open3D's cluster_connected_triangles, then
+ * remove_triangles_by_mask / remove_unreferenced_vertices / remove_degenerate_triangles) as kernels (mesh_post.hip), with the
+ * semantics of gaussmart_amd/mesh.py: post_process_mesh, bit for bit:
+ *   - two triangles are linked when they share an undirected edge (min(a,b), max(a,b)); clusters are the connected
+ *     components (all triangles of a non-manifold edge are linked);
+ *   - k = min(cluster_to_keep, number of clusters); threshold = max(k-th largest cluster size, 50); a triangle is kept when
+ *     its cluster's size is >= threshold (ties are kept);
+ *   - a vertex is kept when a kept triangle uses it (decided BEFORE degenerate triangles are dropped); vertices are
+ *     compacted in order, triangle indices remapped, then triangles with two equal indices are dropped; order is preserved.
+ * tris: device int32 [n_tris,3].  A vertex index outside [0, n_verts) is the caller's error: it is NOT checked on the device
+ * (gsr_mesh_clusters only sorts by the indices; the filter indexes per-vertex arrays with them).
+ *   gsr_mesh_clusters    : labels[t] = smallest triangle index of t's cluster, cluster_size[t] = its triangle count.  Edge
+ *                          records sorted by (lo, hi) with the library's radix sort (two stable sorts over the bits n_verts - 1
+ *                          uses), lock-free union-find, integer counts: identical on every run.  No synchronisation.
+ *   gsr_mesh_filter_count: clusters, the threshold (on the device), the keep marks and the two scans; ONE stream
+ *                          synchronisation reads the two totals.  ws: gsr_mesh_filter_workspace_bytes(n_tris, n_verts).
+ *   gsr_mesh_filter_emit : vertices / colours f32 [n_verts_out,3] and triangles int32 [n_tris_out,3] (same arguments, same
+ *                          workspace, nothing else enqueued on it in between).
+ * n_tris == 0: nothing is launched, the totals are 0.  Negative counts, cluster_to_keep < 1, a null pointer with a non-zero
+ * count or a workspace that is too small: GSR_E_INVALID, the message names the argument.  3 n_tris > 2^31 - 1 (the sort's
+ * element count) or n_verts > 2^31 - 1: GSR_E_UNSUPPORTED. */
+size_t gsr_mesh_clusters_workspace_bytes(int64_t n_tris);
+size_t gsr_mesh_filter_workspace_bytes(int64_t n_tris, int64_t n_verts);
+int32_t gsr_mesh_clusters(const int32_t* tris, int64_t n_tris, int64_t n_verts, int32_t* labels, int32_t* cluster_size,
+                          void* ws, size_t ws_bytes, gsr_stream_t stream);
+int32_t gsr_mesh_filter_count(const int32_t* tris, int64_t n_tris, int64_t n_verts, int32_t cluster_to_keep, void* ws,
+                              size_t ws_bytes, int64_t* n_verts_out, int64_t* n_tris_out, gsr_stream_t stream);
+int32_t gsr_mesh_filter_emit(const float* verts, const float* colors, const int32_t* tris, int64_t n_tris, int64_t n_verts,
+                             void* ws, size_t ws_bytes, float* verts_out, float* colors_out, int32_t* tris_out,
+                             gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only

@@ -1,10 +1,14 @@
 """Developer probe: time each part of the bounded mesh export (gaussmart_amd.mesh) on a unit-sphere surfel scene at the DTU
 flags (--voxel_size 0.004 --sdf_trunc 0.016 --depth_trunc 3.0, depth_ratio 1): rendering the views, the block AABB,
-TSDF touch + integrate, marching cubes and post-processing.  Prints one JSON line.
+TSDF touch + integrate, marching cubes and post-processing.  The AABB pass, the extraction and the post-processing are timed
+on the host path (torch AABB, mesh copied to the host, numpy + scipy filter) and on the device path (gsr_depth_aabb, mesh kept
+on the device, gsr_mesh_filter_*) in the same run; both must give equal arrays.  Prints one JSON line.
 
     python scripts/mesh_bench.py [--surfels 300000] [--views 49] [--width 1600] [--height 1200]
 """
 import argparse
+import contextlib
+import io
 import json
 import math
 import os
@@ -38,7 +42,7 @@ def main():
     from gaussmart_amd.camera import look_at_camera
     from gaussmart_amd.gaussian_model import GaussianModel
     from gaussmart_amd.gaussian_renderer import render
-    from gaussmart_amd.mesh import GaussianExtractor, camera_intrinsics, post_process_mesh
+    from gaussmart_amd.mesh import GaussianExtractor, camera_intrinsics, post_process_mesh, post_process_mesh_device
     from gaussmart_amd.params import PipelineParams
     from gaussmart_amd.tsdf import TSDFVolume
     dev = torch.device("cuda", 0)
@@ -70,21 +74,40 @@ def main():
         sync(); t1 = time.perf_counter()
         aabb = ex.block_aabb(args.voxel_size, args.sdf_trunc, args.depth_trunc)
         sync(); t2 = time.perf_counter()
-        vol = TSDFVolume(args.voxel_size, args.sdf_trunc, aabb, device=dev)
+        aabb_dev = ex.block_aabb_device(args.voxel_size, args.sdf_trunc, args.depth_trunc)
+        sync(); t2d = time.perf_counter()
+        vol = TSDFVolume(args.voxel_size, args.sdf_trunc, aabb_dev, device=dev)
         touched = [vol.integrate(ex._masked_depth(i, True), ex.rgbmaps[i], camera_intrinsics(c), c.world_view_transform.T,
                                  args.depth_trunc) for i, c in enumerate(cams)]
         sync(); t3 = time.perf_counter()
         mesh = vol.extract_triangle_mesh()
         sync(); t4 = time.perf_counter()
-        post = post_process_mesh(mesh, 1)
+        with contextlib.redirect_stdout(io.StringIO()):
+            post = post_process_mesh(mesh, 1)
         t5 = time.perf_counter()
+        dmesh = vol.extract_triangle_mesh(to_host=False)
+        sync(); t6 = time.perf_counter()
+        with contextlib.redirect_stdout(io.StringIO()):
+            dpost = post_process_mesh_device(dmesh, 1)
+        sync(); t7 = time.perf_counter()
+        dmesh_host, dpost_host = dmesh.cpu(), dpost.cpu()      # what writing fuse.ply and fuse_post.ply copies
+        t8 = time.perf_counter()
+        for a, b in ((mesh, dmesh_host), (post, dpost_host)):
+            for f in ("vertices", "triangles", "vertex_colors"):
+                x, y = getattr(a, f), getattr(b, f)
+                assert x.dtype == y.dtype and np.array_equal(x, y), f"host and device path differ in {f}"
+        ti = 1e3 * (t3 - t2d)
         res = {"surfels": n, "views": args.views, "width": args.width, "height": args.height,
                "voxel_size": args.voxel_size, "sdf_trunc": args.sdf_trunc, "depth_trunc": args.depth_trunc,
                "grid_blocks": vol.n_blocks, "allocated_blocks": vol.n_alloc, "mean_touched_per_view": float(np.mean(touched)),
                "vertices": len(mesh.vertices), "triangles": len(mesh.triangles), "post_vertices": len(post.vertices),
-               "render_ms": 1e3 * (t1 - t0), "aabb_ms": 1e3 * (t2 - t1), "touch_integrate_ms": 1e3 * (t3 - t2),
-               "marching_cubes_ms": 1e3 * (t4 - t3), "post_process_ms": 1e3 * (t5 - t4),
-               "integrate_plus_extract_ms": 1e3 * (t4 - t2), "repeat": rep}
+               "block_aabb": aabb, "block_aabb_device": aabb_dev,
+               "render_ms": 1e3 * (t1 - t0), "aabb_ms": 1e3 * (t2 - t1), "aabb_device_ms": 1e3 * (t2d - t2),
+               "touch_integrate_ms": ti, "marching_cubes_ms": 1e3 * (t4 - t3), "extract_device_ms": 1e3 * (t6 - t5),
+               "post_process_ms": 1e3 * (t5 - t4), "post_process_device_ms": 1e3 * (t7 - t6),
+               "device_to_host_ms": 1e3 * (t8 - t7), "integrate_plus_extract_ms": 1e3 * (t4 - t2d),
+               "export_total_ms_host": 1e3 * ((t2 - t1) + (t5 - t3)) + ti,
+               "export_total_ms_device": 1e3 * ((t2d - t2) + (t8 - t5)) + ti, "repeat": rep}
     print(json.dumps(res))
 
 
