@@ -11,10 +11,11 @@
 //   mp_threshold_kernel  one thread: max(sorted[F - min(k, n_clusters)], 50) -> a device word
 //   mp_mark_kernel       keep_tri, used[v] (before the degenerate test), emit flag keep && !degenerate
 //   (scans)              vertex and triangle offsets (binning.hip's scan); ONE synchronisation reads the two totals
-//   (compact rows)       vertices and colours in one launch (compact.hip);  mp_emit_tris_kernel writes the remapped triangles
+//   (compact rows)       vertices and colours in one launch (compact.hip);  mesh_emit_tris_kernel (mesh_emit.h) writes the remapped triangles
 //
 // Everything is integer work: labels, counts and the output are the same on every run, whatever the schedule.
 #include "gsr_common.h"
+#include "mesh_emit.h"
 
 #define MP_MIN_CLUSTER 50u            // utils/mesh_utils.py:36: never keep a cluster below 50 triangles
 #define MP_MAX_EDGES 0x7fffffffLL     // the sort's element count is an int32
@@ -256,16 +257,6 @@ __global__ void __launch_bounds__(256) mp_mark_kernel(const int32_t* __restrict_
     emit[t] = keep && a != b && b != c && a != c;
 }
 
-__global__ void __launch_bounds__(256) mp_emit_tris_kernel(const int32_t* __restrict__ tris, int64_t F,
-                                                           const uint8_t* __restrict__ emit, const uint32_t* __restrict__ tri_off,
-                                                           const uint32_t* __restrict__ vert_off, int32_t* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= F || !emit[t]) return;
-    const int64_t o = 3 * (int64_t)tri_off[t];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[o + k] = (int32_t)vert_off[tris[3 * t + k]];
-}
-
 extern "C" int32_t gsr_mesh_filter_count(const int32_t* tris, int64_t n_tris, int64_t n_verts, int32_t cluster_to_keep,
                                          void* ws, size_t ws_bytes, int64_t* n_verts_out, int64_t* n_tris_out,
                                          gsr_stream_t stream_) {
@@ -333,7 +324,7 @@ extern "C" int32_t gsr_mesh_filter_emit(const float* verts, const float* colors,
     rc = gsr_compact_apply(2, src, dst, row_bytes, n_verts, w.used, w.vert_off, stream_);
     if (rc != GSR_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream_);
-    hipLaunchKernelGGL(mp_emit_tris_kernel, dim3((unsigned)((n_tris + 255) / 256)), dim3(256), 0, s, tris, n_tris, w.emit,
+    hipLaunchKernelGGL(mesh_emit_tris_kernel, dim3((unsigned)((n_tris + 255) / 256)), dim3(256), 0, s, tris, n_tris, w.emit,
                        w.tri_off, w.vert_off, tris_out);
     GSR_LAUNCH_CHECK();
     return GSR_OK;

@@ -34,10 +34,11 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 8   /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
+#define GSR_ABI_VERSION 9   /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
                                 6: gsr_surface_maps_forward / _backward;
                                 7: TSDF fusion and marching cubes (GsrTsdfVolume, gsr_tsdf_*, gsr_mcubes_*);
-                                8: mesh post-processing (gsr_mesh_*) and gsr_depth_aabb */
+                                8: mesh post-processing (gsr_mesh_*) and gsr_depth_aabb;
+                                9: mesh culling by view masks (gsr_mask_dilate_*, gsr_mesh_cull_*) */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -509,6 +510,74 @@ int32_t gsr_mesh_filter_count(const int32_t* tris, int64_t n_tris, int64_t n_ver
 int32_t gsr_mesh_filter_emit(const float* verts, const float* colors, const int32_t* tris, int64_t n_tris, int64_t n_verts,
                              void* ws, size_t ws_bytes, float* verts_out, float* colors_out, int32_t* tris_out,
                              gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- mesh evaluation: culling by view masks
+ * The reference's cull_scan (scripts/eval_dtu/evaluate_single_scene.py:19-101: skimage's binary_dilation with disk(24), a
+ * projection of every vertex into every view, grid_sample on the dilated mask, trimesh's update_vertices / update_faces) as
+ * kernels (mesh_cull.hip).  Inputs: a mesh (f32 vertices [V,3], optional f32 colours [V,3], int32 triangles [F,3]) and n views,
+ * each with a row-major 3x4 projection and a uint8 mask [H,W].  The rules, each in this one place:
+ *   CULL_MASK_BINARISE  a mask pixel is set when its byte is non-zero (the reference divides channel 0 by 256 and lets the
+ *                       dilation treat non-zero as true).
+ *   CULL_DISK           the structuring element of radius r is dx^2 + dy^2 <= r^2.  RECALLED from scikit-image's `disk`, which
+ *                       is not available to read here (like the Open3D rules of the block above).  Pixels outside the image
+ *                       count as unset; r = 0 is the identity (binarised); the reference uses r = 24.
+ *   CULL_PROJECT        the per-view matrix is Pn = P / ||P[2,:3]||, P = (world_mat @ scale_mat)[:3,:4], formed on the host in
+ *                       float64 from the float32 matrices and passed as f32 (gaussmart_amd/mesh_cull.py: dtu_projection, which
+ *                       refuses det(P[:,:3]) <= 0).  For det > 0 it equals the reference's K/K[2,2] @ inverse(pose) of
+ *                       load_K_Rt_from_P (scripts/eval_dtu/render_utils.py:31-52): the third row carries true camera depth,
+ *                       which matters only because of the + 1e-6.  On the device in fp32, fmaf in this order:
+ *                         p.k = fmaf(Pn[k][2], z, fmaf(Pn[k][1], y, fmaf(Pn[k][0], x, Pn[k][3])))      k = x, y, z
+ *                         u = p.x / (p.z + 1e-6f),  v = p.y / (p.z + 1e-6f)
+ *                         gx = (u / (Wn - 1) - 0.5f) * 2,  gy = (v / (Hn - 1) - 0.5f) * 2
+ *                         valid = -1 < gx < 1 && -1 < gy < 1   (strict; NaN makes it false)
+ *                       Wn, Hn: the size the pixel coordinates are normalised by (the reference hard-codes 1600 x 1200, DTU's
+ *                       mask size; the Python layer defaults to the mask size).  Wn = 1 or Hn = 1 divides by zero: no vertex
+ *                       is valid in such a view.  Depth gets no special treatment: a vertex behind the camera is handled
+ *                       exactly as the formula says.
+ *   CULL_SAMPLE         ix = nearbyint((gx + 1) / 2 * (W - 1)), half to even; iy likewise with H.  The sample is the dilated
+ *                       mask at (iy, ix) when that is inside the image, else 0: grid_sample(mode='nearest',
+ *                       padding_mode='zeros', align_corners=True).
+ *   CULL_VOTE           a view keeps a vertex when sample != 0 || !valid; a vertex is kept when every view keeps it.  With
+ *                       zero views every vertex is kept.
+ *   CULL_COMPACT        a triangle is kept when its three vertices are kept.  Kept vertices are compacted in order, whether or
+ *                       not a kept triangle still uses them; triangles are remapped with their order preserved; degenerate
+ *                       triangles are NOT dropped (trimesh's update_vertices(mask) + update_faces(face_mask); not the rule of
+ *                       the cluster filter above).
+ *   CULL_TO_WORLD       output vertex = fmaf(v, s, t) per component in fp32, scale_offset_host = (s, t.x, t.y, t.z) with s =
+ *                       scale_mat_0[0,0], t = scale_mat_0[:3,3]; NULL: the vertex is copied unchanged.  Colours are carried
+ *                       through unchanged.  DEVIATION: the reference does this product in float64 inside trimesh; meshes
+ *                       here are f32 end to end.
+ *   gsr_mask_dilate_disk : masks, out: device uint8 [n,H,W]; out is 0 / 1.  Exact integer work in two passes (per row the
+ *                          horizontal distance to the nearest set pixel, capped at r + 1, in ws; then per pixel the rows dy in
+ *                          [-r, r] against the integer span table w(dy) = floor(sqrt(r^2 - dy^2))): the same bytes whatever the
+ *                          launch shape.  radius 0 ... 127; larger: GSR_E_UNSUPPORTED.  No synchronisation.
+ *   gsr_mesh_cull_count  : the vote (one thread per vertex over the views in index order, out at the first view that removes
+ *                          it), the triangle marks and the two scans; ONE stream synchronisation per call reads the two
+ *                          totals (a caller that passes the views in k chunks pays the marks, scans and read-back k times).
+ *                          dilated: device uint8 [n_views,H,W], non-zero = set; proj_host: host f32 [n_views,12], uploaded into
+ *                          ws.  vertex_keep (device uint8 [n_verts], may be NULL) is IN / OUT: on entry the marks left by the
+ *                          calls for earlier chunks of views (the caller fills it with 1 before the first), on return those
+ *                          marks ANDed with this call's views -- so the views may arrive in chunks and the totals of the
+ *                          last call are those of all views.  NULL: the marks start as all kept.
+ *                          ws: gsr_mesh_cull_workspace_bytes(n_tris, n_verts, n_views).
+ *   gsr_mesh_cull_emit   : vertices / colours f32 [n_verts_out,3] and triangles int32 [n_tris_out,3] of the preceding count
+ *                          call (same mesh, same workspace, nothing else enqueued on it in between); colors NULL: colors_out
+ *                          is not written.
+ * n_verts == 0 launches nothing and the totals are 0; n_tris == 0 launches nothing for the triangles (the vertices of a mesh
+ * without triangles are still culled: CULL_COMPACT keeps vertices no triangle uses).  Negative counts, H, W, Wn or Hn < 1, a
+ * negative radius, a null pointer with a non-zero count or a workspace that is too small: GSR_E_INVALID before anything is
+ * launched, the message names the argument.  A vertex index outside [0, n_verts) is the caller's error, as above. */
+size_t gsr_mask_dilate_workspace_bytes(int32_t n, int32_t H, int32_t W);
+int32_t gsr_mask_dilate_disk(const uint8_t* masks, int32_t n, int32_t H, int32_t W, int32_t radius, uint8_t* out, void* ws,
+                             size_t ws_bytes, gsr_stream_t stream);
+size_t gsr_mesh_cull_workspace_bytes(int64_t n_tris, int64_t n_verts, int32_t n_views);
+int32_t gsr_mesh_cull_count(const float* verts, const int32_t* tris, int64_t n_tris, int64_t n_verts, const uint8_t* dilated,
+                            int32_t n_views, int32_t H, int32_t W, int32_t Wn, int32_t Hn, const float* proj_host, void* ws,
+                            size_t ws_bytes, uint8_t* vertex_keep, int64_t* n_verts_out, int64_t* n_tris_out,
+                            gsr_stream_t stream);
+int32_t gsr_mesh_cull_emit(const float* verts, const float* colors, const int32_t* tris, int64_t n_tris, int64_t n_verts,
+                           const float* scale_offset_host, void* ws, size_t ws_bytes, float* verts_out, float* colors_out,
+                           int32_t* tris_out, gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only

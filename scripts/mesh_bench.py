@@ -4,7 +4,15 @@ TSDF touch + integrate, marching cubes and post-processing.  The AABB pass, the 
 on the host path (torch AABB, mesh copied to the host, numpy + scipy filter) and on the device path (gsr_depth_aabb, mesh kept
 on the device, gsr_mesh_filter_*) in the same run; both must give equal arrays.  Prints one JSON line.
 
+With --cull the post-processed mesh is then culled against one synthetic ellipse mask per view (gaussmart_amd.mesh_cull: the
+DTU evaluation's cull_scan, disk radius 24) on the device and on the host path in the same run; the two keep masks must be
+equal outside the unstable set (a vertex whose vote changes within DELTA pixels, scaled to the frame width, of its float64 position:
+tests/mesh_cull_ref.py); a second JSON
+line with the times goes to --cull_out (default profiles/r07_mesh_cull_bench.json).  cull_device_ms starts from masks on
+the device, cull_host_ms from masks in host memory; the comparison the script asserts adds mask_upload_ms to the device side.
+
     python scripts/mesh_bench.py [--surfels 300000] [--views 49] [--width 1600] [--height 1200]
+    python scripts/mesh_bench.py --cull
 """
 import argparse
 import contextlib
@@ -18,7 +26,9 @@ import time
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.join(ROOT, "tests"))          # mesh_cull_ref: the stability rule of the culling comparison
 
 
 def fib(n):
@@ -38,6 +48,10 @@ def main():
     ap.add_argument("--sdf_trunc", type=float, default=0.016)
     ap.add_argument("--depth_trunc", type=float, default=3.0)
     ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--cull", action="store_true", help="also time the mask culling of the post-processed mesh")
+    ap.add_argument("--cull_radius", type=int, default=24)
+    ap.add_argument("--cull_out", type=str, default=os.path.join(ROOT, "profiles", "r07_mesh_cull_bench.json"),
+                    help="the culling JSON line is written to this file as well")
     args = ap.parse_args()
     from gaussmart_amd.camera import look_at_camera
     from gaussmart_amd.gaussian_model import GaussianModel
@@ -109,6 +123,91 @@ def main():
                "export_total_ms_host": 1e3 * ((t2 - t1) + (t5 - t3)) + ti,
                "export_total_ms_device": 1e3 * ((t2d - t2) + (t8 - t5)) + ti, "repeat": rep}
     print(json.dumps(res))
+    if args.cull:
+        cull = cull_bench(args, cams, dpost, dev)
+        print(json.dumps(cull))
+        if args.cull_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.cull_out)), exist_ok=True)
+            with open(args.cull_out, "w") as f:
+                f.write(json.dumps(cull) + "\n")
+
+
+def cull_views(cams, width, height):
+    """One projection and one ellipse mask per camera.  The ellipse sits on the sphere's image, a little wider and a little
+    flatter than it and shifted sideways: every view cuts slivers off the limb, and all views together leave about 60 % of the
+    sphere (ellipses smaller than the image would leave nothing: every vertex is on some view's limb)."""
+    from gaussmart_amd.mesh import camera_intrinsics
+    from gaussmart_amd.mesh_cull import dtu_projection
+    proj, masks = [], []
+    y, x = np.mgrid[0:height, 0:width]
+    for i, cam in enumerate(cams):
+        fx, fy, cx, cy = camera_intrinsics(cam)
+        wm = np.eye(4)
+        wm[:3, :4] = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1.0]]) @ cam.world_view_transform.T.cpu().numpy().astype(np.float64)[:3]
+        proj.append(dtu_projection(wm, np.eye(4)))
+        r_img = fx / math.sqrt(2.5 ** 2 - 1.0)                 # the unit sphere's image radius from distance 2.5
+        a, b = r_img * (1.10 + 0.05 * math.sin(i)), r_img * (0.95 + 0.05 * math.cos(2 * i))
+        masks.append(((((x - cx - 0.1 * r_img * math.sin(3 * i)) / a) ** 2 + ((y - cy) / b) ** 2) <= 1).astype(np.uint8) * 255)
+    return np.stack(proj), np.stack(masks)
+
+
+def unstable_vertices(verts, proj, dilated, delta):
+    """bool [V]: the stability rule of tests/mesh_cull_ref.py (its vote_at and pixel_positions64, nothing restated here), one view
+    at a time to keep the arrays small: some view's vote differs among the four positions (cx +- delta, cy +- delta) around the
+    float64 pixel position, and no view whose vote is the same at all four removes the vertex."""
+    import mesh_cull_ref as R
+    n, H, W = dilated.shape
+    unstable_any = np.zeros(len(verts), bool)
+    stable_remove = np.zeros(len(verts), bool)
+    for i in range(n):
+        cx, cy = R.pixel_positions64(verts, proj[i:i + 1], (H, W), (H, W))
+        votes = np.stack([R.vote_at(cx + sx, cy + sy, dilated[i:i + 1])[0][0] for sx in (-delta, delta) for sy in (-delta, delta)])
+        same = (votes == votes[0]).all(0)
+        unstable_any |= ~same
+        stable_remove |= same & ~votes[0]
+    return unstable_any & ~stable_remove
+
+
+def cull_bench(args, cams, dpost, dev):
+    from gaussmart_amd.mesh_cull import compact_host, cull_mesh_by_masks, dilate_masks, dilate_masks_host, vote_host
+    import mesh_cull_ref as R
+    sync = torch.cuda.synchronize
+    proj, masks = cull_views(cams, args.width, args.height)
+    hpost = dpost.cpu()
+    r = args.cull_radius
+    out = {}
+    for rep in range(args.repeats):
+        sync(); t0 = time.perf_counter()
+        dmasks = torch.from_numpy(masks).to(dev)
+        sync(); t1 = time.perf_counter()
+        dil = dilate_masks(dmasks, r)
+        sync(); t2 = time.perf_counter()
+        dculled, dkeep = cull_mesh_by_masks(dpost, proj, dmasks, r, return_keep=True)      # dilates again: the whole step
+        sync(); t3 = time.perf_counter()
+        hdil = dilate_masks_host(masks, r)                     # the three steps of cull_mesh_by_masks_host
+        t4 = time.perf_counter()
+        hkeep = vote_host(hpost.vertices, proj, hdil)
+        hculled = compact_host(hpost, hkeep)
+        t5 = time.perf_counter()
+        assert np.array_equal(dil.cpu().numpy(), hdil), "device and host dilation differ"
+        dk = dkeep.cpu().numpy().astype(bool)
+        # DELTA was measured on 320-pixel-wide frames; the pixel error of the fp32 projection grows with the coordinates
+        unstable = unstable_vertices(hpost.vertices, proj, hdil, R.DELTA * args.width / 320)
+        differ = dk != hkeep
+        assert not (differ & ~unstable).any(), f"{int((differ & ~unstable).sum())} stable vertices differ between the paths"
+        assert len(hculled.vertices) == int(hkeep.sum())
+        assert 0.1 < dk.mean() < 0.9, f"the masks leave {dk.mean():.1%} of the vertices: not a culling workload"
+        # both paths from masks in host memory: the device side pays the upload as well
+        assert (t1 - t0) + (t3 - t2) <= (t5 - t3), "the device path is slower than the host path"
+        out = {"views": len(cams), "width": args.width, "height": args.height, "radius": r,
+               "vertices": len(hpost.vertices), "triangles": len(hpost.triangles),
+               "culled_vertices": int(dk.sum()), "culled_triangles": len(dculled.triangles),
+               "host_culled_vertices": int(hkeep.sum()), "unstable_vertices": int(unstable.sum()),
+               "differing_vertices": int(differ.sum()),
+               "mask_upload_ms": 1e3 * (t1 - t0), "dilate_device_ms": 1e3 * (t2 - t1), "cull_device_ms": 1e3 * (t3 - t2),
+               "cull_device_with_upload_ms": 1e3 * ((t1 - t0) + (t3 - t2)),
+               "dilate_host_ms": 1e3 * (t4 - t3), "cull_host_ms": 1e3 * (t5 - t3), "repeat": rep}
+    return out
 
 
 if __name__ == "__main__":
