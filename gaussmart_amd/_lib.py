@@ -16,7 +16,7 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSR_LIB_PATH: developer aid for same-box A/B runs of two builds of the library (scripts/ab_builds.sh)
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "lib", "libgsr_hip.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_SCRATCH, GSR_BUF_SCRATCH2 = range(5)
 GSR_BUF_SYNC_SH = 100     # not a buffer: "the SH colour pass is about to be enqueued" (GSR_FLAG_DEFER_COLOR)
@@ -243,6 +243,23 @@ def lib():
         L.gsr_mesh_cull_emit.restype = C.c_int32
         L.gsr_mesh_cull_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                          C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.gsr_mesh_depth_workspace_bytes.restype = C.c_size_t
+        L.gsr_mesh_depth_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+        L.gsr_mesh_depth_render.restype = C.c_int32
+        L.gsr_mesh_depth_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.gsr_mesh_vis_count.restype = C.c_int32
+        L.gsr_mesh_vis_count.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]
+        L.gsr_mesh_vis_workspace_bytes.restype = C.c_size_t
+        L.gsr_mesh_vis_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+        L.gsr_mesh_vis_compact_count.restype = C.c_int32
+        L.gsr_mesh_vis_compact_count.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t,
+                                                 C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]
+        L.gsr_mesh_vis_emit.restype = C.c_int32
+        L.gsr_mesh_vis_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]
         L.gsr_profile_reset.restype = None

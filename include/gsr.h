@@ -34,11 +34,12 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 9   /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
+#define GSR_ABI_VERSION 10  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
                                 6: gsr_surface_maps_forward / _backward;
                                 7: TSDF fusion and marching cubes (GsrTsdfVolume, gsr_tsdf_*, gsr_mcubes_*);
                                 8: mesh post-processing (gsr_mesh_*) and gsr_depth_aabb;
-                                9: mesh culling by view masks (gsr_mask_dilate_*, gsr_mesh_cull_*) */
+                                9: mesh culling by view masks (gsr_mask_dilate_*, gsr_mesh_cull_*);
+                                10: mesh depth rendering and culling by visibility (gsr_mesh_depth_*, gsr_mesh_vis_*) */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -578,6 +579,92 @@ int32_t gsr_mesh_cull_count(const float* verts, const int32_t* tris, int64_t n_t
 int32_t gsr_mesh_cull_emit(const float* verts, const float* colors, const int32_t* tris, int64_t n_tris, int64_t n_verts,
                            const float* scale_offset_host, void* ws, size_t ws_bytes, float* verts_out, float* colors_out,
                            int32_t* tris_out, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- mesh evaluation: culling by visibility
+ * The reference's Tanks-and-Temples culling (scripts/eval_tnt/cull_mesh.py: pyrender's depth image of the mesh itself from
+ * every camera of the trajectory, point_masks at lines 126-176, trimesh's update_faces / remove_unreferenced_vertices) as
+ * kernels (mesh_vis.hip).  Inputs: a mesh (f32 vertices [V,3], optional f32 colours [V,3], int32 triangles [F,3]) and n views
+ * that share one pinhole fx, fy, cx, cy and an image size H x W.  The rules, each in this one place:
+ *   VIS_CAMERA   a view is an OpenCV world-to-camera matrix (x right, y down, z forward), row-major f32 [3,4], formed on the
+ *                host in float64 as inverse(camera-to-world) and rounded once (gaussmart_amd/mesh_visibility.py: w2c_from_c2w).
+ *                Camera-space position in fp32, fmaf in mc_vote's order:
+ *                  p.k = fmaf(M[k][2], z, fmaf(M[k][1], y, fmaf(M[k][0], x, M[k][3])))      k = x, y, z
+ *   VIS_RAY      pixel (i, j) (column, row) asks the ray d = ((i + 0.5 - cx) / fx, (j + 0.5 - cy) / fy, 1).  RECALLED from
+ *                pyrender's IntrinsicsCamera projection matrix and OpenGL's sampling at pixel centres; pyrender is not
+ *                available to read here (like Open3D and scikit-image in the blocks above).  The half pixel is deliberate:
+ *                the reference renders at pixel centres and then samples the image as if pixel i sat at u = i (VIS_SAMPLE).
+ *                Both are kept.
+ *   VIS_COVER    with camera-space vertices p0, p1, p2 and b0 = (p1 x p2).d, b1 = (p2 x p0).d, b2 = (p0 x p1).d the ray hits
+ *                the triangle when the three are all >= 0 or all <= 0 and not all zero: both faces are drawn (the reference's
+ *                SKIP_CULL_FACES).  There is no clipping in screen space: a triangle that crosses the camera plane is handled
+ *                by this homogeneous form and by VIS_RANGE.  The cross product of an edge is a x b = (ay bz - az by, ...) with
+ *                each product and each difference rounded on its own (so a x a = 0 and a x b = -(b x a) exactly), formed from
+ *                the endpoint with the smaller vertex index to the other and negated when that reverses the edge; the dot
+ *                product is fmaf(c.x, d.x, fmaf(c.y, d.y, c.z)).  Two triangles that share an edge therefore see exactly
+ *                opposite values there: a closed mesh has no cracks.  A triangle with a non-finite camera-space coordinate,
+ *                or with an index outside [0, V), draws nothing.  GUARD: when all three vertices have p.z >= near, only pixels
+ *                with umin - 1 <= i + 0.5 <= umax + 1 (u = fmaf(fx, p.x / p.z, cx) over the three vertices; rows likewise)
+ *                are asked.  In exact arithmetic every hit lies inside [umin, umax]; in fp32 the edge functions of a triangle
+ *                whose edges are shorter than about |p| fx 2^-23 are rounding noise farther out than one pixel, and such hits
+ *                are not wanted.  A triangle with a vertex nearer than `near` (but not all three) is asked at every pixel.
+ *   VIS_DEPTH    n = (p1 - p0) x (p2 - p0) (the same cross product), z = (n.p0) / (n.d) with n.p0 = fmaf(n.x, p0.x,
+ *                fmaf(n.y, p0.y, n.z p0.z)) and n.d as the dot product above: the plane form.  (The determinant form
+ *                det / (b0 + b1 + b2) loses 3e-4 relative on sub-pixel triangles in fp32, the plane form 2e-6.)  n.d == 0: no
+ *                hit.
+ *   VIS_RANGE    a hit counts when near <= z <= far (0.01 and 20 in the reference); this rejects a non-finite z as well.  A
+ *                pixel's depth is the smallest such z over all triangles, 0.0 when there is none.  DEVIATION: OpenGL's
+ *                depth buffer quantises z (24 bits of a non-linear function of it) and pyrender converts back; that is not
+ *                reproduced, the image holds the fp32 z itself.
+ *   VIS_PROJECT  (the vote; p by VIS_CAMERA)  z = p.z + 1e-8f,  u = fmaf(fx, p.x, cx p.z) / z,  v = fmaf(fy, p.y, cy p.z) / z
+ *                (the product cx p.z rounded on its own; the reference's K @ p, then the division),
+ *                in_frustum = 0 <= u <= W - 1 && 0 <= v <= H - 1 && z > 0 (false for NaN).
+ *   VIS_SAMPLE   ds is the bilinear sample of the view's depth image at (u, v) with pixel i at u = i:
+ *                grid_sample(align_corners=True, padding_mode='border').  x0 = floor(u), y0 = floor(v),
+ *                  ds = I[y0][x0] (x0 + 1 - u)(y0 + 1 - v) + I[y0][x0+1] (u - x0)(y0 + 1 - v)
+ *                     + I[y0+1][x0] (x0 + 1 - u)(v - y0) + I[y0+1][x0+1] (u - x0)(v - y0)
+ *                each weight one rounded product, the taps added in this order with fmaf; a tap outside the image (only
+ *                possible at u = W - 1 or v = H - 1, where its weight is 0) is left out.  A no-hit 0 blends with hit depths
+ *                like any other value, as in the reference.  Only in_frustum vertices are sampled, so the border clamp
+ *                never acts.
+ *   VIS_VOTE     a view sees a vertex when in_frustum && (ds > 0 ? z < ds + eps : true), eps = 0.005 in the reference.  A
+ *                vertex is kept when at least min_views views see it (20 in the reference).
+ *   VIS_COMPACT  a triangle stays when its three vertices are kept (degenerate ones too); ONLY vertices that a staying
+ *                triangle uses are emitted, in order (trimesh's remove_unreferenced_vertices: the "used vertices" rule of the
+ *                cluster filter, not CULL_COMPACT), triangles remapped with their order preserved.
+ *   gsr_mesh_depth_render : depth_out: device f32 [n_views,H,W] by VIS_CAMERA ... VIS_RANGE.  w2c_host: host f32 [n_views,12],
+ *                          uploaded into ws (gsr_mesh_depth_workspace_bytes(n_tris, n_views): 4 bytes per (triangle, view) for
+ *                          the work list of the pairs whose pixel box exceeds 8 x 8).  Depths are stored with atomicMin on
+ *                          the bit pattern of the positive float, so the images are the same bits on every run, for every
+ *                          order of the triangles and every split of the views over calls.  near must be > 0 and below a
+ *                          finite far.  n_tris * n_views must stay below 2^32 (GSR_E_UNSUPPORTED: pass fewer views).  No
+ *                          synchronisation.
+ *   gsr_mesh_vis_count    : VIS_PROJECT ... VIS_VOTE for n_views depth images (device f32 [n_views,H,W]) and their matrices
+ *                          (host f32 [n_views,12]; they travel as kernel arguments, 64 views a launch); intrinsics: host f32
+ *                          (fx, fy, cx, cy).  counts_inout: device int32 [n_verts], IN / OUT: the caller zeroes it before the
+ *                          first chunk of views and every call adds the views that see the vertex, in index order, and stops
+ *                          at min_views: the count is CLAMPED at min_views (a vertex that has reached it is not looked at
+ *                          again).  No synchronisation.
+ *   gsr_mesh_vis_compact_count / gsr_mesh_vis_emit : VIS_COMPACT from the counts, as gsr_mesh_cull_count / _emit: marks, two
+ *                          scans and ONE stream synchronisation that reads the two totals; vertex_keep (device uint8
+ *                          [n_verts], may be NULL) receives count >= min_views.  ws: gsr_mesh_vis_workspace_bytes(n_tris,
+ *                          n_verts), the same for both calls, nothing else enqueued on it in between.  colors NULL: colors_out
+ *                          is not written.  n_tris == 0: both totals are 0 and nothing is read back.
+ * Negative counts, H or W < 1, near <= 0, near >= far, a null pointer with a non-zero count or a workspace that is too small:
+ * GSR_E_INVALID before anything is launched, the message names the argument. */
+size_t gsr_mesh_depth_workspace_bytes(int64_t n_tris, int32_t n_views);
+int32_t gsr_mesh_depth_render(const float* verts, const int32_t* tris, int64_t n_tris, int64_t n_verts, const float* w2c_host,
+                              int32_t n_views, int32_t H, int32_t W, float fx, float fy, float cx, float cy, float near,
+                              float far, float* depth_out, void* ws, size_t ws_bytes, gsr_stream_t stream);
+int32_t gsr_mesh_vis_count(const float* verts, int64_t n_verts, const float* depths, int32_t n_views, int32_t H, int32_t W,
+                           const float* w2c_host, const float* intrinsics, float eps, int32_t min_views, int32_t* counts_inout,
+                           gsr_stream_t stream);
+size_t gsr_mesh_vis_workspace_bytes(int64_t n_tris, int64_t n_verts);
+int32_t gsr_mesh_vis_compact_count(const int32_t* tris, int64_t n_tris, int64_t n_verts, const int32_t* counts,
+                                   int32_t min_views, void* ws, size_t ws_bytes, uint8_t* vertex_keep, int64_t* n_verts_out,
+                                   int64_t* n_tris_out, gsr_stream_t stream);
+int32_t gsr_mesh_vis_emit(const float* verts, const float* colors, const int32_t* tris, int64_t n_tris, int64_t n_verts,
+                          void* ws, size_t ws_bytes, float* verts_out, float* colors_out, int32_t* tris_out,
+                          gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only

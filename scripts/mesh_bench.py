@@ -11,8 +11,14 @@ tests/mesh_cull_ref.py); a second JSON
 line with the times goes to --cull_out (default profiles/r07_mesh_cull_bench.json).  cull_device_ms starts from masks on
 the device, cull_host_ms from masks in host memory; the comparison the script asserts adds mask_upload_ms to the device side.
 
+With --vis the post-processed mesh is culled by visibility from the same cameras (gaussmart_amd.mesh_visibility: the
+Tanks-and-Temples step): wall times of the depth rendering, the vote and the compaction, with the bytes the small-box rasterizer
+has to move next to them; the JSON line goes to --vis_out (default profiles/r08_mesh_vis_bench.json).  There is no host side to
+this comparison: the numpy path is far too slow at this size.
+
     python scripts/mesh_bench.py [--surfels 300000] [--views 49] [--width 1600] [--height 1200]
     python scripts/mesh_bench.py --cull
+    python scripts/mesh_bench.py --vis
 """
 import argparse
 import contextlib
@@ -52,6 +58,10 @@ def main():
     ap.add_argument("--cull_radius", type=int, default=24)
     ap.add_argument("--cull_out", type=str, default=os.path.join(ROOT, "profiles", "r07_mesh_cull_bench.json"),
                     help="the culling JSON line is written to this file as well")
+    ap.add_argument("--vis", action="store_true", help="also time the culling by visibility of the post-processed mesh")
+    ap.add_argument("--vis_min_views", type=int, default=12,
+                    help="views that must see a vertex (a camera at distance 2.5 sees 30 %% of the unit sphere: about 14 of 49)")
+    ap.add_argument("--vis_out", type=str, default=os.path.join(ROOT, "profiles", "r08_mesh_vis_bench.json"))
     args = ap.parse_args()
     from gaussmart_amd.camera import look_at_camera
     from gaussmart_amd.gaussian_model import GaussianModel
@@ -130,6 +140,54 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(args.cull_out)), exist_ok=True)
             with open(args.cull_out, "w") as f:
                 f.write(json.dumps(cull) + "\n")
+
+
+    if args.vis:
+        vis = vis_bench(args, cams, dpost, dev)
+        print(json.dumps(vis))
+        if args.vis_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.vis_out)), exist_ok=True)
+            with open(args.vis_out, "w") as f:
+                f.write(json.dumps(vis) + "\n")
+
+
+def vis_bench(args, cams, dpost, dev):
+    from gaussmart_amd.mesh import camera_intrinsics
+    from gaussmart_amd.mesh_visibility import compact_by_counts, render_mesh_depth, visibility_counts, w2c_from_c2w
+    sync = torch.cuda.synchronize
+    c2w = np.stack([np.linalg.inv(c.world_view_transform.T.cpu().numpy().astype(np.float64)) for c in cams])
+    w2c = w2c_from_c2w(c2w, opengl=False)
+    intr = camera_intrinsics(cams[0])
+    H, W, n, mv = args.height, args.width, len(cams), args.vis_min_views
+    F, V = len(dpost.triangles), len(dpost.vertices)
+    runs = []
+    for rep in range(max(args.repeats, 3)):
+        sync(); t0 = time.perf_counter()
+        depths = render_mesh_depth(dpost, w2c, H, W, *intr)
+        sync(); t1 = time.perf_counter()
+        counts = visibility_counts(dpost.vertices, w2c, depths, *intr, min_views=mv)
+        sync(); t2 = time.perf_counter()
+        culled, keep = compact_by_counts(dpost, counts, mv, return_keep=True)
+        sync(); t3 = time.perf_counter()
+        runs.append((1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (t3 - t2)))
+        if rep == 0:
+            first = depths.clone()
+        else:
+            assert torch.equal(first.view(torch.int32), depths.view(torch.int32)), "depth images differ between two runs"
+    kept = int(keep.sum())
+    assert 0 < kept < V, f"{kept} of {V} vertices kept: not a culling workload"
+    hit = float((depths > 0).float().mean())
+    best = [min(r[k] for r in runs[1:]) for k in range(3)]
+    # what mv_raster_small has to move: every (triangle, view) pair reads its 12-byte index row; the vertex rows (12 bytes) are
+    # gathered three per pair, from HBM at least once per call and at most once per view; every hit pixel is at least one
+    # 4-byte atomic.  The image itself is written by the fill before and read and written by the resolve pass after.
+    return {"views": n, "width": W, "height": H, "vertices": V, "triangles": F, "pairs": F * n, "min_views": mv,
+            "kept_vertices": kept, "culled_vertices": len(culled.vertices), "culled_triangles": len(culled.triangles),
+            "hit_pixel_share": hit, "depth_render_ms": best[0], "vote_ms": best[1], "compact_ms": best[2],
+            "first_run_ms": list(runs[0]), "all_runs_ms": [list(r) for r in runs],
+            "raster_small_index_bytes": 12 * F * n, "raster_small_vertex_bytes_once": 12 * V,
+            "raster_small_vertex_bytes_per_view": 12 * V * n, "raster_small_gathered_bytes": 36 * F * n,
+            "hit_pixel_atomic_bytes_min": int(4 * hit * n * H * W), "image_bytes": 4 * n * H * W}
 
 
 def cull_views(cams, width, height):
