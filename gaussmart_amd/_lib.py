@@ -16,7 +16,7 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSR_LIB_PATH: developer aid for same-box A/B runs of two builds of the library (scripts/ab_builds.sh)
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "lib", "libgsr_hip.so")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_SCRATCH, GSR_BUF_SCRATCH2 = range(5)
 GSR_BUF_SYNC_SH = 100     # not a buffer: "the SH colour pass is about to be enqueued" (GSR_FLAG_DEFER_COLOR)
@@ -260,6 +260,23 @@ def lib():
         L.gsr_mesh_vis_emit.restype = C.c_int32
         L.gsr_mesh_vis_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        vp, i64, f64, sz = C.c_void_p, C.c_int64, C.c_double, C.c_size_t
+        for name, res, args in (
+                ("gsr_mesh_sample_workspace_bytes", sz, [i64]),
+                ("gsr_mesh_sample_count", C.c_int32, [vp, vp, i64, i64, f64, vp, sz, C.POINTER(i64), vp]),
+                ("gsr_mesh_sample_emit", C.c_int32, [vp, vp, i64, i64, f64, vp, sz, vp, vp]),
+                ("gsr_points_gather", C.c_int32, [vp, i64, vp, i64, vp, vp]),
+                ("gsr_points_search_workspace_bytes", sz, [i64, i64]),
+                ("gsr_points_downsample", C.c_int32, [vp, i64, f64, vp, sz, vp, C.POINTER(C.c_int32), vp]),
+                ("gsr_points_nearest", C.c_int32, [vp, i64, vp, i64, f64, vp, sz, vp, vp, vp]),
+                ("gsr_points_obs_workspace_bytes", sz, [i64]),
+                ("gsr_points_obs_filter_count", C.c_int32, [vp, i64, vp, vp, vp, f64, f64, vp, sz, vp, vp, C.POINTER(i64),
+                                                            C.POINTER(i64), vp]),
+                ("gsr_points_obs_filter_emit", C.c_int32, [vp, i64, vp, sz, vp, vp, vp]),
+                ("gsr_points_plane_filter", C.c_int32, [vp, i64, vp, vp, vp]),
+                ("gsr_dist_mean_workspace_bytes", sz, [i64]),
+                ("gsr_dist_mean", C.c_int32, [vp, i64, vp, sz, vp, vp, vp])):
+            getattr(L, name).restype, getattr(L, name).argtypes = res, args
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]
         L.gsr_profile_reset.restype = None

@@ -34,12 +34,13 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 10  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
+#define GSR_ABI_VERSION 11  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
                                 6: gsr_surface_maps_forward / _backward;
                                 7: TSDF fusion and marching cubes (GsrTsdfVolume, gsr_tsdf_*, gsr_mcubes_*);
                                 8: mesh post-processing (gsr_mesh_*) and gsr_depth_aabb;
                                 9: mesh culling by view masks (gsr_mask_dilate_*, gsr_mesh_cull_*);
-                                10: mesh depth rendering and culling by visibility (gsr_mesh_depth_*, gsr_mesh_vis_*) */
+                                10: mesh depth rendering and culling by visibility (gsr_mesh_depth_*, gsr_mesh_vis_*);
+                                11: DTU mesh evaluation (gsr_mesh_sample_*, gsr_points_*, gsr_dist_mean) */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -665,6 +666,89 @@ int32_t gsr_mesh_vis_compact_count(const int32_t* tris, int64_t n_tris, int64_t 
 int32_t gsr_mesh_vis_emit(const float* verts, const float* colors, const int32_t* tris, int64_t n_tris, int64_t n_verts,
                           void* ws, size_t ws_bytes, float* verts_out, float* colors_out, int32_t* tris_out,
                           gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- mesh evaluation: DTU Chamfer distance
+ * The reference's scripts/eval_dtu/eval.py (sampling the mesh, shuffle, greedy down-sampling, ObsMask and ground-plane
+ * filters, the two nearest-neighbour searches and their means) as kernels (mesh_eval.hip).  All arithmetic is fp64 on the
+ * device unless stated, and mesh_eval.o is compiled with -ffp-contract=off, so every expression below rounds operation by
+ * operation as numpy's does.  Point clouds are f32 [n,3]; counts are int32-indexable (more: GSR_E_UNSUPPORTED).  The rules,
+ * each in this one place:
+ *   EVAL_SAMPLE     (eval.py:50-71)  vertices f32, widened to fp64.  Per triangle v1 = p1 - p0, v2 = p2 - p0,
+ *                   l1 = sqrt((v1x^2 + v1y^2) + v1z^2), l2 likewise, area2 = |v1 x v2| with the same order of sums and
+ *                   v1 x v2 = (v1y v2z - v1z v2y, v1z v2x - v1x v2z, v1x v2y - v1y v2x).  A triangle with `area2 > 0` false
+ *                   or with an index outside [0, V) gives nothing.  thr = thresh sqrt(l1 l2 / area2), n1 = floor(l1 / thr),
+ *                   n2 = floor(l2 / thr); n1 = 0 or n2 = 0 (or NaN): no sample.  For i = 0 ... n1 (outer), j = 0 ... n2 (inner):
+ *                   a = (i + 0.5) / n1, b = (j + 0.5) / n2, the sample is kept iff a + b < 1 and is q = (v1 a + v2 b) + p0.
+ *                   (For n1, n2 < 80 this fp64 test equals the integer test (2i+1) n2 + (2j+1) n1 < 2 n1 n2; the fp64 form
+ *                   is the rule.)  The output cloud is the V vertices, then the samples in triangle order.
+ *                   CAP: a triangle with n1 n2 > 2^24 is refused (GSR_E_UNSUPPORTED, the message names downsample_density).
+ *   EVAL_POINT_F32  a sample is rounded once, fp64 -> f32, when it is stored.  DEVIATION: the reference keeps fp64 points;
+ *                   DTU coordinates are millimetres up to about 500, an f32 ulp there is 3e-5 mm against a sampling density
+ *                   of 0.2 mm.
+ *   EVAL_ORDER      the reference shuffles with an unseeded generator; here the caller passes the permutation (device int32
+ *                   [n]) and gsr_points_gather applies it: out[k] = points[perm[k]].
+ *   EVAL_DIST       for f32 points a, b: dx = (double)a.x - (double)b.x (dy, dz likewise), d2 = (dx dx + dy dy) + dz dz,
+ *                   d = sqrt(d2).  Used for every decision and every reported distance.  Pruning bounds are the same
+ *                   expression on the fp64 gaps between the query and a box's f32 faces: every operation is monotone, so a
+ *                   bound never exceeds the d2 of a point inside the box, and boxes are skipped only when bound > limit.
+ *   EVAL_DOWNSAMPLE (eval.py:86-94)  in the order given, point i is kept iff no kept j < i has d2 <= thresh^2 (thresh^2 in
+ *                   fp64; inclusive, as radius_neighbors is): the lexicographically first maximal independent set.  Built in
+ *                   rounds over three states: an undecided point becomes removed when some lower neighbour is kept, kept when
+ *                   all lower neighbours are removed.  A state is written once, so asynchronous in-place updates give the
+ *                   sequential result on every run.  The host launches 8 rounds, reads one word back (bit r: somebody was
+ *                   undecided after round r) and goes on while the last bit is set; at most n rounds (a sorted chain).
+ *   EVAL_NN         (eval.py:119-134)  per query the nearest point of the other cloud by EVAL_DIST: f64 distance and int32
+ *                   index, the smallest index among exactly equal d2.  Finite max_dist: a query whose nearest point has
+ *                   d >= max_dist gives +inf and -1 (the search prunes at max_dist^2 (1 + 2^-50); the decision is taken on
+ *                   d itself).  max_dist = +inf gives the true nearest point.  An empty cloud gives +inf and -1.  Exact for
+ *                   any cloud: the searched cloud is sorted by 30-bit Morton code, bounded in leaves of 64 points, nodes of
+ *                   64 leaves and tops of 64 nodes; queries run in their own Morton order (codes clamped into the cloud's
+ *                   bounds), are seeded from the leaf at the lower bound of their code, and open only boxes whose bound is
+ *                   not above the best d2 so far.  Non-finite coordinates are not supported (no fault, no promise).
+ *   EVAL_OBSMASK    (eval.py:98-110)  BB widened from f32 [2,3]; Res and patch fp64.  inbound = all(p >= BB0 - patch) &&
+ *                   all(p < BB1 + patch 2).  g = rint((p - BB0) / Res), half to even; in_obs = inbound && 0 <= g < shape on
+ *                   the three axes && ObsMask[gx][gy][gz] != 0 (uint8, C order of that index).  DEVIATION: the reference
+ *                   forms BB0 - patch in f32; here in fp64.  Two compacted clouds, order kept: data_in (inbound), data_in_obs.
+ *   EVAL_PLANE      (eval.py:126-130)  a ground-truth point is used when ((P0 x + P1 y) + P2 z) + P3 > 0.
+ *   EVAL_MEAN       the mean of the finite entries of a distance array: thread t of workgroup b (of min(1024, ceil(n / 256)))
+ *                   adds its elements in index order, a fixed tree adds the 256 sums, one workgroup adds the partials the same
+ *                   way: the same bits on every run.  No finite entry: NaN, as numpy's mean of an empty array.
+ *   gsr_mesh_sample_count / _emit : EVAL_SAMPLE.  _count: per-triangle counts, their scan and ONE stream synchronisation that
+ *                   reads the total; *n_points_out = n_verts + samples.  _emit: points_out device f32 [n_points,3]; same ws
+ *                   (gsr_mesh_sample_workspace_bytes(n_tris)), nothing else enqueued on it in between, same thresh.
+ *   gsr_points_downsample : EVAL_DOWNSAMPLE; keep_out device uint8 [n]; *rounds_out (host, may be NULL) the rounds it took.
+ *                   ws: gsr_points_search_workspace_bytes(n, 0).  Synchronises once per 8 rounds.
+ *   gsr_points_nearest : EVAL_NN; dist_out device f64 [n_query], idx_out device int32 [n_query].
+ *                   ws: gsr_points_search_workspace_bytes(n_cloud, n_query).  No synchronisation.
+ *   gsr_points_obs_filter_count / _emit : EVAL_OBSMASK as gsr_mesh_vis_compact_count / _emit: flags, two scans, ONE
+ *                   synchronisation for the two totals; inbound_out / in_obs_out (device uint8 [n], may be NULL) receive the
+ *                   flags.  shape_host: host int32 [3]; bb_host: host f32 [6].  _emit: either output may be NULL.
+ *   gsr_points_plane_filter : EVAL_PLANE; plane_host: host f64 [4]; keep_out device uint8 [n] (compact with gsr_compact_*).
+ *   gsr_dist_mean  : EVAL_MEAN; mean_out device f64 [1], count_out device int64 [1] (may be NULL).  No synchronisation.
+ * Negative counts, thresh <= 0, max_dist <= 0, a null pointer with a non-zero count or a workspace that is too small:
+ * GSR_E_INVALID before anything is launched, the message names the argument. */
+size_t gsr_mesh_sample_workspace_bytes(int64_t n_tris);
+int32_t gsr_mesh_sample_count(const float* verts, const int32_t* tris, int64_t n_tris, int64_t n_verts, double thresh, void* ws,
+                              size_t ws_bytes, int64_t* n_points_out, gsr_stream_t stream);
+int32_t gsr_mesh_sample_emit(const float* verts, const int32_t* tris, int64_t n_tris, int64_t n_verts, double thresh, void* ws,
+                             size_t ws_bytes, float* points_out, gsr_stream_t stream);
+int32_t gsr_points_gather(const float* points, int64_t n_src, const int32_t* perm, int64_t n, float* out, gsr_stream_t stream);
+size_t gsr_points_search_workspace_bytes(int64_t n_cloud, int64_t n_query);
+int32_t gsr_points_downsample(const float* points, int64_t n, double thresh, void* ws, size_t ws_bytes, uint8_t* keep_out,
+                              int32_t* rounds_out, gsr_stream_t stream);
+int32_t gsr_points_nearest(const float* query, int64_t n_query, const float* cloud, int64_t n_cloud, double max_dist, void* ws,
+                           size_t ws_bytes, double* dist_out, int32_t* idx_out, gsr_stream_t stream);
+size_t gsr_points_obs_workspace_bytes(int64_t n);
+int32_t gsr_points_obs_filter_count(const float* points, int64_t n, const uint8_t* obs_mask, const int32_t* shape_host,
+                                    const float* bb_host, double res, double patch, void* ws, size_t ws_bytes,
+                                    uint8_t* inbound_out, uint8_t* in_obs_out, int64_t* n_in_out, int64_t* n_in_obs_out,
+                                    gsr_stream_t stream);
+int32_t gsr_points_obs_filter_emit(const float* points, int64_t n, void* ws, size_t ws_bytes, float* data_in_out,
+                                   float* data_in_obs_out, gsr_stream_t stream);
+int32_t gsr_points_plane_filter(const float* points, int64_t n, const double* plane_host, uint8_t* keep_out, gsr_stream_t stream);
+size_t gsr_dist_mean_workspace_bytes(int64_t n);
+int32_t gsr_dist_mean(const double* dist, int64_t n, void* ws, size_t ws_bytes, double* mean_out, int64_t* count_out,
+                      gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only

@@ -19,6 +19,13 @@ this comparison: the numpy path is far too slow at this size.
     python scripts/mesh_bench.py [--surfels 300000] [--views 49] [--width 1600] [--height 1200]
     python scripts/mesh_bench.py --cull
     python scripts/mesh_bench.py --vis
+    python scripts/mesh_bench.py --eval
+
+With --eval the post-processed mesh is scored like a DTU scan (gaussmart_amd.mesh_eval: sampling, shuffle, greedy down-sampling,
+ObsMask and plane filters, the two nearest-neighbour searches, the means) against a ground-truth cloud sampled from the analytic
+sphere, on the device and on the host path (numpy + cKDTree) in the same run; masks, indices and distances must be equal and the
+means within the summation bound.  Wall times per stage of both paths go to --eval_out (default
+profiles/r09_mesh_eval_bench.json).
 """
 import argparse
 import contextlib
@@ -62,6 +69,10 @@ def main():
     ap.add_argument("--vis_min_views", type=int, default=12,
                     help="views that must see a vertex (a camera at distance 2.5 sees 30 %% of the unit sphere: about 14 of 49)")
     ap.add_argument("--vis_out", type=str, default=os.path.join(ROOT, "profiles", "r08_mesh_vis_bench.json"))
+    ap.add_argument("--eval", action="store_true", help="also score the post-processed mesh against an analytic ground truth")
+    ap.add_argument("--eval_density", type=float, default=0.002, help="downsample_density in scene units (half the voxel size)")
+    ap.add_argument("--eval_gt_points", type=int, default=1_000_000)
+    ap.add_argument("--eval_out", type=str, default=os.path.join(ROOT, "profiles", "r09_mesh_eval_bench.json"))
     args = ap.parse_args()
     from gaussmart_amd.camera import look_at_camera
     from gaussmart_amd.gaussian_model import GaussianModel
@@ -149,6 +160,52 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(args.vis_out)), exist_ok=True)
             with open(args.vis_out, "w") as f:
                 f.write(json.dumps(vis) + "\n")
+    if args.eval:
+        ev = eval_bench(args, dpost, dev)
+        print(json.dumps(ev))
+        if args.eval_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.eval_out)), exist_ok=True)
+            with open(args.eval_out, "w") as f:
+                f.write(json.dumps(ev) + "\n")
+
+
+def eval_bench(args, dpost, dev):
+    from gaussmart_amd.mesh_eval import evaluate_dtu_mesh, evaluate_dtu_mesh_host
+    rng = np.random.default_rng(0)
+    n_gt, thresh = args.eval_gt_points, args.eval_density
+    gt = (fib(n_gt) * (1.0 + rng.normal(scale=0.5 * thresh, size=(n_gt, 1)))).astype(np.float32)
+    obs = np.ones((45, 45, 45), np.uint8)
+    obs[:22, :22, :22] = 0                                   # one octant of the volume was not observed
+    kw = dict(stl_points=gt, obs_mask=obs, bb=np.array([[-1.1] * 3, [1.1] * 3], np.float32), res=0.05,
+              plane=np.array([0.0, 0.0, 1.0, 0.0]), downsample_density=thresh, patch_size=0.1, max_dist=100 * thresh)
+    dev_runs = []
+    for rep in range(max(args.repeats, 2)):
+        td = {}
+        t0 = time.perf_counter()
+        d = evaluate_dtu_mesh(dpost, timings=td, **kw)
+        td["total_ms"] = 1e3 * (time.perf_counter() - t0)
+        dev_runs.append(td)
+        if rep:
+            assert (d["mean_d2s"], d["mean_s2d"]) == first, "the means differ between two runs"
+        first = (d["mean_d2s"], d["mean_s2d"])
+    th = {}
+    t0 = time.perf_counter()
+    h = evaluate_dtu_mesh_host(dpost.cpu(), timings=th, **kw)
+    th["total_ms"] = 1e3 * (time.perf_counter() - t0)
+    for key in ("keep", "inbound", "in_obs", "above", "idx_d2s", "idx_s2d", "dist_d2s", "dist_s2d"):
+        assert np.array_equal(d[key].cpu().numpy(), h[key]), f"host and device path differ in {key}"
+    for key, dk in (("mean_d2s", "dist_d2s"), ("mean_s2d", "dist_s2d")):
+        n = int(np.isfinite(h[dk]).sum())
+        assert abs(d[key] - h[key]) <= n * 2.0 ** -53 * h[key], f"{key}: {d[key]!r} against {h[key]!r}"
+    best = {k: min(r[k] for r in dev_runs[1:]) for k in dev_runs[0]}
+    stages = [k for k in best if k != "total_ms"]
+    return {"vertices": len(dpost.vertices), "triangles": len(dpost.triangles), "density": thresh, "gt_points": n_gt,
+            "sampled_points": len(h["keep"]), "kept_points": int(h["keep"].sum()), "rounds": d["rounds"],
+            "inbound": int(h["inbound"].sum()), "in_obs": int(h["in_obs"].sum()), "gt_above": int(h["above"].sum()),
+            "mean_d2s": d["mean_d2s"], "mean_s2d": d["mean_s2d"], "overall": d["overall"],
+            "host_mean_d2s": h["mean_d2s"], "host_mean_s2d": h["mean_s2d"],
+            "device_ms": best, "device_first_run_ms": dev_runs[0], "host_ms": th,
+            "slowest_device_stage": max(stages, key=lambda k: best[k]), "slowest_host_stage": max(stages, key=lambda k: th[k])}
 
 
 def vis_bench(args, cams, dpost, dev):
