@@ -16,7 +16,7 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSR_LIB_PATH: developer aid for same-box A/B runs of two builds of the library (scripts/ab_builds.sh)
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "lib", "libgsr_hip.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_SCRATCH, GSR_BUF_SCRATCH2 = range(5)
 GSR_BUF_SYNC_SH = 100     # not a buffer: "the SH colour pass is about to be enqueued" (GSR_FLAG_DEFER_COLOR)
@@ -275,7 +275,17 @@ def lib():
                 ("gsr_points_obs_filter_emit", C.c_int32, [vp, i64, vp, sz, vp, vp, vp]),
                 ("gsr_points_plane_filter", C.c_int32, [vp, i64, vp, vp, vp]),
                 ("gsr_dist_mean_workspace_bytes", sz, [i64]),
-                ("gsr_dist_mean", C.c_int32, [vp, i64, vp, sz, vp, vp, vp])):
+                ("gsr_dist_mean", C.c_int32, [vp, i64, vp, sz, vp, vp, vp]),
+                ("gsr_mesh_face_centres", C.c_int32, [vp, vp, i64, i64, vp, vp]),
+                ("gsr_points_transform", C.c_int32, [vp, i64, vp, vp, vp]),
+                ("gsr_points_crop_polygon", C.c_int32, [vp, i64, C.c_int32, f64, f64, vp, C.c_int32, vp, vp]),
+                ("gsr_points_voxel_workspace_bytes", sz, [i64]),
+                ("gsr_points_voxel_count", C.c_int32, [vp, i64, f64, vp, sz, C.POINTER(i64), vp]),
+                ("gsr_points_voxel_emit", C.c_int32, [vp, i64, f64, vp, sz, vp, vp, vp]),
+                ("gsr_icp_sums_workspace_bytes", sz, [i64]),
+                ("gsr_icp_sums", C.c_int32, [vp, i64, vp, i64, vp, vp, vp, vp, sz, vp, vp]),
+                ("gsr_dist_score_workspace_bytes", sz, [C.c_int32]),
+                ("gsr_dist_score", C.c_int32, [vp, i64, vp, C.c_int32, f64, vp, sz, vp, vp, vp])):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]

@@ -34,13 +34,15 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 11  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
+#define GSR_ABI_VERSION 12  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
                                 6: gsr_surface_maps_forward / _backward;
                                 7: TSDF fusion and marching cubes (GsrTsdfVolume, gsr_tsdf_*, gsr_mcubes_*);
                                 8: mesh post-processing (gsr_mesh_*) and gsr_depth_aabb;
                                 9: mesh culling by view masks (gsr_mask_dilate_*, gsr_mesh_cull_*);
                                 10: mesh depth rendering and culling by visibility (gsr_mesh_depth_*, gsr_mesh_vis_*);
-                                11: DTU mesh evaluation (gsr_mesh_sample_*, gsr_points_*, gsr_dist_mean) */
+                                11: DTU mesh evaluation (gsr_mesh_sample_*, gsr_points_*, gsr_dist_mean);
+                                12: Tanks-and-Temples mesh evaluation (gsr_mesh_face_centres, gsr_points_transform / _crop_polygon /
+                                    _voxel_*, gsr_icp_sums, gsr_dist_score) */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -749,6 +751,82 @@ int32_t gsr_points_plane_filter(const float* points, int64_t n, const double* pl
 size_t gsr_dist_mean_workspace_bytes(int64_t n);
 int32_t gsr_dist_mean(const double* dist, int64_t n, void* ws, size_t ws_bytes, double* mean_out, int64_t* count_out,
                       gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- mesh evaluation: Tanks-and-Temples F-score
+ * The reference's scripts/eval_tnt/run.py (the mesh as a cloud, crop, voxel-grid down-sampling, three ICP refinements, the
+ * precision / recall histograms and the F-score) without Open3D or trimesh: kernels in tnt_eval.hip around EVAL_NN's
+ * gsr_points_nearest.  Open3D cannot be run beside this code, so the rules below are the rules; they restate what Open3D
+ * 0.9 - 0.18 does where that is deterministic and name each deviation.  All arithmetic is fp64 on the device unless stated,
+ * tnt_eval.o is compiled with -ffp-contract=off, point clouds are f32 [n,3], counts are int32-indexable (more:
+ * GSR_E_UNSUPPORTED).  No floating-point atomic is used: every result has the same bits on every run.  The rules, each in
+ * this one place:
+ *   TNT_CLOUD       (run.py:94-108)  the evaluated cloud is the mesh's V vertices followed by its F face centres; a centre
+ *                   is ((p0 + p1) + p2) / 3 on the fp64-widened f32 vertices, rounded once to f32.  The caller checks the
+ *                   index range; the kernel gives a NaN row for an index outside [0, V), never a wild read.
+ *   TNT_TRANSFORM   x' = ((T00 x + T01 y) + T02 z) + T03, y' and z' likewise with rows 1 and 2 of the host fp64 4x4 row-major
+ *                   matrix T (passed by value); the last row must be (0, 0, 0, 1) (Open3D divides by w; a similarity never
+ *                   needs that).
+ *   TNT_POINT_F32   a transformed point, a face centre and a voxel's mean are rounded once, fp64 -> f32, when stored.
+ *                   DEVIATION: the reference keeps fp64 points; TnT coordinates are metres up to a few tens, an f32 ulp there
+ *                   is about 2e-6 m against the smallest tau of 3e-3 m.
+ *   TNT_CROP        (Open3D SelectionPolygonVolume::CropInPolygon)  orthogonal_axis a in {0: X, 1: Y, 2: Z}; (u, v) = (1, 2)
+ *                   for X, (0, 2) for Y, (0, 1) for Z.  A point p is kept iff min(axis_min, axis_max) <= p[a] <=
+ *                   max(axis_min, axis_max) and the number of nodes strictly < p.u over the polygon's edges (i, j = (i + 1)
+ *                   mod m) is odd.  An edge gives a node when (Pi.v < p.v && Pj.v >= p.v) || (Pj.v < p.v && Pi.v >= p.v); the
+ *                   node is Pi.u + (p.v - Pi.v) / (Pj.v - Pi.v) * (Pj.u - Pi.u), evaluated left to right.  The polygon is a
+ *                   device fp64 [m,3] array, 1 <= m <= 256 (more: GSR_E_UNSUPPORTED).
+ *   TNT_VOXEL       (Open3D VoxelDownSample)  lo = per-axis minimum of the cloud - 0.5 voxel; cell = floor((p - lo) / voxel)
+ *                   per axis; one output point per occupied cell: the sum of the cell's points in ascending input index,
+ *                   added sequentially, divided by their number.  Output order: ascending (ix, iy, iz).  DEVIATION: Open3D's
+ *                   order is its hash map's and unspecified.  A cell index >= 2^21 on an axis (or a non-finite coordinate) is
+ *                   refused: GSR_E_UNSUPPORTED, the message names voxel_size.  Built as: minimum, 63-bit keys ix << 42 |
+ *                   iy << 21 | iz, a stable sort of the key's two words from low to high, run heads, their scan; one thread
+ *                   per cell walks its run, which is what makes the order of the sum the rule (a cloud that falls into one
+ *                   cell is summed by one thread: slow, correct).
+ *   TNT_UNIFORM     (registration.py:124-128)  n > max_points (default 4e6): keep the indices 0, k, 2k, ... with
+ *                   k = int(round(n / max_points)), Python's round; applied with gsr_points_gather.
+ *   TNT_ICP_SUMS    correspondences are gsr_points_nearest(source, target, max_dist = threshold): by EVAL_NN source point i
+ *                   corresponds to target idx[i] when d < threshold.  Pass 1 over the pairs (i, idx[i] >= 0): count, sum s,
+ *                   sum t, sum d^2 (d = dist[i]).  The host forms the means sm, tm.  Pass 2: sum (t - tm)(s - sm)^T (row-major,
+ *                   rows t) and sum |s - sm|^2 = (dx dx + dy dy) + dz dz.  Both passes add in EVAL_MEAN's fixed order.
+ *   TNT_ICP_APPLY   DEVIATION for the sake of f32 points: every ICP iteration transforms the ORIGINAL source by the cumulative
+ *                   fp64 T (T <- U T on the host), one rounding per iteration, not a rounding of a rounding.
+ *   TNT_SCORE       (evaluation.py:173-215)  the int64 count of d < tau, and np.histogram's counts for explicit edges e_0 <=
+ *                   ... <= e_B: bin k holds e_k <= d < e_(k+1), the last bin also d == e_B; anything else (NaN, +inf) is in
+ *                   no bin.  A value's bin is found by a binary search against the edge values themselves (the caller forms
+ *                   them with numpy, so their bits are numpy's); int32 bins in LDS per workgroup, integer atomics to the
+ *                   global bins.  1 <= B <= 4096 (more: GSR_E_UNSUPPORTED).
+ *   gsr_mesh_face_centres : TNT_CLOUD's centres; centres_out device f32 [n_tris,3].
+ *   gsr_points_transform : TNT_TRANSFORM; transform_host: host f64 [16]; out device f32 [n,3] (may not alias points).
+ *   gsr_points_crop_polygon : TNT_CROP; polygon device f64 [n_polygon,3]; keep_out device uint8 [n] (compact with gsr_compact_*).
+ *   gsr_points_voxel_count / _emit : TNT_VOXEL as gsr_mesh_sample_count / _emit.  _count: keys, sort, heads, scan and ONE
+ *                   stream synchronisation that reads the number of cells.  _emit: points_out device f32 [n_cells,3],
+ *                   cell_of_point_out (device int32 [n], may be NULL) the output row of every input point; same ws
+ *                   (gsr_points_voxel_workspace_bytes(n)), nothing else enqueued on it in between.
+ *   gsr_icp_sums   : TNT_ICP_SUMS; dist / idx: gsr_points_nearest's outputs for `source`; means_host NULL: pass 1, out =
+ *                   (count, sum s.xyz, sum t.xyz, sum d^2, 0, 0); means_host = host f64 [6] (sm, tm): pass 2, out = (the 9
+ *                   sums row-major, sum |s - sm|^2).  out device f64 [10]; ws: gsr_icp_sums_workspace_bytes(n_source).  An
+ *                   idx outside [0, n_target) is no pair.  No synchronisation.
+ *   gsr_dist_score : TNT_SCORE; edges_host: host f64 [n_bins + 1], finite and not decreasing; count_out device int64 [1],
+ *                   hist_out device int64 [n_bins]; ws: gsr_dist_score_workspace_bytes(n_bins).  No synchronisation.
+ * Negative counts, voxel_size / tau <= 0, an axis outside 0..2, a null pointer with a non-zero count or a workspace that is
+ * too small: GSR_E_INVALID before anything is launched, the message names the argument. */
+int32_t gsr_mesh_face_centres(const float* verts, const int32_t* tris, int64_t n_tris, int64_t n_verts, float* centres_out,
+                              gsr_stream_t stream);
+int32_t gsr_points_transform(const float* points, int64_t n, const double* transform_host, float* out, gsr_stream_t stream);
+int32_t gsr_points_crop_polygon(const float* points, int64_t n, int32_t orthogonal_axis, double axis_min, double axis_max,
+                                const double* polygon, int32_t n_polygon, uint8_t* keep_out, gsr_stream_t stream);
+size_t gsr_points_voxel_workspace_bytes(int64_t n);
+int32_t gsr_points_voxel_count(const float* points, int64_t n, double voxel_size, void* ws, size_t ws_bytes, int64_t* n_cells_out,
+                               gsr_stream_t stream);
+int32_t gsr_points_voxel_emit(const float* points, int64_t n, double voxel_size, void* ws, size_t ws_bytes, float* points_out,
+                              int32_t* cell_of_point_out, gsr_stream_t stream);
+size_t gsr_icp_sums_workspace_bytes(int64_t n_source);
+int32_t gsr_icp_sums(const float* source, int64_t n_source, const float* target, int64_t n_target, const double* dist,
+                     const int32_t* idx, const double* means_host, void* ws, size_t ws_bytes, double* out, gsr_stream_t stream);
+size_t gsr_dist_score_workspace_bytes(int32_t n_bins);
+int32_t gsr_dist_score(const double* dist, int64_t n, const double* edges_host, int32_t n_bins, double tau, void* ws,
+                       size_t ws_bytes, int64_t* count_out, int64_t* hist_out, gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only

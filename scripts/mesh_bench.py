@@ -20,12 +20,19 @@ this comparison: the numpy path is far too slow at this size.
     python scripts/mesh_bench.py --cull
     python scripts/mesh_bench.py --vis
     python scripts/mesh_bench.py --eval
+    python scripts/mesh_bench.py --tnt
 
 With --eval the post-processed mesh is scored like a DTU scan (gaussmart_amd.mesh_eval: sampling, shuffle, greedy down-sampling,
 ObsMask and plane filters, the two nearest-neighbour searches, the means) against a ground-truth cloud sampled from the analytic
 sphere, on the device and on the host path (numpy + cKDTree) in the same run; masks, indices and distances must be equal and the
 means within the summation bound.  Wall times per stage of both paths go to --eval_out (default
 profiles/r09_mesh_eval_bench.json).
+
+With --tnt the post-processed mesh, moved by the inverse of a known similarity, is scored like a Tanks-and-Temples scene
+(gaussmart_amd.tnt_eval: the mesh as a cloud, crop, voxel grid, three ICP refinements, histograms and F-score) against the
+analytic sphere cloud, on the device and on the host path in the same run; ICP iteration counts, correspondence counts and
+fitness, precision, recall and the histograms must be equal.  Wall times per stage of both paths go to --tnt_out (default
+profiles/r10_tnt_eval_bench.json).
 """
 import argparse
 import contextlib
@@ -73,6 +80,10 @@ def main():
     ap.add_argument("--eval_density", type=float, default=0.002, help="downsample_density in scene units (half the voxel size)")
     ap.add_argument("--eval_gt_points", type=int, default=1_000_000)
     ap.add_argument("--eval_out", type=str, default=os.path.join(ROOT, "profiles", "r09_mesh_eval_bench.json"))
+    ap.add_argument("--tnt", action="store_true", help="also score the post-processed mesh like a Tanks-and-Temples scene")
+    ap.add_argument("--tnt_tau", type=float, default=0.004, help="distance threshold in scene units (the voxel size)")
+    ap.add_argument("--tnt_gt_points", type=int, default=1_000_000)
+    ap.add_argument("--tnt_out", type=str, default=os.path.join(ROOT, "profiles", "r10_tnt_eval_bench.json"))
     args = ap.parse_args()
     from gaussmart_amd.camera import look_at_camera
     from gaussmart_amd.gaussian_model import GaussianModel
@@ -167,6 +178,61 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(args.eval_out)), exist_ok=True)
             with open(args.eval_out, "w") as f:
                 f.write(json.dumps(ev) + "\n")
+    if args.tnt:
+        tn = tnt_bench(args, dpost, dev)
+        print(json.dumps(tn))
+        if args.tnt_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.tnt_out)), exist_ok=True)
+            with open(args.tnt_out, "w") as f:
+                f.write(json.dumps(tn) + "\n")
+
+
+def tnt_bench(args, dpost, dev):
+    from gaussmart_amd import tnt_eval as TE
+    from gaussmart_amd.mesh import DeviceTriangleMesh
+    from tnt_eval_ref import similarity
+    rng = np.random.default_rng(0)
+    n_gt, tau = args.tnt_gt_points, args.tnt_tau
+    gt = (fib(n_gt) * (1.0 + rng.normal(scale=0.25 * tau, size=(n_gt, 1)))).astype(np.float32)
+    S = similarity(1.01, [0.3, -0.5, 0.8], 2.0, [0.01, -0.02, 0.015])
+    init = similarity(1.0005, [0.6, 0.2, -0.4], 0.1, [0.5 * tau, -0.4 * tau, 0.3 * tau]) @ S
+    moved = DeviceTriangleMesh(TE.transform_points(dpost.vertices, np.linalg.inv(S)), dpost.triangles)
+    crop = {"orthogonal_axis": "Z", "axis_min": -0.7, "axis_max": 0.9,
+            "bounding_polygon": np.array([[-0.9, -0.8, 0.0], [0.85, -0.9, 0.0], [0.9, 0.8, 0.0], [0.1, 0.3, 0.0], [-0.8, 0.9, 0.0]])}
+    dev_runs = []
+    for rep in range(max(args.repeats, 2)):
+        td = {}
+        t0 = time.perf_counter()
+        d = TE.evaluate_tnt_mesh(moved, gt, crop, tau, init, device=dev, timings=td)
+        td["total_ms"] = 1e3 * (time.perf_counter() - t0)
+        dev_runs.append(td)
+        if rep:
+            assert np.array_equal(d["transformation"], first), "the transformation differs between two runs"
+        first = d["transformation"]
+    th = {}
+    t0 = time.perf_counter()
+    h = TE.evaluate_tnt_mesh_host(moved.cpu(), gt, crop, tau, init, timings=th)
+    th["total_ms"] = 1e3 * (time.perf_counter() - t0)
+    for k, (a, b) in enumerate(zip(d["registrations"], h["registrations"])):
+        assert a["iterations"] == b["iterations"], f"registration {k}: {a['iterations']} against {b['iterations']} iterations"
+        assert [c for c, _ in a["trace"]] == [c for c, _ in b["trace"]], f"registration {k}: correspondence counts differ"
+        assert a["fitness"] == b["fitness"], f"registration {k}: fitness differs"
+    for key in ("precision", "recall", "fscore"):
+        assert d[key] == h[key], f"{key}: {d[key]!r} against {h[key]!r}"
+    for key in ("hist_source", "hist_target"):
+        assert np.array_equal(d[key], h[key]), f"host and device path differ in {key}"
+    best = {k: min(r[k] for r in dev_runs[1:]) for k in dev_runs[0]}
+    stages = [k for k in best if k != "total_ms"]
+    regs = d["registrations"]
+    return {"vertices": len(dpost.vertices), "triangles": len(dpost.triangles), "tau": tau, "gt_points": n_gt,
+            "icp_points": [[r["n_source"], r["n_target"]] for r in regs], "icp_iterations": [r["iterations"] for r in regs],
+            "icp_fitness": [r["fitness"] for r in regs], "icp_rmse": [r["inlier_rmse"] for r in regs],
+            "scored_points": [len(d["cloud_source"]), len(d["cloud_target"])],
+            "precision": d["precision"], "recall": d["recall"], "fscore": d["fscore"],
+            "transformation_error": float(np.abs(d["transformation"] - S).max()),
+            "host_transformation_diff": float(np.abs(d["transformation"] - h["transformation"]).max()),
+            "device_ms": best, "device_first_run_ms": dev_runs[0], "host_ms": th,
+            "slowest_device_stage": max(stages, key=lambda k: best[k]), "slowest_host_stage": max(stages, key=lambda k: th[k])}
 
 
 def eval_bench(args, dpost, dev):
