@@ -16,7 +16,7 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSR_LIB_PATH: developer aid for same-box A/B runs of two builds of the library (scripts/ab_builds.sh)
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "lib", "libgsr_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_SCRATCH, GSR_BUF_SCRATCH2 = range(5)
 GSR_BUF_SYNC_SH = 100     # not a buffer: "the SH colour pass is about to be enqueued" (GSR_FLAG_DEFER_COLOR)
@@ -81,6 +81,13 @@ class GsrTsdfVolume(C.Structure):
                 ("block_lo", C.c_int32 * 3), ("block_hi", C.c_int32 * 3),
                 ("block_index", C.c_void_p), ("pool", C.c_void_p), ("pool_blocks", C.c_int64), ("n_alloc", C.c_int64),
                 ("n_views", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class GsrSegView(C.Structure):
+    """include/gsr.h: one view of the segment assignment (gaussmart_amd/segment_init.py)."""
+    _fields_ = [("kind", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("n_masks", C.c_int32),
+                ("label_offset", C.c_int64), ("world_mat", C.c_double * 16), ("scale_mat", C.c_double * 16),
+                ("camera_mat", C.c_double * 9), ("cam_pos", C.c_double * 3), ("img_w", C.c_double), ("img_h", C.c_double)]
 
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t)
@@ -285,7 +292,17 @@ def lib():
                 ("gsr_icp_sums_workspace_bytes", sz, [i64]),
                 ("gsr_icp_sums", C.c_int32, [vp, i64, vp, i64, vp, vp, vp, vp, sz, vp, vp]),
                 ("gsr_dist_score_workspace_bytes", sz, [C.c_int32]),
-                ("gsr_dist_score", C.c_int32, [vp, i64, vp, C.c_int32, f64, vp, sz, vp, vp, vp])):
+                ("gsr_dist_score", C.c_int32, [vp, i64, vp, C.c_int32, f64, vp, sz, vp, vp, vp]),
+                ("gsr_seg_hull_distance", C.c_int32, [vp, C.c_int32, i64, vp, C.c_int32, vp, vp]),
+                ("gsr_seg_mean_std_workspace_bytes", sz, [i64]),
+                ("gsr_seg_mean_std", C.c_int32, [vp, i64, vp, vp, sz, vp]),
+                ("gsr_seg_label_map", C.c_int32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]),
+                ("gsr_seg_views_workspace_bytes", sz, [C.c_int32]),
+                ("gsr_seg_views_prepare", C.c_int32, [vp, C.c_int32, i64, C.POINTER(GsrSegView), C.c_int32, i64, vp, sz, vp]),
+                ("gsr_seg_project", C.c_int32, [vp, C.c_int32, i64, vp, sz, C.c_int32, C.c_int32, vp, vp, vp]),
+                ("gsr_seg_assign", C.c_int32, [vp, C.c_int32, i64, vp, sz, C.c_int32, vp, vp, vp]),
+                ("gsr_seg_stats", C.c_int32, [vp, vp, vp, vp, i64, C.c_int32, vp, vp, vp]),
+                ("gsr_seg_augment_emit", C.c_int32, [vp, vp, C.c_int32, vp, vp, vp, vp, i64, vp, vp, vp, vp])):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]

@@ -5,7 +5,10 @@ method names, activations (exp / sigmoid / normalize, :37-43), Adam groups and l
 (:282-295), densify / prune / reset logic (:398-553), checkpoint tuple (:66-101) and PLY column
 layout incl. the extra `segment` column (:305-396).  Differences: the device is a constructor
 argument (the reference hard-codes "cuda"), PLY I/O is self-contained (no plyfile), and the
-SAM-mask segment augmentation of create_from_pcd (:132-258) is out of scope.
+segment augmentation of create_from_pcd (:132-258) runs through gaussmart_amd.segment_init (HIP kernels
+on the device, the numpy twins for a model on the CPU): its noise is one torch.randn from the generator
+passed in, not the reference's per-segment draws, and the uniform-upsampling branch labels its new
+points 0, which the reference forgets.
 """
 import os
 
@@ -117,17 +120,32 @@ class GaussianModel:
                       params["rotation"], params["opacity"])
         self.active_sh_degree = self.max_sh_degree if active_sh_degree is None else active_sh_degree
 
-    def create_from_pcd(self, pcd, spatial_lr_scale: float, dist2_fn=None):
-        """pcd has .points [N,3], .colors [N,3] in [0,1] (and optionally .segments).
-        scene/gaussian_model.py:166-275 without the mask-area augmentation."""
+    def create_from_pcd(self, pcd, spatial_lr_scale: float, dist2_fn=None, generator=None):
+        """pcd has .points [N,3], .colors [N,3] in [0,1] (and optionally .segments, .mask_areas).
+        scene/gaussian_model.py:166-275.  A non-empty pcd.mask_areas augments the cloud per segment, else
+        uniform_upsampling augments it as one segment (new points labelled 0), else nothing is added.  generator: the
+        torch.Generator (on the model's device) of the new points' noise; None is the device's global one.  A model on the
+        CPU takes segment_init's numpy twins."""
         self.spatial_lr_scale = spatial_lr_scale
         dev = self.device
         pts = torch.tensor(np.asarray(pcd.points)).float().to(dev)
         col = RGB2SH(torch.tensor(np.asarray(pcd.colors)).float().to(dev))
-        feats = torch.zeros((pts.shape[0], 3, (self.max_sh_degree + 1) ** 2), device=dev)
-        feats[:, :3, 0] = col
         seg = getattr(pcd, "segments", None)
         seg = torch.tensor(np.asarray(seg)).long() if seg is not None else None
+        mask_areas = getattr(pcd, "mask_areas", None)
+        if mask_areas or self.uniform_upsampling:
+            from . import segment_init as SI
+            if mask_areas:
+                seg = torch.zeros(len(pts), dtype=torch.long) if seg is None else seg
+                augment = SI.augment_point_cloud if dev.type == "cuda" else SI.augment_point_cloud_host
+                new_pts, new_col, new_seg = augment(pts, col, seg.to(dev), dict(mask_areas), generator=generator)
+            else:
+                new_pts, new_col, new_seg = SI.augment_uniform(pts, col, generator=generator)
+                seg = torch.zeros(len(pts), dtype=torch.long) if seg is None else seg
+            pts, col = torch.cat([pts, new_pts.to(dev)]), torch.cat([col, new_col.to(dev)])
+            seg = torch.cat([seg.to(dev), new_seg.to(dev)])
+        feats = torch.zeros((pts.shape[0], 3, (self.max_sh_degree + 1) ** 2), device=dev)
+        feats[:, :3, 0] = col
         if dist2_fn is None:
             from .knn import distCUDA2 as dist2_fn
         dist2 = torch.clamp_min(dist2_fn(pts), 0.0000001)

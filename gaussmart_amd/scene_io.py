@@ -4,9 +4,10 @@ point-cloud PLY the reference seeds Gaussians from, and the `Scene` container.
 Counterpart of scene/colmap_loader.py:43-242, scene/dataset_readers.py:26-341,
 utils/camera_utils.py:19-82 and scene/__init__.py:21-94 of the reference.  File formats are COLMAP's
 (public); the readers are checked against the reference's own readers on small committed models
-(tests/golden/colmap_*/, tests/test_scene_io.py).  The SAM/segment-specific branches of the
-reference (cleaned point cloud lookup, mask areas) are out of scope; a `segment` column is carried
-through when present.
+(tests/golden/colmap_*/, tests/test_scene_io.py).  A `segment` column is carried through when present;
+`fetchPly(path, segmentation_dir)` reads the segment labels and mask areas that gaussmart_amd.segment_cli
+(or the reference's identification/main.py) wrote, where the reference looks them up under fixed relative
+paths (scene/dataset_readers.py:114-159).  Its cleaned-point-cloud lookup is out of scope.
 """
 import json
 import os
@@ -155,6 +156,7 @@ class BasicPointCloud(NamedTuple):
     colors: np.ndarray
     normals: np.ndarray
     segments: np.ndarray
+    mask_areas: dict = {}      # {segment label: largest mask area in pixels}; empty: no augmentation
 
 
 _PLY_TYPES = {"float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8", "uchar": "u1", "uint8": "u1",
@@ -190,13 +192,28 @@ def read_ply_vertices(path):
         return np.frombuffer(f.read(count * dt.itemsize), dtype=dt, count=count)
 
 
-def fetchPly(path):
+def fetchPly(path, segmentation_dir=None):
+    """segmentation_dir: a directory with segment_indices.npy and / or mask_areas.npy (a pickled dict); a file that is there
+    replaces the PLY's `segment` column / fills mask_areas.  Points and labels are cut to the shorter of the two, as in the
+    reference (scene/dataset_readers.py:152-159)."""
     v = read_ply_vertices(path)
     pos = np.vstack([v["x"], v["y"], v["z"]]).T
     col = np.vstack([v["red"], v["green"], v["blue"]]).T / 255.0
     nrm = np.vstack([v["nx"], v["ny"], v["nz"]]).T if "nx" in v.dtype.names else np.zeros_like(pos)
     seg = v["segment"].astype(np.int32) if "segment" in v.dtype.names else np.zeros(len(pos), dtype=np.int32)
-    return BasicPointCloud(points=pos, colors=col, normals=nrm, segments=seg)
+    if segmentation_dir is None:
+        return BasicPointCloud(points=pos, colors=col, normals=nrm, segments=seg)
+    if not os.path.isdir(segmentation_dir):
+        raise FileNotFoundError(f"segmentation_dir {segmentation_dir} is not a directory")
+    seg_path, area_path = os.path.join(segmentation_dir, "segment_indices.npy"), os.path.join(segmentation_dir, "mask_areas.npy")
+    mask_areas = {}
+    if os.path.exists(seg_path):
+        seg = np.load(seg_path).reshape(-1)
+    if os.path.exists(area_path):
+        # (a dict saved with np.save is a pickle: only read directories you wrote yourself)
+        mask_areas = {int(k): int(a) for k, a in np.load(area_path, allow_pickle=True).item().items()}
+    n = min(len(seg), len(pos))
+    return BasicPointCloud(points=pos[:n], colors=col[:n], normals=nrm[:n], segments=seg[:n], mask_areas=mask_areas)
 
 
 def storePly(path, xyz, rgb, segments=None):
@@ -287,7 +304,7 @@ def _create_once(ply_path, make):
         dist.barrier()
 
 
-def readColmapSceneInfo(path, images=None, eval=False, llffhold=8, open_images=True):
+def readColmapSceneInfo(path, images=None, eval=False, llffhold=8, open_images=True, segmentation_dir=None):
     sparse = os.path.join(path, "sparse/0")
     if os.path.exists(os.path.join(sparse, "images.bin")):
         ext, intr = read_extrinsics_binary(os.path.join(sparse, "images.bin")), read_intrinsics_binary(os.path.join(sparse, "cameras.bin"))
@@ -307,7 +324,7 @@ def readColmapSceneInfo(path, images=None, eval=False, llffhold=8, open_images=T
             xyz, rgb, _ = read_points3D_text(os.path.join(sparse, "points3D.txt"))
         storePly(dst, xyz, rgb, np.zeros(len(xyz), dtype=np.int32))
     _create_once(ply_path, make)
-    return SceneInfo(fetchPly(ply_path), train, test, getNerfppNorm(train), ply_path)
+    return SceneInfo(fetchPly(ply_path, segmentation_dir), train, test, getNerfppNorm(train), ply_path)
 
 
 def readCamerasFromTransforms(path, transformsfile, white_background, extension=".png", open_images=True):
@@ -334,7 +351,8 @@ def readCamerasFromTransforms(path, transformsfile, white_background, extension=
     return infos
 
 
-def readNerfSyntheticInfo(path, white_background=False, eval=False, extension=".png", open_images=True, seed=0):
+def readNerfSyntheticInfo(path, white_background=False, eval=False, extension=".png", open_images=True, seed=0,
+                          segmentation_dir=None):
     train = readCamerasFromTransforms(path, "transforms_train.json", white_background, extension, open_images)
     test = readCamerasFromTransforms(path, "transforms_test.json", white_background, extension, open_images)
     if not eval:
@@ -345,14 +363,14 @@ def readNerfSyntheticInfo(path, white_background=False, eval=False, extension=".
         xyz = rng.random((100_000, 3)) * 2.6 - 1.3
         storePly(dst, xyz, SH2RGB(rng.random((100_000, 3)) / 255.0) * 255)
     _create_once(ply_path, make)
-    return SceneInfo(fetchPly(ply_path), train, test, getNerfppNorm(train), ply_path)
+    return SceneInfo(fetchPly(ply_path, segmentation_dir), train, test, getNerfppNorm(train), ply_path)
 
 
-def load_scene_info(path, images=None, eval=False, white_background=False, open_images=True):
+def load_scene_info(path, images=None, eval=False, white_background=False, open_images=True, segmentation_dir=None):
     if os.path.exists(os.path.join(path, "sparse")):
-        return readColmapSceneInfo(path, images, eval, open_images=open_images)
+        return readColmapSceneInfo(path, images, eval, open_images=open_images, segmentation_dir=segmentation_dir)
     if os.path.exists(os.path.join(path, "transforms_train.json")):
-        return readNerfSyntheticInfo(path, white_background, eval, open_images=open_images)
+        return readNerfSyntheticInfo(path, white_background, eval, open_images=open_images, segmentation_dir=segmentation_dir)
     raise ValueError(f"could not recognise the scene type of {path}")
 
 
@@ -384,9 +402,9 @@ class Scene:
 
     def __init__(self, source_path, gaussians, model_path=None, load_iteration=None, images=None, eval=False,
                  white_background=False, resolution=-1, resolution_scales=(1.0,), data_device="cuda", shuffle=True, seed=0,
-                 dist2_fn=None):
+                 dist2_fn=None, segmentation_dir=None):
         self.model_path, self.gaussians, self.loaded_iter = model_path, gaussians, None
-        info = load_scene_info(source_path, images, eval, white_background)
+        info = load_scene_info(source_path, images, eval, white_background, segmentation_dir=segmentation_dir)
         self.cameras_extent = info.nerf_normalization["radius"]
         if load_iteration is not None and model_path:
             if load_iteration == -1:

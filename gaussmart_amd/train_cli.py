@@ -46,6 +46,11 @@ def main(argv=None):
     ap.add_argument("--lambda_dist", type=float, default=0.0)
     ap.add_argument("--start_checkpoint", default=None)
     ap.add_argument("--log_every", type=int, default=500)
+    ap.add_argument("--segmentation_dir", default=None,
+                    help="directory with segment_indices.npy / mask_areas.npy (gaussmart_amd.segment_cli's OUT/segments/point_cloud): "
+                         "the initial cloud is augmented per segment")
+    ap.add_argument("--uniform_upsampling", action="store_true",
+                    help="without mask areas: augment the initial cloud as one segment")
     args = ap.parse_args(argv)
 
     import torch.distributed as dist
@@ -59,9 +64,10 @@ def main(argv=None):
 
     opt = OptimizationParams(iterations=args.iterations, lambda_normal=args.lambda_normal, lambda_dist=args.lambda_dist)
     pipe = PipelineParams(depth_ratio=args.depth_ratio)
-    gaussians = GaussianModel(args.sh_degree, device=dev)
+    gaussians = GaussianModel(args.sh_degree, uniform_upsampling=args.uniform_upsampling, device=dev)
     scene = Scene(args.source_path, gaussians, model_path=args.model_path, images=args.images, eval=args.eval,
-                  white_background=args.white_background, resolution=args.resolution, data_device=dev)
+                  white_background=args.white_background, resolution=args.resolution, data_device=dev,
+                  segmentation_dir=args.segmentation_dir)
     gaussians.training_setup(opt)
     first_iter = 0
     if args.start_checkpoint:

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 12  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
+#define GSR_ABI_VERSION 13  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
                                 6: gsr_surface_maps_forward / _backward;
                                 7: TSDF fusion and marching cubes (GsrTsdfVolume, gsr_tsdf_*, gsr_mcubes_*);
                                 8: mesh post-processing (gsr_mesh_*) and gsr_depth_aabb;
@@ -42,7 +42,8 @@ extern "C" {
                                 10: mesh depth rendering and culling by visibility (gsr_mesh_depth_*, gsr_mesh_vis_*);
                                 11: DTU mesh evaluation (gsr_mesh_sample_*, gsr_points_*, gsr_dist_mean);
                                 12: Tanks-and-Temples mesh evaluation (gsr_mesh_face_centres, gsr_points_transform / _crop_polygon /
-                                    _voxel_*, gsr_icp_sums, gsr_dist_score) */
+                                    _voxel_*, gsr_icp_sums, gsr_dist_score);
+                                13: segment-aware initialisation of the point cloud (GsrSegView, gsr_seg_*) */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -827,6 +828,105 @@ int32_t gsr_icp_sums(const float* source, int64_t n_source, const float* target,
 size_t gsr_dist_score_workspace_bytes(int32_t n_bins);
 int32_t gsr_dist_score(const double* dist, int64_t n, const double* edges_host, int32_t n_bins, double tau, void* ws,
                        size_t ws_bytes, int64_t* count_out, int64_t* hist_out, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- segment-aware initialisation of the point cloud
+ * What the reference does to the initial cloud before training: the convex-hull filter (filter/hull_removal.py:10-25), the
+ * labelling of points by view masks (identification/main.py:114-148, identification/pc_projection.py:21-135) and the
+ * per-segment augmentation (scene/gaussian_model.py:132-258); kernels in seg_init.hip.  The masks are somebody else's
+ * (segments_NNN.npz); SAM, the camera clustering and the DINO encoder are not part of this.  All geometry decisions are
+ * fp64 on the device, seg_init.o is compiled with -ffp-contract=off, points are f32 or f64 [n,3] (point_f64 = 0 / 1) and
+ * are widened on load, counts are int32-indexable (more: GSR_E_UNSUPPORTED).  No floating-point atomic is used: every
+ * result has the same bits on every run.  The rules, each in this one place:
+ *   SEG_HULL        d_i = min over the facets f, in index order, of |((n_f.x p.x + n_f.y p.y) + n_f.z p.z) + o_f| / |n_f|,
+ *                   |n_f| = sqrt((x x + y y) + z z) formed once per facet; equations [F,4] are scipy's ConvexHull.equations
+ *                   (Qhull runs on the host).  A NaN distance stays (np.min).  No N x F matrix exists.
+ *   SEG_MEANSTD     population mean and standard deviation (np.std, ddof = 0): mean = sum d / n, std = sqrt(sum (d - mean)^2
+ *                   / n), each sum in a fixed order (thread t of workgroup b adds elements b 256 + t, + blocks 256, ...; a
+ *                   fixed tree over the 256 threads; the partials likewise).  n = 0: NaN, NaN.
+ *   SEG_FILTER      keep_i = (d_i - mean) / std >= -theta (theta = 1.96).  std = 0 (every point on the hull) makes z NaN and
+ *                   nothing is kept, which is what numpy yields.  Formed by the caller on the device arrays.
+ *   SEG_LABEL       one view's masks [M,H,W] (uint8, set = non-zero): label[y,x] = the highest m with masks[m,y,x] != 0, or
+ *                   -1; area[m] = number of set pixels of mask m.  The reference overwrites mask by mask, so the last, i.e.
+ *                   the highest, index wins (pc_projection.py:125-133).  M <= 32767 (more: GSR_E_UNSUPPORTED); M = 0 gives an
+ *                   all -1 map.
+ *   SEG_AREAS       areas[m] = max over the views of area[m] (the caller's dict).  The reference keys by the per-view mask
+ *                   index, so index 3 of view 0 and index 3 of view 2 are the same segment id; that is kept.
+ *   SEG_PROJ_DTU    s = scale_mat [p;1], c = world_mat s, each row ((m0 a + m1 b) + m2 c) + m3 d; u = fx (c.x / c.w) + cx,
+ *                   v = fy (c.y / c.w) + cy, z = c.z with fx, fy, cx, cy = camera_mat[0,0], [1,1], [0,2], [1,2].  If fewer than
+ *                   0.1 n points have 0 <= u < 1554 and 0 <= v < 1162 (the reference's hard-coded size; an int64 count by
+ *                   integer atomics, read from device memory by the later kernels) the view uses the normalised rays instead:
+ *                   r = (p - cam_pos) / |p - cam_pos|, u = (r.x / (r.z + 1e-10)) (1554 / 3) + 1554 / 2, v likewise with 1162;
+ *                   z stays c.z.  cam_pos = -inv(world_mat[:3,:3]) world_mat[:3,3] is formed by the host with numpy.
+ *   SEG_PROJ_NERF   c = R p + t (R, t from world_mat), q = K c (K = camera_mat, 3x3), each row (m0 a + m1 b) + m2 c;
+ *                   u = q.x / q.z, v = q.y / q.z, z = c.z.
+ *   SEG_PROJ_TYT    lo, hi = per-axis minimum / maximum over the points without a NaN (one reduction shared by all views);
+ *                   u = nan_to_num((0.1 + (1 - 2 0.1) (p.x - lo.x) / ((hi.x - lo.x) + 1e-10)) img_w), v likewise with y and
+ *                   img_h; z = ((p - cam_pos) . world_mat[2,:3]) added left to right, cam_pos = -R^T t formed by the host.  If
+ *                   every point has a NaN, u = v = z = 0.
+ *   SEG_ASSIGN      a point takes the label of the first view, in order, with (a) n_masks > 0, (b) 0 <= u < W and 0 <= v < H
+ *                   (W, H: that view's label map), (c) z > 0, (d) label[rint(clip(v, 0, H - 1)), rint(clip(u, 0, W - 1))] != -1,
+ *                   rint rounding half to even; else -1.  Any NaN makes (b) or (c) false.  Views may differ in size.
+ *   SEG_STATS       per label l in [0, n_labels), over the points in ascending index (a stable sort by label): count; mean =
+ *                   sum p / count; cov = sum (p - mean)(p - mean)^T / (count - 1) (torch.cov, correction 1); std = sqrt of its
+ *                   diagonal; mean colour.  fp64 from the f32 inputs, thread t of the label's workgroup adds the run's elements
+ *                   t, t + 256, ... and SEG_MEANSTD's tree adds the 256 sums; the caller rounds once to f32.  count 0: NaN
+ *                   means; count 0 or 1: NaN cov and std.
+ *   SEG_FACTOR      (caller, batched fp64 on the host) eigh(cov), eigenvalues clamped at 1e-6, V diag(w) V^T, times alpha^2 =
+ *                   0.25, Cholesky factor L.  A segment whose L is not finite takes diag(0.5 std) (the reference's except
+ *                   branch).
+ *   SEG_PLAN        (caller) labels in ascending order; -1 and counts < 5 are skipped; target = max(int(sqrt(area) 0.1), 10),
+ *                   area = areas.get(label, median of the areas); add = target - count where positive.
+ *   SEG_EMIT        new point i belongs to the segment s with offsets[s] <= i < offsets[s + 1] (binary search); xyz = mean_s +
+ *                   L_s eps_i in fp64, each row (l0 e0 + l1 e1) + l2 e2, rounded once to f32; colour = mean colour of s, label
+ *                   = labels[s].  eps is the caller's torch.randn((total, 3), generator=...).  DEVIATION: the reference draws
+ *                   one MultivariateNormal.sample per segment from the global generator; that random stream is not reproduced.
+ *   gsr_seg_hull_distance : SEG_HULL; equations device f64 [n_facets,4]; out device f64 [n].
+ *   gsr_seg_mean_std : SEG_MEANSTD; out device f64 [2]; ws: gsr_seg_mean_std_workspace_bytes(n).
+ *   gsr_seg_label_map : SEG_LABEL; masks device uint8 [n_masks,H,W]; label device int16 [H,W]; area device int64 [n_masks].
+ *   gsr_seg_views_prepare : copies views_host [n_views] into ws, checks that every view with masks has its label map inside
+ *                   label_maps (label_elems int16 elements), and enqueues SEG_PROJ_TYT's bounds and SEG_PROJ_DTU's counts.
+ *                   ws: gsr_seg_views_workspace_bytes(n_views); the two calls below take the same ws, points and n.
+ *   gsr_seg_project : SEG_PROJ_* of view `view`; uv_out device f64 [n,2], z_out device f64 [n].
+ *   gsr_seg_assign : SEG_ASSIGN; label_maps device int16 (every view's map at its label_offset); out device int32 [n].
+ *   gsr_seg_stats  : SEG_STATS; points, colors device f32 [n,3]; order device int64 [n]; seg_off device int64 [n_labels + 1];
+ *                   count_out device int64 [n_labels]; stats_out device f64 [n_labels,18]: mean 3, cov 9, std 3, colour 3.
+ *   gsr_seg_augment_emit : SEG_EMIT; eps device f32 [total,3]; offsets device int64 [n_segs + 1]; mean, mean_color device f32
+ *                   [n_segs,3]; tril device f32 [n_segs,9]; labels device int64 [n_segs]; outputs device f32 [total,3] twice and
+ *                   int64 [total].
+ * None of these calls synchronises.  Negative counts, a kind outside the three, a null pointer with a non-zero count or a
+ * workspace that is too small: GSR_E_INVALID before anything is launched, the message names the argument. */
+#define GSR_SEG_DTU 0
+#define GSR_SEG_NERF 1
+#define GSR_SEG_TYT 2
+typedef struct GsrSegView {
+    int32_t kind;             /* GSR_SEG_DTU / _NERF / _TYT */
+    int32_t width, height;    /* of this view's label map */
+    int32_t n_masks;
+    int64_t label_offset;     /* first element of this view's map in label_maps */
+    double world_mat[16];     /* row-major 4x4 */
+    double scale_mat[16];     /* DTU */
+    double camera_mat[9];     /* row-major 3x3 */
+    double cam_pos[3];        /* DTU fallback and TYT: the camera centre, formed by the host */
+    double img_w, img_h;      /* TYT: the image size of the normalisation */
+} GsrSegView;
+int32_t gsr_seg_hull_distance(const void* points, int32_t point_f64, int64_t n, const double* equations, int32_t n_facets,
+                              double* out, gsr_stream_t stream);
+size_t gsr_seg_mean_std_workspace_bytes(int64_t n);
+int32_t gsr_seg_mean_std(const double* d, int64_t n, double* out, void* ws, size_t ws_bytes, gsr_stream_t stream);
+int32_t gsr_seg_label_map(const uint8_t* masks, int32_t n_masks, int32_t H, int32_t W, int16_t* label, int64_t* area,
+                          gsr_stream_t stream);
+size_t gsr_seg_views_workspace_bytes(int32_t n_views);
+int32_t gsr_seg_views_prepare(const void* points, int32_t point_f64, int64_t n, const GsrSegView* views_host, int32_t n_views,
+                              int64_t label_elems, void* ws, size_t ws_bytes, gsr_stream_t stream);
+int32_t gsr_seg_project(const void* points, int32_t point_f64, int64_t n, void* ws, size_t ws_bytes, int32_t n_views, int32_t view,
+                        double* uv_out, double* z_out, gsr_stream_t stream);
+int32_t gsr_seg_assign(const void* points, int32_t point_f64, int64_t n, void* ws, size_t ws_bytes, int32_t n_views,
+                       const int16_t* label_maps, int32_t* out, gsr_stream_t stream);
+int32_t gsr_seg_stats(const float* points, const float* colors, const int64_t* order, const int64_t* seg_off, int64_t n,
+                      int32_t n_labels, int64_t* count_out, double* stats_out, gsr_stream_t stream);
+int32_t gsr_seg_augment_emit(const float* eps, const int64_t* offsets, int32_t n_segs, const float* mean, const float* tril,
+                             const float* mean_color, const int64_t* labels, int64_t total, float* out_xyz, float* out_color,
+                             int64_t* out_label, gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only
