@@ -148,6 +148,30 @@ def plane_filter(points, plane):
 
 
 # ---------------------------------------------------------------- fixtures shared by the CPU and the GPU tests
+def random_cloud(n, seed, thresh=0.2, neighbours=5.0):
+    """n uniform points in a cube sized so that a ball of radius thresh holds `neighbours` of them on average."""
+    side = (max(n, 1) * 4.0 / 3.0 * np.pi * thresh ** 3 / neighbours) ** (1.0 / 3.0)
+    return (np.random.default_rng(seed).random((n, 3)) * side).astype(np.float32)
+
+
+def lattice():
+    g = np.arange(6, dtype=np.float32) * np.float32(0.25)          # dyadic: d2 == thresh^2 exactly between neighbours
+    return np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+
+
+# name -> (make the cloud, thresh, whether pair_margin is asserted first): the down-sampling cases of tests/test_gpu_mesh_eval.py,
+# which tests/test_cloud_scale_ref_cpu.py also runs the fast reference over
+DOWNSAMPLE = {f"n{n}": (lambda n=n: random_cloud(n, 100 + n), 0.2, True) for n in (0, 1, 63, 64, 65, 4097)}
+DOWNSAMPLE.update({
+    "random_3000": (lambda: random_cloud(3000, 7), 0.2, True),
+    "lattice_6": (lattice, 0.25, False),
+    "lattice_6_shuffled": (lambda: np.random.default_rng(3).permutation(lattice()), 0.25, False),
+    "duplicates_200": (lambda: np.tile(np.array([[0.5, -1.0, 2.0]], np.float32), (200, 1)), 0.1, False),
+    "sorted_line_2000": (lambda: np.stack([np.arange(2000) * 0.6 * 0.2, np.zeros(2000), np.zeros(2000)], 1).astype(np.float32),
+                         0.2, True),
+})
+
+
 def icosphere(subdiv, radius):
     """Icosahedron subdivided `subdiv` times: 20 * 4^subdiv triangles (3 -> 1,280)."""
     t = (1 + 5 ** 0.5) / 2

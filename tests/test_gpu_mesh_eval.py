@@ -72,25 +72,7 @@ def test_sampling_cap_names_the_density():
 
 
 # ---------------------------------------------------------------- 2. down-sampling
-def _random_cloud(n, seed, thresh=0.2, neighbours=5.0):
-    side = (max(n, 1) * 4.0 / 3.0 * np.pi * thresh ** 3 / neighbours) ** (1.0 / 3.0)
-    return (np.random.default_rng(seed).random((n, 3)) * side).astype(np.float32)
-
-
-def _lattice():
-    g = np.arange(6, dtype=np.float32) * np.float32(0.25)          # dyadic: d2 == thresh^2 exactly between neighbours
-    return np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
-
-
-DOWNSAMPLE = {f"n{n}": (lambda n=n: _random_cloud(n, 100 + n), 0.2, True) for n in (0, 1, 63, 64, 65, 4097)}
-DOWNSAMPLE.update({
-    "random_3000": (lambda: _random_cloud(3000, 7), 0.2, True),
-    "lattice_6": (_lattice, 0.25, False),
-    "lattice_6_shuffled": (lambda: np.random.default_rng(3).permutation(_lattice()), 0.25, False),
-    "duplicates_200": (lambda: np.tile(np.array([[0.5, -1.0, 2.0]], np.float32), (200, 1)), 0.1, False),
-    "sorted_line_2000": (lambda: np.stack([np.arange(2000) * 0.6 * 0.2, np.zeros(2000), np.zeros(2000)], 1).astype(np.float32),
-                         0.2, True),
-})
+_random_cloud, DOWNSAMPLE = R.random_cloud, R.DOWNSAMPLE          # (the table lives beside the reference: the CPU tests share it)
 
 
 @pytest.mark.parametrize("name", list(DOWNSAMPLE))
@@ -207,7 +189,7 @@ def test_obs_filter_and_plane_exact():
 def test_distance_mean_fixed_order():
     from gaussmart_amd.mesh_eval import distance_mean
     rng = np.random.default_rng(9)
-    for n in (0, 1, 255, 256, 257, 300001):
+    for n in (0, 1, 255, 256, 257, 64 ** 3, 64 ** 3 + 1, 300001):      # 64^3 = 1024 x 256: the last size of one trip of the grid
         d = rng.random(n) * 20
         d[rng.random(n) < 0.3] = np.inf
         fin = d[np.isfinite(d)]

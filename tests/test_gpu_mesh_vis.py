@@ -81,6 +81,36 @@ def test_depth_interval_subpixel_triangles():
     assert share < 0.05 and (got > 0).sum() > 1000
 
 
+def _large_pairs(verts, tris, w2c, H, W, intr):
+    """The number of (triangle, view) pairs whose pixel box (VIS_COVER's guard, in float64) is wider or higher than 8."""
+    fx, fy, cx, cy = intr
+    total = 0
+    for m in w2c:
+        q = R.camera_space(verts, m)[tris]
+        u, v = fx * q[:, :, 0] / q[:, :, 2] + cx, fy * q[:, :, 1] / q[:, :, 2] + cy
+        x0, x1 = np.clip(np.ceil(u.min(1) - 1.5), 0, W), np.clip(np.floor(u.max(1) + 0.5), -1, W - 1)
+        y0, y1 = np.clip(np.ceil(v.min(1) - 1.5), 0, H), np.clip(np.floor(v.max(1) + 0.5), -1, H - 1)
+        ok = (q[:, :, 2] >= R.NEAR).all(1) & (x0 <= x1) & (y0 <= y1)
+        total += int((ok & ((x1 - x0 >= 8) | (y1 - y0 >= 8))).sum())
+    return total
+
+
+def test_depth_interval_many_large_pairs():
+    """The large path's fixed grid of 2,048 workgroups takes a second trip over its work list: two coarse spheres (280 triangles
+    of some 6 x 9 pixels) in 16 views give about 3,000 large pairs; every pixel of every view under the interval test."""
+    v, t = R.join(R.uv_sphere(10, 8, 0.5, (-0.25, 0.05, 0.45)), R.uv_sphere(10, 8, 0.7, (0.3, -0.1, -0.4)))
+    w2c = R.w2c32(R.ring_cameras(16, seed=11))
+    H, W, f = SIZES["96x64"]
+    intr = R.intrinsics(H, W, f)
+    n_large = _large_pairs(v, t, w2c, H, W, intr)
+    assert n_large > 2048 + 512                              # well beyond one trip, whatever the last bit of a box says
+    got = _render(v, t, w2c, H, W, intr).cpu().numpy()
+    mixed = _check_interval(got, v, t, w2c, H, W, intr, ("coarse",))
+    print(f"coarse spheres: {n_large} large pairs of {len(t) * len(w2c)}, {int((got > 0).sum())} of {got.size} pixels hit, "
+          f"{mixed} with disagreeing samples")
+    assert all(0.1 < (g > 0).mean() < 0.6 for g in got)
+
+
 def _single(verts, tris, H=30, W=40, intr=(10.0, 10.0, 20.0, 15.0), near=R.NEAR, far=R.FAR, exact=True):
     """One view from the origin along +z, held to the interval test; exact=True: no pixel's five samples disagree, so the hit
     mask must be float64's exactly."""

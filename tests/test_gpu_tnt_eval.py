@@ -16,15 +16,11 @@ from gaussmart_amd import tnt_eval as TE
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
-SIZES = (0, 1, 255, 256, 257, 4097)
+SIZES, _cloud = R.SIZES, R.cloud
 
 
 def _dev(a, dtype=np.float32):
     return torch.from_numpy(np.ascontiguousarray(a, dtype)).to(DEV)
-
-
-def _cloud(n, seed, scale=10.0):
-    return ((np.random.default_rng(seed).random((n, 3)) - 0.4) * scale).astype(np.float32)
 
 
 # ---------------------------------------------------------------- 1. TNT_CLOUD, TNT_TRANSFORM
@@ -119,18 +115,7 @@ def test_crop_polygon_sizes():
 
 
 # ---------------------------------------------------------------- 3. TNT_VOXEL
-def _dyadic(n, seed):
-    return (np.random.default_rng(seed).integers(-40, 40, size=(n, 3)) * 0.25).astype(np.float32)
-
-
-VOXEL = {f"n{n}": (lambda n=n: _cloud(n, 60 + n, 4.0), 0.37) for n in SIZES}
-VOXEL.update({
-    "n20000": (lambda: _cloud(20000, 61, 6.0), 0.21),
-    "dyadic_on_faces": (lambda: _dyadic(4097, 62), 0.5),
-    "negative": (lambda: -np.abs(_cloud(4097, 63, 5.0)) - 3.0, 0.3),
-    "copies_of_one_point": (lambda: np.repeat(_cloud(1, 64), 4097, 0), 0.1),
-    "one_cell_distinct": (lambda: _cloud(4097, 65, 1.0), 50.0),
-})
+VOXEL = R.VOXEL          # (the table lives beside the reference: the CPU tests share it)
 
 
 @pytest.mark.parametrize("name", list(VOXEL))
@@ -171,13 +156,18 @@ def test_uniform_down_sample():
 
 
 # ---------------------------------------------------------------- 4. TNT_ICP_SUMS
-@pytest.mark.parametrize("n", SIZES + (20000,))
-def test_icp_sums_fixed_order(n):
+def check_icp_sums(n, pairs_from=0, pair_at_end=False):
+    """Both passes of the sums on n random pairs (three in ten without a correspondence; none below index `pairs_from`; the last
+    point has one if `pair_at_end`) against numpy under the order-independent bound, twice for the same bits, and against the
+    host twin.  tests/test_gpu_cloud_scale.py runs the same body beyond one trip of the grid."""
     rng = np.random.default_rng(70 + n)
     m = 500
     src, tgt = _cloud(n, 71 + n), _cloud(m, 72)
     idx = rng.integers(0, m, size=n).astype(np.int32)
     idx[rng.random(n) < 0.3] = -1
+    idx[:pairs_from] = -1
+    if pair_at_end:
+        idx[-1] = m - 1
     dist = rng.random(n) * 0.3
     dist[idx < 0] = np.inf
     args = (_dev(src), _dev(tgt), _dev(dist, np.float64), _dev(idx, np.int32))
@@ -198,6 +188,12 @@ def test_icp_sums_fixed_order(n):
     assert np.array_equal(TE.icp_sums(*args, means=means), p2)
     host1, host2 = TE.icp_sums_host(src, tgt, dist, idx), TE.icp_sums_host(src, tgt, dist, idx, means)
     assert host1[0] == p1[0] and np.allclose(host1, p1, rtol=1e-12, atol=1e-12) and np.allclose(host2, p2, rtol=1e-10, atol=1e-10)
+    return len(rows)
+
+
+@pytest.mark.parametrize("n", SIZES + (20000,))
+def test_icp_sums_fixed_order(n):
+    check_icp_sums(n)
 
 
 def test_icp_sums_without_pairs():

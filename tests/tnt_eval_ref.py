@@ -105,6 +105,29 @@ def score(dist, tau, edges):
 
 
 # ---------------------------------------------------------------- fixtures
+SIZES = (0, 1, 255, 256, 257, 4097)
+
+
+def cloud(n, seed, scale=10.0):
+    return ((np.random.default_rng(seed).random((n, 3)) - 0.4) * scale).astype(np.float32)
+
+
+def dyadic(n, seed):
+    return (np.random.default_rng(seed).integers(-40, 40, size=(n, 3)) * 0.25).astype(np.float32)
+
+
+# name -> (make the cloud, voxel size): the voxel-grid cases of tests/test_gpu_tnt_eval.py, which
+# tests/test_cloud_scale_ref_cpu.py also runs the fast reference over
+VOXEL = {f"n{n}": (lambda n=n: cloud(n, 60 + n, 4.0), 0.37) for n in SIZES}
+VOXEL.update({
+    "n20000": (lambda: cloud(20000, 61, 6.0), 0.21),
+    "dyadic_on_faces": (lambda: dyadic(4097, 62), 0.5),
+    "negative": (lambda: -np.abs(cloud(4097, 63, 5.0)) - 3.0, 0.3),
+    "copies_of_one_point": (lambda: np.repeat(cloud(1, 64), 4097, 0), 0.1),
+    "one_cell_distinct": (lambda: cloud(4097, 65, 1.0), 50.0),
+})
+
+
 def similarity(scale, axis, degrees, translation):
     axis = np.asarray(axis, np.float64) / np.linalg.norm(axis)
     a = math.radians(degrees)
