@@ -16,7 +16,7 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSR_LIB_PATH: developer aid for same-box A/B runs of two builds of the library (scripts/ab_builds.sh)
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "lib", "libgsr_hip.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_SCRATCH, GSR_BUF_SCRATCH2 = range(5)
 GSR_BUF_SYNC_SH = 100     # not a buffer: "the SH colour pass is about to be enqueued" (GSR_FLAG_DEFER_COLOR)
@@ -81,6 +81,12 @@ class GsrTsdfVolume(C.Structure):
                 ("block_lo", C.c_int32 * 3), ("block_hi", C.c_int32 * 3),
                 ("block_index", C.c_void_p), ("pool", C.c_void_p), ("pool_blocks", C.c_int64), ("n_alloc", C.c_int64),
                 ("n_views", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class GsrUnbView(C.Structure):
+    """include/gsr.h: one view of the unbounded field's device table (gaussmart_amd/mesh_unbounded.py)."""
+    _fields_ = [("col_x", C.c_float * 4), ("col_y", C.c_float * 4), ("col_w", C.c_float * 4),
+                ("depth", C.c_void_p), ("rgb", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32)]
 
 
 class GsrSegView(C.Structure):
@@ -267,7 +273,7 @@ def lib():
         L.gsr_mesh_vis_emit.restype = C.c_int32
         L.gsr_mesh_vis_emit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        vp, i64, f64, sz = C.c_void_p, C.c_int64, C.c_double, C.c_size_t
+        vp, i64, f64, sz, fp = C.c_void_p, C.c_int64, C.c_double, C.c_size_t, C.POINTER(C.c_float)
         for name, res, args in (
                 ("gsr_mesh_sample_workspace_bytes", sz, [i64]),
                 ("gsr_mesh_sample_count", C.c_int32, [vp, vp, i64, i64, f64, vp, sz, C.POINTER(i64), vp]),
@@ -302,7 +308,15 @@ def lib():
                 ("gsr_seg_project", C.c_int32, [vp, C.c_int32, i64, vp, sz, C.c_int32, C.c_int32, vp, vp, vp]),
                 ("gsr_seg_assign", C.c_int32, [vp, C.c_int32, i64, vp, sz, C.c_int32, vp, vp, vp]),
                 ("gsr_seg_stats", C.c_int32, [vp, vp, vp, vp, i64, C.c_int32, vp, vp, vp]),
-                ("gsr_seg_augment_emit", C.c_int32, [vp, vp, C.c_int32, vp, vp, vp, vp, i64, vp, vp, vp, vp])):
+                ("gsr_seg_augment_emit", C.c_int32, [vp, vp, C.c_int32, vp, vp, vp, vp, i64, vp, vp, vp, vp]),
+                ("gsr_unb_lattice_size", C.c_int32, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+                ("gsr_unb_points", C.c_int32, [vp, C.c_int32, vp, i64, fp, C.c_float, C.c_float, C.c_int32, vp, vp, vp]),
+                ("gsr_unb_lattice_box", C.c_int32, [vp, C.c_int32, f64, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                    C.POINTER(C.c_int32), fp, C.c_float, C.c_float, vp, vp]),
+                ("gsr_unb_block_flags", C.c_int32, [vp, C.c_int32, f64, C.c_int32, C.c_int32, fp, C.c_float, C.c_float, vp, vp]),
+                ("gsr_unb_alloc", C.c_int32, [V, C.c_int32, C.c_int32, vp, vp]),
+                ("gsr_unb_fill", C.c_int32, [V, vp, C.c_int32, f64, C.c_int32, C.c_int32, fp, C.c_float, C.c_float, vp]),
+                ("gsr_unb_finish", C.c_int32, [vp, i64, f64, C.c_int32, C.c_int32, fp, C.c_float, C.c_float, vp])):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]

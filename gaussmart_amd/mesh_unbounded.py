@@ -1,0 +1,461 @@
+"""Mesh export for unbounded scenes: the reference's GaussianExtractor.extract_mesh_unbounded (utils/mesh_utils.py:184-279)
+and marching_cubes_with_contraction (utils/mcube_utils.py:17-95) on the HIP library (include/gsr.h, "unbounded mesh export":
+the UNB_* rules; kernels in csrc/unbounded.hip).
+
+    from gaussmart_amd.mesh_unbounded import UnboundedExtractor
+    ex = UnboundedExtractor(gaussians, render, pipe, bg_color=[0, 0, 0])
+    ex.reconstruction(scene.getTrainCameras())
+    mesh = ex.extract_mesh_unbounded(resolution=1024)            # mesh.TriangleMesh with vertex colours
+    post_process_mesh_device(ex.extract_mesh_unbounded(1024, to_host=False), cluster_to_keep=50)
+
+A view is (full_proj_transform [4,4], depth [1,H,W], rgb [3,H,W]); H and W may differ between views and the maps stay where
+they are (on the device for the kernels).  The field of all views is evaluated inside one launch; the lattice is never held
+densely: pass 1 keeps two sign flags per 16^3 block, the blocks around a sign change get pool slots, pass 2 fills only those,
+and the existing marching cubes run on that block-sparse volume (UNB_ALLOC).
+
+The *_host functions are torch fp32 twins on the CPU, operation by operation what the kernels do; they hold the lattice
+densely and are meant for small resolutions (tests, --host).
+"""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import torch
+
+from . import _lib
+from .mesh import DeviceTriangleMesh, GaussianExtractor, TriangleMesh
+from .tsdf import BLOCK, TSDFVolume
+
+
+def contract(x):
+    mag = torch.linalg.norm(x, ord=2, dim=-1)[..., None]
+    return torch.where(mag < 1, x, (2 - (1 / mag)) * (x / mag))
+
+
+def uncontract(y):
+    """UNB_CONTRACT: torch's arithmetic is the rule, also where |y| >= 2."""
+    mag = torch.linalg.norm(y, ord=2, dim=-1)[..., None]
+    return torch.where(mag < 1, y, (1 / (2 - mag)) * (y / mag))
+
+
+def quantile_radius(xyz, center, radius):
+    """min(np.quantile(|contract((xyz - center) / radius)|, 0.95) + 0.01, 1.9): the norms are sorted where xyz lives and only
+    the two neighbours of the quantile come to the host, interpolated as numpy's default (linear) method does."""
+    n = len(xyz)
+    if n == 0:
+        raise ValueError("quantile_radius: the model has no Gaussians")
+    c = torch.as_tensor(center, dtype=torch.float32, device=xyz.device)
+    m = contract((xyz.detach().float() - c) / float(radius)).norm(dim=-1)
+    s = torch.sort(m).values
+    pos = (n - 1) * 0.95
+    lo = min(int(np.floor(pos)), n - 1)
+    hi = min(lo + 1, n - 1)
+    a, b = (float(v) for v in s[[lo, hi]].cpu())
+    t = pos - lo
+    q = a + (b - a) * t if t < 0.5 else b - (b - a) * (1 - t)   # numpy's _lerp
+    return min(q + 0.01, 1.9)
+
+
+def lattice_size(resolution, crop):
+    """UNB_LATTICE: (G, blocks per axis) of the n^3 crops of `crop` points that share their boundary planes."""
+    resolution, crop = int(resolution), int(crop)
+    if crop < 2 or resolution < crop or resolution % crop != 0:
+        raise ValueError(f"resolution {resolution} must be a positive multiple of crop {crop} (crop >= 2)")
+    G = (resolution // crop) * (crop - 1) + 1
+    return G, -(-G // BLOCK)
+
+
+def lattice_coords(R, resolution, crop):
+    """UNB_LATTICE: the G coordinates of one axis, formed in fp64 and rounded to fp32 (host tensor)."""
+    G, _ = lattice_size(resolution, crop)
+    step = 2.0 * float(R) / (G - 1)
+    return torch.from_numpy((-float(R) + np.arange(G, dtype=np.float64) * step).astype(np.float32))
+
+
+def _check_views(views):
+    out = []
+    for i, (M, depth, rgb) in enumerate(views):
+        d = depth.detach()
+        if d.dim() == 3:
+            d = d[0]
+        if d.dim() != 2 or d.numel() == 0:
+            raise ValueError(f"view {i}: depth must be [1,H,W] with H, W > 0, got {list(depth.shape)}")
+        H, W = d.shape
+        c = rgb.detach()
+        if tuple(c.shape) != (3, H, W):
+            raise ValueError(f"view {i}: rgb must be [3,{H},{W}], got {list(rgb.shape)}")
+        M = torch.as_tensor(M).detach().to("cpu", torch.float32)
+        if tuple(M.shape) != (4, 4):
+            raise ValueError(f"view {i}: full_proj_transform must be [4,4], got {list(M.shape)}")
+        out.append((M, d, c))
+    return out
+
+
+class ViewTable:
+    """The device table of GsrUnbView records (include/gsr.h) of a list of views; keeps the maps it points to alive."""
+
+    def __init__(self, views, device):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.GsrError("ViewTable: the unbounded field kernels need a device (use the *_host twins on the CPU)")
+        self.maps = []
+        recs = (_lib.GsrUnbView * max(1, len(views)))()
+        for r, (M, d, c) in zip(recs, _check_views(views)):
+            d = d.to(self.device, torch.float32).contiguous()
+            c = c.to(self.device, torch.float32).contiguous()
+            self.maps += [d, c]
+            r.col_x[:], r.col_y[:], r.col_w[:] = M[:, 0].tolist(), M[:, 1].tolist(), M[:, 3].tolist()
+            r.depth, r.rgb, r.height, r.width = d.data_ptr(), c.data_ptr(), d.shape[0], d.shape[1]
+        self.n = len(views)
+        self.table = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(self.device)
+
+    @property
+    def ptr(self):
+        return C.c_void_p(self.table.data_ptr()) if self.n else None
+
+
+def _table(views, device):
+    return views if isinstance(views, ViewTable) else ViewTable(views, device)
+
+
+def _frame(center, radius, voxel_size):
+    c = np.asarray(center.detach().cpu() if torch.is_tensor(center) else center, dtype=np.float32).reshape(-1)
+    if c.size != 3:
+        raise ValueError("center needs 3 values")
+    # UNB_TRUNC: 5 voxel_size in double, rounded once to f32
+    return (C.c_float * 3)(*c.tolist()), float(radius), float(np.float32(5.0 * float(voxel_size)))
+
+
+def _stream(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+@torch.no_grad()
+def unbounded_field(points, views, center, radius, voxel_size, contracted=True, return_rgb=False):
+    """compute_unbounded_tsdf of the reference for device points [n,3] (gsr_unb_points): contracted samples, or with
+    contracted=False world points and the plain truncation.  Returns tsdf [n], or (tsdf, rgb [n,3])."""
+    if not points.is_cuda:
+        raise _lib.GsrError("unbounded_field: points must be a device tensor (unbounded_field_host is the CPU twin)")
+    dev = points.device
+    tab = _table(views, dev)
+    p = points.detach().to(torch.float32).reshape(-1, 3).contiguous()
+    n = len(p)
+    tsdf = torch.empty(n, dtype=torch.float32, device=dev)
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=dev) if return_rgb else None
+    cen, rad, trunc = _frame(center, radius, voxel_size)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().gsr_unb_points(tab.ptr, tab.n, C.c_void_p(p.data_ptr()), n, cen, rad, trunc, int(bool(contracted)),
+                                             C.c_void_p(tsdf.data_ptr()), C.c_void_p(rgb.data_ptr()) if return_rgb else None,
+                                             _stream(dev)))
+    return (tsdf, rgb) if return_rgb else tsdf
+
+
+def _sample_host(m, ix, iy):
+    """UNB_SAMPLE on a [C,H,W] map at clamped pixel coordinates: taps nw, ne, sw, se summed in that order."""
+    H, W = m.shape[-2:]
+    fx, fy = torch.floor(ix), torch.floor(iy)
+    x0, y0 = fx.long(), fy.long()
+    x1, y1 = (x0 + 1).clamp(max=W - 1), (y0 + 1).clamp(max=H - 1)
+    ax, ay, bx, by = ix - fx, iy - fy, (fx + 1) - ix, (fy + 1) - iy
+    r = m[:, y0, x0] * (bx * by)
+    r = r + m[:, y0, x1] * (ax * by)
+    r = r + m[:, y1, x0] * (bx * ay)
+    r = r + m[:, y1, x1] * (ax * ay)
+    return r
+
+
+@torch.no_grad()
+def unbounded_field_host(points, views, center, radius, voxel_size, contracted=True, return_rgb=False):
+    """The fp32 CPU twin of unbounded_field: the kernel's operations in the kernel's order, in torch."""
+    f32 = torch.float32
+    s = points.detach().to("cpu", f32).reshape(-1, 3)
+    cen, rad, trunc0 = _frame(center, radius, voxel_size)
+    cen, rad, trunc0 = torch.tensor(list(cen), dtype=f32), torch.tensor(rad, dtype=f32), torch.tensor(trunc0, dtype=f32)
+    if contracted:
+        m = torch.sqrt(s[:, 0] * s[:, 0] + s[:, 1] * s[:, 1] + s[:, 2] * s[:, 2])
+        a = 1 / (2 - m)
+        y = torch.where((m < 1)[:, None], s, a[:, None] * (s / m[:, None]))
+        x = y * rad + cen
+        trunc = torch.where(m > 1, trunc0 * (1 / (2 - m.clamp(max=1.9))), trunc0.expand_as(m))
+    else:
+        x, trunc = s, trunc0.expand(len(s))
+    tsdf = torch.ones(len(s), dtype=f32)
+    w = torch.ones(len(s), dtype=f32)
+    rgb = torch.zeros((len(s), 3), dtype=f32)
+    for M, d, c in _check_views(views):
+        d, c = d.to("cpu", f32), c.to("cpu", f32)
+        H, W = d.shape
+        px = x[:, 0] * M[0, 0] + x[:, 1] * M[1, 0] + x[:, 2] * M[2, 0] + M[3, 0]
+        py = x[:, 0] * M[0, 1] + x[:, 1] * M[1, 1] + x[:, 2] * M[2, 1] + M[3, 1]
+        z = x[:, 0] * M[0, 3] + x[:, 1] * M[1, 3] + x[:, 2] * M[2, 3] + M[3, 3]
+        u, v = px / z, py / z
+        ok = (u > -1) & (u < 1) & (v > -1) & (v < 1) & (z > 0)
+        ix = ((u + 1) / 2 * (W - 1)).clamp(0, W - 1)
+        iy = ((v + 1) / 2 * (H - 1)).clamp(0, H - 1)
+        ix, iy = torch.where(ok, ix, torch.zeros_like(ix)), torch.where(ok, iy, torch.zeros_like(iy))
+        sdf = _sample_host(d[None], ix, iy)[0] - z
+        ok = ok & (sdf > -trunc)
+        t = (sdf / trunc).clamp(-1, 1)
+        w1 = w + 1
+        tsdf = torch.where(ok, (tsdf * w + t) / w1, tsdf)
+        if return_rgb:
+            col = _sample_host(c, ix, iy).T
+            rgb = torch.where(ok[:, None], (rgb * w[:, None] + col) / w1[:, None], rgb)
+        w = torch.where(ok, w1, w)
+    return (tsdf, rgb) if return_rgb else tsdf
+
+
+def _box(lo, dims):
+    lo, dims = [int(v) for v in lo], [int(v) for v in dims]
+    if len(lo) != 3 or len(dims) != 3:
+        raise ValueError("lo and dims need 3 values each")
+    return lo, dims
+
+
+@torch.no_grad()
+def lattice_field(R, resolution, crop, lo, dims, views, center, radius, device=None):
+    """The dense field [dims] of lattice points lo + [0, dims) (gsr_unb_lattice_box): a test and debugging aid."""
+    dev = views.device if isinstance(views, ViewTable) else torch.device(device if device is not None else views[0][1].device)
+    tab = _table(views, dev)
+    lo, dims = _box(lo, dims)
+    out = torch.empty([max(0, d) for d in dims], dtype=torch.float32, device=dev)
+    cen, rad, trunc = _frame(center, radius, 2.0 * float(radius) / int(resolution))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().gsr_unb_lattice_box(tab.ptr, tab.n, float(R), int(resolution), int(crop), (C.c_int32 * 3)(*lo),
+                                                  (C.c_int32 * 3)(*dims), cen, rad, trunc, C.c_void_p(out.data_ptr()),
+                                                  _stream(dev)))
+    return out
+
+
+@torch.no_grad()
+def lattice_field_host(R, resolution, crop, lo, dims, views, center, radius):
+    """The CPU twin of lattice_field."""
+    lo, dims = _box(lo, dims)
+    s = lattice_coords(R, resolution, crop)
+    ax = [s[l:l + d] for l, d in zip(lo, dims)]
+    pts = torch.stack(torch.meshgrid(*ax, indexing="ij"), -1).reshape(-1, 3)
+    return unbounded_field_host(pts, views, center, radius, 2.0 * float(radius) / int(resolution)).reshape(dims)
+
+
+def block_flags_of_dense(field):
+    """UNB_ALLOC's pass-1 flags of a dense [G,G,G] field: uint8 [nb,nb,nb] (x, y, z), bit 0 = the block holds a negative
+    value, bit 1 = a non-negative one."""
+    f = torch.as_tensor(field)
+    G = f.shape[0]
+    nb = -(-G // BLOCK)
+    neg = torch.zeros((nb * BLOCK,) * 3, dtype=torch.bool, device=f.device)
+    pos = torch.zeros_like(neg)
+    neg[:G, :G, :G] = f < 0
+    pos[:G, :G, :G] = f >= 0
+    blk = lambda m: m.reshape(nb, BLOCK, nb, BLOCK, nb, BLOCK).permute(0, 2, 4, 1, 3, 5).reshape(nb, nb, nb, -1).any(-1)
+    return blk(neg).to(torch.uint8) + 2 * blk(pos).to(torch.uint8)
+
+
+def alloc_set_host(flags):
+    """UNB_ALLOC on the host: bool [nb,nb,nb] of the allocated blocks for flags uint8 [nb,nb,nb] (x, y, z)."""
+    f = np.asarray(flags.cpu() if torch.is_tensor(flags) else flags, dtype=np.uint8)
+    nx, ny, nz = f.shape
+    pad = np.zeros((nx + 1, ny + 1, nz + 1), np.uint8)
+    pad[:nx, :ny, :nz] = f
+    union = np.zeros_like(f)
+    for o in range(8):
+        ox, oy, oz = o & 1, (o >> 1) & 1, o >> 2
+        union |= pad[ox:ox + nx, oy:oy + ny, oz:oz + nz]
+    anchor = np.zeros((nx + 1, ny + 1, nz + 1), bool)
+    anchor[1:, 1:, 1:] = union == 3
+    alloc = np.zeros(f.shape, bool)
+    for o in range(8):
+        ox, oy, oz = o & 1, (o >> 1) & 1, o >> 2
+        alloc |= anchor[1 - ox:1 - ox + nx, 1 - oy:1 - oy + ny, 1 - oz:1 - oz + nz]
+    return alloc
+
+
+def _lattice_volume(resolution, crop, device):
+    _, nb = lattice_size(resolution, crop)
+    return TSDFVolume(1.0, 1.0, ([0, 0, 0], [nb, nb, nb]), device=device)
+
+
+def _alloc(vol, resolution, crop, flags):
+    """gsr_unb_alloc + pool growth: the one read-back of the extraction."""
+    with torch.cuda.device(vol.device):
+        _lib.check(_lib.lib().gsr_unb_alloc(C.byref(vol._v), int(resolution), int(crop), C.c_void_p(flags.data_ptr()),
+                                            _stream(vol.device)))
+    vol._grow_pool(vol.n_alloc)
+
+
+@torch.no_grad()
+def block_flags(views, center, radius, R, resolution, crop, device=None):
+    """Pass 1 (gsr_unb_block_flags): uint8 [nb^3] device tensor, x fastest."""
+    dev = views.device if isinstance(views, ViewTable) else torch.device(device if device is not None else views[0][1].device)
+    tab = _table(views, dev)
+    _, nb = lattice_size(resolution, crop)
+    flags = torch.empty(nb ** 3, dtype=torch.uint8, device=dev)
+    cen, rad, trunc = _frame(center, radius, 2.0 * float(radius) / int(resolution))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().gsr_unb_block_flags(tab.ptr, tab.n, float(R), int(resolution), int(crop), cen, rad, trunc,
+                                                  C.c_void_p(flags.data_ptr()), _stream(dev)))
+    return flags
+
+
+@torch.no_grad()
+def sparse_volume(views, center, radius, R, resolution, crop, device=None, timer=None):
+    """The two passes of UNB_ALLOC: a TSDFVolume (voxel_size 1, block AABB [0, nb)^3) holding the field of the blocks around
+    its sign changes.  timer(name): called after each stage (scripts/mesh_bench.py)."""
+    dev = views.device if isinstance(views, ViewTable) else torch.device(device if device is not None else views[0][1].device)
+    tab = _table(views, dev)
+    tick = timer or (lambda name: None)
+    flags = block_flags(tab, center, radius, R, resolution, crop)
+    vol = _lattice_volume(resolution, crop, dev)
+    _alloc(vol, resolution, crop, flags)
+    tick("pass1")
+    cen, rad, trunc = _frame(center, radius, 2.0 * float(radius) / int(resolution))
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().gsr_unb_fill(C.byref(vol._v), tab.ptr, tab.n, float(R), int(resolution), int(crop), cen, rad, trunc,
+                                           _stream(dev)))
+    tick("pass2")
+    return vol
+
+
+@torch.no_grad()
+def sparse_volume_from_dense(field, resolution, crop, device):
+    """Test-only path: the same allocation (gsr_unb_alloc) with flags and pool filled from a dense [G,G,G] field instead of
+    the two evaluating passes."""
+    G, nb = lattice_size(resolution, crop)
+    f = torch.as_tensor(field, dtype=torch.float32).to(device)
+    if tuple(f.shape) != (G, G, G):
+        raise ValueError(f"field must be [{G},{G},{G}], got {list(f.shape)}")
+    flags = block_flags_of_dense(f).permute(2, 1, 0).reshape(-1).contiguous()   # x fastest
+    vol = _lattice_volume(resolution, crop, device)
+    _alloc(vol, resolution, crop, flags)
+    A = vol.n_alloc
+    pad = torch.ones((2, nb * BLOCK, nb * BLOCK, nb * BLOCK), dtype=torch.float32, device=f.device)
+    pad[1] = 0
+    pad[0, :G, :G, :G] = f
+    pad[1, :G, :G, :G] = 1
+    pad = pad.reshape(2, nb, BLOCK, nb, BLOCK, nb, BLOCK).permute(0, 5, 3, 1, 6, 4, 2).reshape(2, nb ** 3, BLOCK ** 3)
+    vol.pool[:2, :A] = pad[:, vol._slot_block()[:A].long()]
+    return vol
+
+
+@torch.no_grad()
+def finish_vertices(verts, R, resolution, crop, center, radius, max_range=32.0):
+    """UNB_VERTEX in place on device index-space vertices [n,3] (gsr_unb_finish)."""
+    cen, rad, _ = _frame(center, radius, 1.0)
+    with torch.cuda.device(verts.device):
+        _lib.check(_lib.lib().gsr_unb_finish(C.c_void_p(verts.data_ptr()), len(verts), float(R), int(resolution), int(crop), cen,
+                                             rad, float(max_range), _stream(verts.device)))
+    return verts
+
+
+def finish_vertices_host(verts, R, resolution, crop, center, radius, max_range=32.0):
+    """The CPU twin of finish_vertices (returns a new tensor)."""
+    G, _ = lattice_size(resolution, crop)
+    step = 2.0 * float(R) / (G - 1)
+    s = (-float(R) + (verts.detach().cpu().double() - 0.5) * step).float()
+    m = torch.sqrt(s[:, 0] * s[:, 0] + s[:, 1] * s[:, 1] + s[:, 2] * s[:, 2])[:, None]
+    y = torch.where(m < 1, s, (1 / (2 - m)) * (s / m))
+    cen, rad, _ = _frame(center, radius, 1.0)
+    x = y * torch.tensor(rad, dtype=torch.float32) + torch.tensor(list(cen), dtype=torch.float32)
+    return x.clamp(-float(max_range), float(max_range))
+
+
+_MC_TABLE = None
+
+
+def _mc_table():
+    """(tri_edges int [256,15], edge_corner [12], edge_axis [12]) parsed from csrc/mc_tables.h, the kernels' own table."""
+    global _MC_TABLE
+    if _MC_TABLE is None:
+        src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "mc_tables.h")).read()
+
+        def ints(name):
+            body = src[src.index(name):]
+            body = body[body.index("=") + 1:body.index(";")]
+            return np.array([int(v) for v in re.findall(r"-?\d+", body)], dtype=np.int64)
+        _MC_TABLE = (ints("mc_tri_edges[256][15]").reshape(256, 15), ints("mc_edge_corner[12]"), ints("mc_edge_axis[12]"))
+    return _MC_TABLE
+
+
+def mcubes_host(field):
+    """Marching cubes of a dense [X,Y,Z] field by the rules of gsr_mcubes_* (voxel_size 1, every weight 1), in numpy:
+    (index-space vertices f32 [V,3] at position + 0.5, triangles int32 [F,3])."""
+    tri_edges, e_corner, e_axis = _mc_table()
+    f = np.asarray(field, np.float32)
+    X, Y, Z = f.shape
+    neg = f < 0
+    case = np.zeros((X - 1, Y - 1, Z - 1), np.int64)
+    for c in range(8):
+        case |= neg[(c & 1):X - 1 + (c & 1), ((c >> 1) & 1):Y - 1 + ((c >> 1) & 1), (c >> 2):Z - 1 + (c >> 2)].astype(np.int64) << c
+    cubes = np.argwhere((case != 0) & (case != 255))
+    rows = tri_edges[case[tuple(cubes.T)]]                       # [n, 15]
+    use = rows >= 0
+    cube_of = np.repeat(np.arange(len(cubes)), 15).reshape(-1, 15)[use]
+    e = rows[use]
+    c0 = e_corner[e]
+    v = cubes[cube_of] + np.stack([c0 & 1, (c0 >> 1) & 1, c0 >> 2], 1)
+    key = ((v[:, 0] * Y + v[:, 1]) * Z + v[:, 2]) * 3 + e_axis[e]
+    uniq, inv = np.unique(key, return_inverse=True)
+    axis, lin = uniq % 3, uniq // 3
+    p0 = np.stack([lin // (Y * Z), (lin // Z) % Y, lin % Z], 1)
+    p1 = p0.copy()
+    p1[np.arange(len(p1)), axis] += 1
+    f0, f1 = np.abs(f[tuple(p0.T)]), np.abs(f[tuple(p1.T)])
+    verts = p0.astype(np.float32) + np.float32(0.5)
+    verts[np.arange(len(verts)), axis] += f0 / (f0 + f1)
+    return verts.astype(np.float32), inv.reshape(-1, 3).astype(np.int32)
+
+
+@torch.no_grad()
+def marching_cubes_contracted(views, center, radius, R, resolution, crop=512, max_range=32.0, to_host=True, device=None,
+                              timer=None):
+    """marching_cubes_with_contraction plus the colouring pass on the device: pass 1, allocation, pass 2, gsr_mcubes_*,
+    UNB_VERTEX, UNB_COLOUR.  Returns a TriangleMesh, or with to_host=False a DeviceTriangleMesh."""
+    dev = views.device if isinstance(views, ViewTable) else torch.device(device if device is not None else views[0][1].device)
+    tab = _table(views, dev)
+    tick = timer or (lambda name: None)
+    vol = sparse_volume(tab, center, radius, R, resolution, crop, timer=timer)
+    mesh = vol.extract_triangle_mesh(to_host=False)
+    tick("cubes")
+    verts = finish_vertices(mesh.vertices, R, resolution, crop, center, radius, max_range)
+    tick("finish")
+    voxel_size = 2.0 * float(radius) / int(resolution)
+    if len(verts):
+        _, rgb = unbounded_field(verts, tab, center, radius, voxel_size, contracted=False, return_rgb=True)
+    else:
+        rgb = torch.zeros_like(verts)
+    tick("colour")
+    mesh = DeviceTriangleMesh(verts, mesh.triangles, rgb)
+    return mesh.cpu() if to_host else mesh
+
+
+@torch.no_grad()
+def marching_cubes_contracted_host(views, center, radius, R, resolution, crop=512, max_range=32.0):
+    """The CPU twin: the whole lattice held densely (small resolutions only)."""
+    G, _ = lattice_size(resolution, crop)
+    field = lattice_field_host(R, resolution, crop, (0, 0, 0), (G, G, G), views, center, radius)
+    verts, tris = mcubes_host(field.numpy())
+    verts = finish_vertices_host(torch.from_numpy(verts), R, resolution, crop, center, radius, max_range)
+    voxel_size = 2.0 * float(radius) / int(resolution)
+    _, rgb = unbounded_field_host(verts, views, center, radius, voxel_size, contracted=False, return_rgb=True)
+    return TriangleMesh(verts.numpy(), tris, rgb.numpy())
+
+
+class UnboundedExtractor(GaussianExtractor):
+    """GaussianExtractor whose extract_mesh_unbounded is implemented (the base class keeps its stub)."""
+
+    def views(self):
+        return [(cam.full_proj_transform, self.depthmaps[i], self.rgbmaps[i]) for i, cam in enumerate(self.viewpoint_stack)]
+
+    @torch.no_grad()
+    def extract_mesh_unbounded(self, resolution=1024, crop=512, to_host=True):
+        """utils/mesh_utils.py:184-279.  On a CPU model the *_host twins run (and to_host is moot)."""
+        xyz = self.gaussians.get_xyz
+        voxel_size = self.radius * 2 / resolution
+        print(f"Computing sdf gird resolution {resolution} x {resolution} x {resolution}")
+        print(f"Define the voxel_size as {voxel_size}")
+        R = quantile_radius(xyz, self.center, self.radius)
+        if xyz.is_cuda:
+            return marching_cubes_contracted(self.views(), self.center, self.radius, R, resolution, crop, to_host=to_host,
+                                             device=xyz.device)
+        return marching_cubes_contracted_host(self.views(), self.center, self.radius, R, resolution, crop)

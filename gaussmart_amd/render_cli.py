@@ -7,7 +7,7 @@
 Writes MODEL/{train,test}/ours_<it>/{renders,gt,vis} and MODEL/train/ours_<it>/fuse.ply, fuse_post.ply (what the reference's
 scripts/dtu_eval_mesh.py reads).  The mesh stays on the device from marching cubes to the PLY writer (cluster filter as
 kernels); --host_post_process runs the numpy + scipy filter instead and writes the same bytes.  --unbounded and --render_path
-are not supported.
+are not supported here; `python -m gaussmart_amd.unbounded_cli` meshes unbounded scenes.
 """
 import argparse
 import os
@@ -48,7 +48,8 @@ def main(argv=None):
     ap.add_argument("--mesh_res", default=1024, type=int, help="Mesh: resolution for unbounded mesh extraction")
     args = ap.parse_args(argv)
     if args.unbounded:
-        sys.exit("render_cli: --unbounded is not supported (only the bounded TSDF mesh path is implemented)")
+        sys.exit("render_cli: --unbounded is not supported (only the bounded TSDF mesh path is implemented here); "
+                 "`python -m gaussmart_amd.unbounded_cli` with the same arguments meshes an unbounded scene")
     if args.render_path:
         sys.exit("render_cli: --render_path (trajectory videos) is not supported")
     print("Rendering " + args.model_path)

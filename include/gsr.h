@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 13  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
+#define GSR_ABI_VERSION 14  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
                                 6: gsr_surface_maps_forward / _backward;
                                 7: TSDF fusion and marching cubes (GsrTsdfVolume, gsr_tsdf_*, gsr_mcubes_*);
                                 8: mesh post-processing (gsr_mesh_*) and gsr_depth_aabb;
@@ -43,7 +43,8 @@ extern "C" {
                                 11: DTU mesh evaluation (gsr_mesh_sample_*, gsr_points_*, gsr_dist_mean);
                                 12: Tanks-and-Temples mesh evaluation (gsr_mesh_face_centres, gsr_points_transform / _crop_polygon /
                                     _voxel_*, gsr_icp_sums, gsr_dist_score);
-                                13: segment-aware initialisation of the point cloud (GsrSegView, gsr_seg_*) */
+                                13: segment-aware initialisation of the point cloud (GsrSegView, gsr_seg_*);
+                                14: unbounded mesh export (GsrUnbView, gsr_unb_*) */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -927,6 +928,74 @@ int32_t gsr_seg_stats(const float* points, const float* colors, const int64_t* o
 int32_t gsr_seg_augment_emit(const float* eps, const int64_t* offsets, int32_t n_segs, const float* mean, const float* tril,
                              const float* mean_color, const int64_t* labels, int64_t total, float* out_xyz, float* out_color,
                              int64_t* out_label, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- unbounded mesh export
+ * The reference's GaussianExtractor.extract_mesh_unbounded (utils/mesh_utils.py:184-279) and marching_cubes_with_contraction
+ * (utils/mcube_utils.py:17-95) as kernels (unbounded.hip; Python: gaussmart_amd/mesh_unbounded.py).  A TSDF field is
+ * evaluated on a lattice in contracted space against every view, meshed with gsr_mcubes_*, and the vertices are taken back
+ * to the world.  Rules, each in one named place of unbounded.hip (fp32 unless said otherwise; the object is built without
+ * fused multiply-adds so that every kernel that runs the shared body rounds alike):
+ *   UNB_LATTICE   resolution % crop == 0, n = resolution / crop: the reference's n^3 crops of `crop` points share their
+ *                 boundary planes, so they are ONE lattice of G = n (crop - 1) + 1 points per axis; point g sits at
+ *                 s = -R + g (2R / (G - 1)), formed in fp64 and rounded to fp32.
+ *   UNB_CONTRACT  m = |s| (Euclidean norm of the 3-vector); y = s if m < 1, else (1 / (2 - m)) * (s / m); world point
+ *                 x = y radius + center.  For m >= 2 the rule is whatever this arithmetic gives (m > 2: a mirrored point,
+ *                 m == 2: a non-finite point that no view accepts); no special case.
+ *   UNB_TRUNC     trunc = 5 voxel_size (voxel_size = 2 radius / resolution, rounded once to f32 by the caller), times
+ *                 1 / (2 - min(m, 1.9)) where m > 1; for points given in world space (contracted = 0) the plain constant.
+ *   UNB_PROJECT   p = [x, 1] @ full_proj_transform, z = p.w, (u, v) = p.xy / z; accepted when -1 < u < 1, -1 < v < 1 and
+ *                 z > 0, all strict (a NaN fails them).
+ *   UNB_SAMPLE    grid_sample(bilinear, padding_mode = border, align_corners = True): pixel coordinate (u + 1) / 2 (W - 1),
+ *                 clamped to [0, W - 1]; taps nw, ne, sw, se with clamped indices, summed in that order.
+ *   UNB_FUSE      views in table order: sdf = d - z, accepted further only if sdf > -trunc; t = clamp(sdf / trunc, -1, 1);
+ *                 tsdf = (tsdf w + t) / (w + 1), rgb = (rgb w + c) / (w + 1), w += 1.  Start: tsdf = 1, rgb = 0, w = 1 (the
+ *                 reference's start; it dims colours by n / (n + 1)).
+ *   UNB_ALLOC     the lattice is cut in 16^3 blocks (block b holds lattice points [16 b, 16 b + 16), points beyond G - 1 do
+ *                 not exist).  Pass 1 keeps two flags per block: bit 0 = has a negative value, bit 1 = has a non-negative
+ *                 one.  Block a is an ANCHOR when the union of the flags over a + {0,1}^3 has both bits; the allocated set
+ *                 is the anchors dilated by + {0,1}^3 (every corner of every cube that starts in an anchor).  Slots are
+ *                 handed out in grid order by a scan.  Pass 2 evaluates the allocated blocks again, into the pool, with
+ *                 weight 1 on the lattice and 0 beyond it.
+ *   UNB_VERTEX    gsr_mcubes_* run on that volume with voxel_size 1, so a vertex arrives as (lattice position + 0.5) per
+ *                 axis; s = -R + (p - 0.5) (2R / (G - 1)) in fp64, rounded to fp32, then UNB_CONTRACT's inverse, times
+ *                 radius plus center, clipped to +-max_range.
+ *   UNB_COLOUR    vertex colours are the rgb of gsr_unb_points(vertices, contracted = 0), on the 0..1 scale.
+ *
+ * GsrUnbView: one record per view in a DEVICE table (read with uniform loads); col_x / col_y / col_w = columns 0, 1 and 3 of
+ * the row-major full_proj_transform; depth f32 [H,W] and rgb f32 [3,H,W] on the device; sizes may differ between views.
+ * The table's contents are the caller's contract (the library cannot read them on the host).
+ *
+ *   gsr_unb_lattice_size : G and ceil(G / 16) of (resolution, crop).  Host only.
+ *   gsr_unb_points       : points device f32 [n,3] (contracted samples, or world points with contracted = 0); tsdf_out f32 [n];
+ *                          rgb_out f32 [n,3] or NULL.  n == 0 launches nothing.
+ *   gsr_unb_lattice_box  : the field of lattice points lo + [0, dims) as dense f32 [dims0, dims1, dims2] (z fastest).
+ *   gsr_unb_block_flags  : pass 1; flags device u8 [ceil(G/16)^3], x fastest.  One byte per block, no atomics.
+ *   gsr_unb_alloc        : UNB_ALLOC on a volume whose block AABB is [0, ceil(G/16))^3: fills block_index and the slot map,
+ *                          sets vol->n_alloc.  ONE stream synchronisation (reads the count back).
+ *   gsr_unb_fill         : pass 2 into vol->pool (planes tsdf and weight; the colour planes are not written).
+ *   gsr_unb_finish       : UNB_VERTEX in place on device f32 [n,3].
+ * No entry but gsr_unb_alloc synchronises.  A null table, n_views <= 0, resolution % crop != 0, an empty or out-of-lattice
+ * box, a non-positive radius / trunc / R: GSR_E_INVALID before anything touches the device.  No floating-point atomics: the
+ * results are the same bits on every run. */
+typedef struct GsrUnbView {
+    float col_x[4], col_y[4], col_w[4];
+    const float* depth;
+    const float* rgb;
+    int32_t height, width;
+} GsrUnbView;
+int32_t gsr_unb_lattice_size(int32_t resolution, int32_t crop, int32_t* G, int32_t* blocks_per_axis);
+int32_t gsr_unb_points(const GsrUnbView* views, int32_t n_views, const float* points, int64_t n, const float* center_host,
+                       float radius, float trunc, int32_t contracted, float* tsdf_out, float* rgb_out, gsr_stream_t stream);
+int32_t gsr_unb_lattice_box(const GsrUnbView* views, int32_t n_views, double R, int32_t resolution, int32_t crop,
+                            const int32_t* lo_host, const int32_t* dims_host, const float* center_host, float radius, float trunc,
+                            float* out, gsr_stream_t stream);
+int32_t gsr_unb_block_flags(const GsrUnbView* views, int32_t n_views, double R, int32_t resolution, int32_t crop,
+                            const float* center_host, float radius, float trunc, uint8_t* flags, gsr_stream_t stream);
+int32_t gsr_unb_alloc(GsrTsdfVolume* vol, int32_t resolution, int32_t crop, const uint8_t* flags, gsr_stream_t stream);
+int32_t gsr_unb_fill(const GsrTsdfVolume* vol, const GsrUnbView* views, int32_t n_views, double R, int32_t resolution,
+                     int32_t crop, const float* center_host, float radius, float trunc, gsr_stream_t stream);
+int32_t gsr_unb_finish(float* verts, int64_t n, double R, int32_t resolution, int32_t crop, const float* center_host,
+                       float radius, float max_range, gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only

@@ -21,6 +21,15 @@ this comparison: the numpy path is far too slow at this size.
     python scripts/mesh_bench.py --vis
     python scripts/mesh_bench.py --eval
     python scripts/mesh_bench.py --tnt
+    python scripts/mesh_bench.py --unbounded [--mesh_res 1024] [--mesh_crop 512]
+
+With --unbounded nothing of the above runs: a ground plane z = -1 is added under the sphere so that the field leaves the unit
+ball, and the unbounded mesh export (gaussmart_amd.mesh_unbounded) is timed per stage on the device (pass 1 with the
+allocation, pass 2, marching cubes, vertex finishing, colouring) at --mesh_res.  The same field is then evaluated on the same
+GPU in the shape the reference computes it (utils/mesh_utils.py:197-248, utils/mcube_utils.py:42-68): per crop a
+torch.linspace lattice, 256^3 chunks, one pass per view over state in memory, torch.nn.functional.grid_sample -- with the maps
+already on the device, which favours it.  The reference's marching cubes run on the host (scikit-image) and are not part of
+that figure.  One JSON line goes to --unbounded_out (default profiles/unbounded_mesh_bench.json).
 
 With --eval the post-processed mesh is scored like a DTU scan (gaussmart_amd.mesh_eval: sampling, shuffle, greedy down-sampling,
 ObsMask and plane filters, the two nearest-neighbour searches, the means) against a ground-truth cloud sampled from the analytic
@@ -84,7 +93,20 @@ def main():
     ap.add_argument("--tnt_tau", type=float, default=0.004, help="distance threshold in scene units (the voxel size)")
     ap.add_argument("--tnt_gt_points", type=int, default=1_000_000)
     ap.add_argument("--tnt_out", type=str, default=os.path.join(ROOT, "profiles", "r10_tnt_eval_bench.json"))
+    ap.add_argument("--unbounded", action="store_true", help="time the unbounded mesh export instead (sphere on a ground plane)")
+    ap.add_argument("--mesh_res", type=int, default=1024)
+    ap.add_argument("--mesh_crop", type=int, default=512)
+    ap.add_argument("--torch_res", type=int, default=-1, help="resolution of the reference-shaped torch run (-1: --mesh_res)")
+    ap.add_argument("--unbounded_out", type=str, default=os.path.join(ROOT, "profiles", "unbounded_mesh_bench.json"))
     args = ap.parse_args()
+    if args.unbounded:
+        ub = unbounded_bench(args)
+        print(json.dumps(ub))
+        if args.unbounded_out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.unbounded_out)), exist_ok=True)
+            with open(args.unbounded_out, "w") as f:
+                f.write(json.dumps(ub) + "\n")
+        return
     from gaussmart_amd.camera import look_at_camera
     from gaussmart_amd.gaussian_model import GaussianModel
     from gaussmart_amd.gaussian_renderer import render
@@ -185,6 +207,132 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(args.tnt_out)), exist_ok=True)
             with open(args.tnt_out, "w") as f:
                 f.write(json.dumps(tn) + "\n")
+
+
+def surfel_params(p, normals, spacing):
+    """Flat surfels at p [n,3] facing normals [n,3], grey, nearly opaque (create_from_params' dictionary)."""
+    n = len(p)
+    z = np.array([0.0, 0.0, 1.0])
+    axis = np.cross(z, normals)
+    s = np.linalg.norm(axis, axis=1, keepdims=True)
+    ang = np.arctan2(s[:, 0], normals @ z)
+    axis = np.where(s > 1e-9, axis / np.maximum(s, 1e-12), np.array([1.0, 0, 0]))
+    q = np.concatenate([np.cos(ang / 2)[:, None], axis * np.sin(ang / 2)[:, None]], 1)
+    return dict(xyz=torch.tensor(p), features_dc=torch.zeros(n, 1, 3), features_rest=torch.zeros(n, 15, 3),
+                scaling=torch.full((n, 2), math.log(0.8 * spacing)), rotation=torch.tensor(q),
+                opacity=torch.full((n, 1), math.log(0.99 / 0.01)))
+
+
+def torch_reference_field(views, center, radius, R, resolution, crop, dev):
+    """The reference's formulation of the field on the device: per crop torch.linspace, 256^3 chunks, one pass per view,
+    grid_sample.  Returns (points evaluated, negative values found)."""
+    import torch.nn.functional as F
+    n = resolution // crop
+    xs = np.linspace(-R, R, n + 1)
+    voxel = 2 * radius / resolution
+    cen = torch.as_tensor(center, dtype=torch.float32, device=dev)
+    total = neg = 0
+    for i in range(n):
+        for j in range(n):
+            for k in range(n):
+                x, y, z = (torch.linspace(xs[a], xs[a + 1], crop, device=dev) for a in (i, j, k))
+                pts = torch.stack(torch.meshgrid(x, y, z, indexing="ij"), -1).reshape(-1, 3)
+                for samples in torch.split(pts, 256 ** 3, dim=0):
+                    m = torch.linalg.norm(samples, dim=-1)
+                    trunc = 5 * voxel * torch.ones_like(samples[:, 0])
+                    mask = m > 1
+                    trunc[mask] *= 1 / (2 - m[mask].clamp(max=1.9))
+                    mag = m[:, None]
+                    w_pts = torch.where(mag < 1, samples, (1 / (2 - mag)) * (samples / mag)) * radius + cen
+                    tsdf = torch.ones_like(samples[:, 0])
+                    wgt = torch.ones_like(samples[:, 0])
+                    hom = torch.cat([w_pts, torch.ones_like(w_pts[:, :1])], -1)
+                    for M, depth, _ in views:
+                        p = hom @ M
+                        zc = p[:, -1:]
+                        pix = p[:, :2] / zc
+                        ok = ((pix > -1.0) & (pix < 1.0) & (zc > 0)).all(-1)
+                        d = F.grid_sample(depth[None], pix[None, None], mode="bilinear", padding_mode="border",
+                                          align_corners=True).reshape(-1)
+                        sdf = d - zc[:, 0]
+                        ok = ok & (sdf > -trunc)
+                        t = torch.clamp(sdf / trunc, min=-1.0, max=1.0)[ok]
+                        w = wgt[ok]
+                        tsdf[ok] = (tsdf[ok] * w + t) / (w + 1)
+                        wgt[ok] = w + 1
+                    total += len(samples)
+                    neg += int((tsdf < 0).sum())
+    return total, neg
+
+
+def unbounded_bench(args):
+    from gaussmart_amd import mesh_unbounded as MU
+    from gaussmart_amd.camera import look_at_camera
+    from gaussmart_amd.gaussian_model import GaussianModel
+    from gaussmart_amd.gaussian_renderer import render
+    from gaussmart_amd.params import PipelineParams
+    dev = torch.device("cuda", 0)
+    sync = torch.cuda.synchronize
+    n = args.surfels
+    p = fib(n)
+    sp = math.sqrt(4 * math.pi / n)
+    half = 6.0
+    fstep = 2 * half / math.ceil(2 * half / sp / 4)          # the plane is seen from further away: four times the spacing
+    gx, gy = np.meshgrid(np.arange(-half, half + 1e-9, fstep), np.arange(-half, half + 1e-9, fstep))
+    fl = np.stack([gx.ravel(), gy.ravel(), np.full(gx.size, -1.0)], 1)
+    a, b = surfel_params(p, p, sp), surfel_params(fl, np.tile([0.0, 0.0, 1.0], (len(fl), 1)), fstep)
+    g = GaussianModel(3, device=dev)
+    g.create_from_params({k: torch.cat([a[k], b[k]]).float().to(dev).contiguous() for k in a})
+    g.active_sh_degree = 0
+    dirs = fib(2 * args.views)
+    dirs = dirs[dirs[:, 2] > 0][:args.views]
+    cams = [look_at_camera(2.5 * d, (0, 0, 0), (0, 0, 1) if abs(d[2]) < 0.95 else (0, 1, 0), math.radians(50), args.width,
+                           args.height, device=dev, uid=i) for i, d in enumerate(dirs)]
+    ex = MU.UnboundedExtractor(g, render, PipelineParams(depth_ratio=1.0), bg_color=[0, 0, 0])
+    with contextlib.redirect_stdout(io.StringIO()):
+        ex.reconstruction(cams)
+    R = MU.quantile_radius(g.get_xyz, ex.center, ex.radius)
+    views = ex.views()
+    res, crop = args.mesh_res, args.mesh_crop
+    G, nb = MU.lattice_size(res, crop)
+    runs = []
+    for rep in range(max(args.repeats, 2)):
+        stages, last = {}, [0.0]
+
+        def tick(name):
+            sync()
+            now = time.perf_counter()
+            stages[name + "_ms"] = 1e3 * (now - last[0])
+            last[0] = now
+        sync()
+        last[0] = t0 = time.perf_counter()
+        tab = MU.ViewTable(views, dev)
+        mesh = MU.marching_cubes_contracted(tab, ex.center, ex.radius, R, res, crop, to_host=False, timer=tick)
+        sync()
+        stages["total_ms"] = 1e3 * (time.perf_counter() - t0)
+        runs.append(stages)
+        if rep:
+            assert torch.equal(mesh.vertices, first), "the vertices differ between two runs"
+        first = mesh.vertices
+    best = {k: min(r[k] for r in runs[1:]) for k in runs[0]}
+    flags = MU.block_flags(tab, ex.center, ex.radius, R, res, crop)
+    n_alloc = int(MU.alloc_set_host(flags.cpu().reshape(nb, nb, nb).permute(2, 1, 0)).sum())
+    tres = args.mesh_res if args.torch_res < 0 else args.torch_res
+    tviews = [(M.to(dev), d.float(), c) for M, d, c in views]
+    sync(); t0 = time.perf_counter()
+    tpoints, tneg = torch_reference_field(tviews, ex.center, ex.radius, R, tres, crop, dev)
+    sync(); torch_ms = 1e3 * (time.perf_counter() - t0)
+    dev_field_ms = best["pass1_ms"] + best["pass2_ms"]
+    out = {"surfels": len(p), "plane_surfels": len(fl), "views": len(cams), "width": args.width, "height": args.height,
+           "mesh_res": res, "mesh_crop": crop, "R": R, "radius": ex.radius, "lattice_points_per_axis": G,
+           "lattice_blocks": nb ** 3, "allocated_blocks": n_alloc, "vertices": len(mesh.vertices),
+           "triangles": len(mesh.triangles), "device_ms": best, "device_first_run_ms": runs[0],
+           "device_field_ms": dev_field_ms, "device_lattice_points": G ** 3,
+           "torch_reference_res": tres, "torch_reference_points": tpoints, "torch_reference_negative_points": tneg,
+           "torch_reference_field_ms": torch_ms}
+    if tres == res:
+        out["field_speedup_vs_torch_reference"] = torch_ms / dev_field_ms
+    return out
 
 
 def tnt_bench(args, dpost, dev):
