@@ -8,7 +8,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _dev, _lib
 
 MAX_TENSORS = 24
 
@@ -29,8 +29,8 @@ def compact_rows(tensors, keep):
     keep = keep.contiguous()
     out = []
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        ws = torch.empty(L.gsr_compact_workspace_bytes(n), dtype=torch.uint8, device=dev)
+        stream = _dev.stream(dev)
+        ws = _dev.workspace(L.gsr_compact_workspace_bytes(n), dev)
         offsets = C.c_void_p()
         _lib.check(L.gsr_compact_plan(C.c_void_p(keep.data_ptr()), n, C.c_void_p(ws.data_ptr()), ws.numel(),
                                       C.byref(offsets), stream))

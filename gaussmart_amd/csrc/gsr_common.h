@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <float.h>
 #include "../../include/gsr.h"
 #include "gsr_constants.h"
 
@@ -67,6 +68,40 @@ struct GsrProfileScope {
 #define GSR_GR_XY 16
 
 static inline size_t gsr_align(size_t x) { return (x + 255) & ~size_t(255); }
+
+// Cursor over a workspace: take<T>(bytes) returns the next region (NULL when the base is NULL: a layout is also computed
+// without memory, for its size) and advances by the 256-byte-aligned size; `off` ends as the layout's total.
+struct GsrWsCursor {
+    char* base;
+    size_t off;
+    explicit GsrWsCursor(void* b) : base(static_cast<char*>(b)), off(0) {}
+    template <class T = void> T* take(size_t bytes) {
+        char* q = base ? base + off : nullptr;
+        off += gsr_align(bytes);
+        return reinterpret_cast<T*>(q);
+    }
+};
+
+// ---------------------------------------------------------------- argument checks of the point-cloud and mesh entry points
+static inline int gsr_check_count(const char* name, int64_t n) {
+    if (n < 0) { gsr_set_error("%s must be >= 0 (got %lld)", name, (long long)n); return GSR_E_INVALID; }
+    if (n > 0x7fffffffLL) { gsr_set_error("%s %lld exceeds int32 indices", name, (long long)n); return GSR_E_UNSUPPORTED; }
+    return GSR_OK;
+}
+static inline int gsr_check_positive(const char* name, double v) {
+    if (!(v > 0.0) || !(v <= DBL_MAX)) { gsr_set_error("%s must be > 0 and finite (got %g)", name, v); return GSR_E_INVALID; }
+    return GSR_OK;
+}
+// tris_message: the text for n_tris > max_tris, with one %lld (the cap is the scan's in the culls, the edge sort's in mesh_post)
+#define GSR_TRIS_EXCEED_SCAN "n_tris %lld exceeds the scan's 2^31 - 1 elements"
+static inline int gsr_check_mesh_counts(int64_t n_tris, int64_t n_verts, int64_t max_tris = 0x7fffffffLL,
+                                        const char* tris_message = GSR_TRIS_EXCEED_SCAN) {
+    if (n_tris < 0) { gsr_set_error("n_tris must be >= 0 (got %lld)", (long long)n_tris); return GSR_E_INVALID; }
+    if (n_verts < 0) { gsr_set_error("n_verts must be >= 0 (got %lld)", (long long)n_verts); return GSR_E_INVALID; }
+    if (n_verts > 0x7fffffffLL) { gsr_set_error("n_verts %lld exceeds int32 vertex indices", (long long)n_verts); return GSR_E_UNSUPPORTED; }
+    if (n_tris > max_tris) { gsr_set_error(tris_message, (long long)n_tris); return GSR_E_UNSUPPORTED; }
+    return GSR_OK;
+}
 
 struct GsrGeomLayout {
     size_t splat, clamped, tiles_touched, tile_rect, depth_key, order, offs, color_jac, total;

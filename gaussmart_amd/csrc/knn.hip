@@ -3,72 +3,11 @@
 // >= 1e-7 and takes log(sqrt(.)) as the initial log-scale).  [U] algorithm outline: Morton-order
 // the points, bound 1024-point boxes, seed the 3 best with the +-3 Morton neighbours, then visit
 // only boxes closer than the current 3rd best.  The result is the exact 3-NN, so it is checked
-// against scipy.spatial.cKDTree in tests/test_knn.py.
-#include "gsr_common.h"
-#include <cfloat>
+// against scipy.spatial.cKDTree in tests/test_gpu_sort_knn.py.
+#include "cloud_common.h"
 
 #define KNN_BOX 1024
 #define KNN_BLOCK 256
-
-__device__ __forceinline__ uint32_t f2ord(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t u) {
-    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
-}
-
-__global__ void __launch_bounds__(KNN_BLOCK) knn_bounds_kernel(const float* __restrict__ xyz, int n,
-                                                               uint32_t* __restrict__ mm /*[6]*/) {
-    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (int i = blockIdx.x * KNN_BLOCK + threadIdx.x; i < n; i += gridDim.x * KNN_BLOCK) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float v = xyz[3 * (size_t)i + a];
-            lo[a] = fminf(lo[a], v); hi[a] = fmaxf(hi[a], v);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            lo[a] = fminf(lo[a], __shfl_xor(lo[a], d, 64));
-            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], d, 64));
-        }
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            atomicMin(&mm[a], f2ord(lo[a]));
-            atomicMax(&mm[3 + a], f2ord(hi[a]));
-        }
-    }
-}
-
-__device__ __forceinline__ uint32_t spread10(uint32_t x) {
-    x = (x | (x << 16)) & 0x030000FFu;
-    x = (x | (x << 8)) & 0x0300F00Fu;
-    x = (x | (x << 4)) & 0x030C30C3u;
-    x = (x | (x << 2)) & 0x09249249u;
-    return x;
-}
-
-__global__ void __launch_bounds__(KNN_BLOCK) knn_morton_kernel(const float* __restrict__ xyz, int n,
-                                                               const uint32_t* __restrict__ mm,
-                                                               uint32_t* __restrict__ codes) {
-    const int i = blockIdx.x * KNN_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    uint32_t c = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float lo = ord2f(mm[a]), hi = ord2f(mm[3 + a]);
-        const float ext = hi - lo;
-        const float rel = ext > 0.f ? (xyz[3 * (size_t)i + a] - lo) / ext : 0.f;
-        const uint32_t q = (uint32_t)fminf(fmaxf(rel * 1023.0f, 0.f), 1023.f);
-        c |= spread10(q) << a;
-    }
-    codes[i] = c;
-}
 
 // gather the points into Morton order (float4 for 16-byte loads) and bound each 1024-point box
 __global__ void __launch_bounds__(KNN_BLOCK) knn_boxes_kernel(const float* __restrict__ xyz, int n,
@@ -90,11 +29,7 @@ __global__ void __launch_bounds__(KNN_BLOCK) knn_boxes_kernel(const float* __res
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            lo[a] = fminf(lo[a], __shfl_xor(lo[a], d, 64));
-            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], d, 64));
-        }
+        lo[a] = wave_min_f32(lo[a]); hi[a] = wave_max_f32(hi[a]);
         if ((threadIdx.x & 63) == 0) { s_lo[a][threadIdx.x >> 6] = lo[a]; s_hi[a][threadIdx.x >> 6] = hi[a]; }
     }
     __syncthreads();
@@ -188,13 +123,11 @@ extern "C" int32_t gsr_knn3(const float* xyz, int32_t n, float* out, void* ws, s
     const int nbox = (n + KNN_BOX - 1) / KNN_BOX;
 
     GsrProfileScope prof(GSR_K_KNN, s);
-    GSR_HIP_CHECK(hipMemsetAsync(mm, 0xFF, 12, s));
-    GSR_HIP_CHECK(hipMemsetAsync(mm + 3, 0x00, 12, s));
-    const int rb = min(1024, (n + KNN_BLOCK - 1) / KNN_BLOCK);
-    hipLaunchKernelGGL(knn_bounds_kernel, dim3(rb), dim3(KNN_BLOCK), 0, s, xyz, n, mm);
-    hipLaunchKernelGGL(knn_morton_kernel, dim3((n + KNN_BLOCK - 1) / KNN_BLOCK), dim3(KNN_BLOCK), 0, s, xyz, n, mm, codes);
+    int rc = cloud_bounds<true>(xyz, n, mm, s);
+    if (rc != GSR_OK) return rc;
+    hipLaunchKernelGGL(cloud_morton_kernel, dim3((n + KNN_BLOCK - 1) / KNN_BLOCK), dim3(KNN_BLOCK), 0, s, xyz, (int64_t)n, mm, codes);
     GSR_LAUNCH_CHECK();
-    int rc = gsr_radix_sort_pairs(codes, nullptr, sorted_codes, order, reinterpret_cast<uint32_t*>(w + okt),
+    rc = gsr_radix_sort_pairs(codes, nullptr, sorted_codes, order, reinterpret_cast<uint32_t*>(w + okt),
                                   reinterpret_cast<uint32_t*>(w + ovt), n, 0, 30, w + osw, s);
     if (rc != GSR_OK) return rc;
     hipLaunchKernelGGL(knn_boxes_kernel, dim3(nbox), dim3(KNN_BLOCK), 0, s, xyz, n, order, pts, boxes);

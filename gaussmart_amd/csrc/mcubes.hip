@@ -31,17 +31,15 @@ struct McWs {
 
 static McWs mc_ws_layout(void* base, int64_t A) {
     McWs w{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += tsdf_align(bytes); return q; };
-    w.totals = reinterpret_cast<unsigned long long*>(take(64 * 4));
-    w.code = reinterpret_cast<uint16_t*>(take(A * TSDF_BV * 2));
-    w.edges = reinterpret_cast<uint8_t*>(take(A * TSDF_BV));
-    w.vert_off = reinterpret_cast<uint32_t*>(take(A * TSDF_BV * 4));
-    w.counts = reinterpret_cast<uint32_t*>(take(2 * A * 4));
-    w.scans = reinterpret_cast<uint32_t*>(take(2 * (A + 1) * 4));
-    w.partial = reinterpret_cast<uint32_t*>(take(2 * scan_tiles(A) * 4 + 4));
-    w.bytes = off;
+    GsrWsCursor c(base);
+    w.totals = c.take<unsigned long long>(64 * 4);
+    w.code = c.take<uint16_t>(A * TSDF_BV * 2);
+    w.edges = c.take<uint8_t>(A * TSDF_BV);
+    w.vert_off = c.take<uint32_t>(A * TSDF_BV * 4);
+    w.counts = c.take<uint32_t>(2 * A * 4);
+    w.scans = c.take<uint32_t>(2 * (A + 1) * 4);
+    w.partial = c.take<uint32_t>(2 * scan_tiles(A) * 4 + 4);
+    w.bytes = c.off;
     return w;
 }
 

@@ -160,18 +160,16 @@ struct McWs {
 
 static McWs mc_layout(void* base, int64_t F, int64_t V, int32_t n_views) {
     McWs w{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += gsr_align(bytes); return q; };
+    GsrWsCursor c(base);
     const size_t f = size_t(F > 0 ? F : 1), v = size_t(V > 0 ? V : 1);
-    w.keep = reinterpret_cast<uint8_t*>(take(v));
-    w.emit = reinterpret_cast<uint8_t*>(take(f));
-    w.vert_off = reinterpret_cast<uint32_t*>(take((v + 1) * 4));
-    w.tri_off = reinterpret_cast<uint32_t*>(take((f + 1) * 4));
-    w.scan_ws = take(gsr_scan_workspace_bytes((int64_t)(v > f ? v : f)));
-    w.bytes_emit = off;
-    w.proj = reinterpret_cast<float*>(take(size_t(n_views > 0 ? n_views : 1) * 12 * 4));
-    w.bytes = off;
+    w.keep = c.take<uint8_t>(v);
+    w.emit = c.take<uint8_t>(f);
+    w.vert_off = c.take<uint32_t>((v + 1) * 4);
+    w.tri_off = c.take<uint32_t>((f + 1) * 4);
+    w.scan_ws = c.take(gsr_scan_workspace_bytes((int64_t)(v > f ? v : f)));
+    w.bytes_emit = c.off;
+    w.proj = c.take<float>(size_t(n_views > 0 ? n_views : 1) * 12 * 4);
+    w.bytes = c.off;
     return w;
 }
 
@@ -225,20 +223,6 @@ __global__ void __launch_bounds__(256) mc_emit_verts_kernel(const float* __restr
     out[3 * (int64_t)off[v] + k] = fmaf(verts[i], s, k == 0 ? tx : k == 1 ? ty : tz);
 }
 
-static int mc_check_counts(int64_t n_tris, int64_t n_verts) {
-    if (n_tris < 0) { gsr_set_error("n_tris must be >= 0 (got %lld)", (long long)n_tris); return GSR_E_INVALID; }
-    if (n_verts < 0) { gsr_set_error("n_verts must be >= 0 (got %lld)", (long long)n_verts); return GSR_E_INVALID; }
-    if (n_verts > 0x7fffffffLL) {
-        gsr_set_error("n_verts %lld exceeds int32 vertex indices", (long long)n_verts);
-        return GSR_E_UNSUPPORTED;
-    }
-    if (n_tris > 0x7fffffffLL) {
-        gsr_set_error("n_tris %lld exceeds the scan's 2^31 - 1 elements", (long long)n_tris);
-        return GSR_E_UNSUPPORTED;
-    }
-    return GSR_OK;
-}
-
 extern "C" size_t gsr_mesh_cull_workspace_bytes(int64_t n_tris, int64_t n_verts, int32_t n_views) {
     return mc_layout(nullptr, n_tris, n_verts, n_views).bytes;
 }
@@ -249,7 +233,7 @@ extern "C" int32_t gsr_mesh_cull_count(const float* verts, const int32_t* tris, 
                                        int64_t* n_verts_out, int64_t* n_tris_out, gsr_stream_t stream_) {
     if (!n_verts_out || !n_tris_out) { gsr_set_error("n_verts_out / n_tris_out are required"); return GSR_E_INVALID; }
     *n_verts_out = *n_tris_out = 0;
-    int rc = mc_check_counts(n_tris, n_verts);
+    int rc = gsr_check_mesh_counts(n_tris, n_verts);
     if (rc != GSR_OK) return rc;
     if (n_views < 0) { gsr_set_error("n_views must be >= 0 (got %d)", n_views); return GSR_E_INVALID; }
     if (H < 1) { gsr_set_error("H must be >= 1 (got %d)", H); return GSR_E_INVALID; }
@@ -299,7 +283,7 @@ extern "C" int32_t gsr_mesh_cull_count(const float* verts, const int32_t* tris, 
 extern "C" int32_t gsr_mesh_cull_emit(const float* verts, const float* colors, const int32_t* tris, int64_t n_tris,
                                       int64_t n_verts, const float* scale_offset_host, void* ws, size_t ws_bytes,
                                       float* verts_out, float* colors_out, int32_t* tris_out, gsr_stream_t stream_) {
-    int rc = mc_check_counts(n_tris, n_verts);
+    int rc = gsr_check_mesh_counts(n_tris, n_verts);
     if (rc != GSR_OK) return rc;
     if (n_verts == 0) {
         if (n_tris > 0) { gsr_set_error("n_verts is 0 with n_tris %lld", (long long)n_tris); return GSR_E_INVALID; }

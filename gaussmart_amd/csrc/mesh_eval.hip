@@ -8,7 +8,7 @@
 //   me_sample_emit_kernel   one thread per triangle writes its samples behind the scan of the counts; the same set-up and
 //                           the same keep test (me_keep) as the count kernel
 //   me_gather_kernel        EVAL_ORDER: out[k] = points[perm[k]]
-//   me_bounds / me_morton / me_leaf / me_level kernels   the search structure: the searched cloud in 30-bit Morton order,
+//   cloud_bounds / cloud_morton (cloud_common.h), me_leaf / me_level kernels   the search structure: the searched cloud in 30-bit Morton order,
 //                           bounds on leaves of 64 points, nodes of 64 leaves and tops of 64 nodes
 //   me_nearest_kernel       EVAL_NN: one thread per query in the queries' own Morton order; the leaf found by a binary search
 //                           of the query's clamped code seeds the best distance, then only boxes not farther than it are opened
@@ -18,14 +18,12 @@
 //
 // Box distances are formed in fp64 from the f32 bounds with the expression of EVAL_DIST; every operation of it is monotone,
 // so a box's distance never exceeds the d^2 of a point inside it and pruning on `box > best` is exact.
-#include "gsr_common.h"
-#include <cfloat>
+#include "cloud_common.h"
 #include <cmath>
 
 #define ME_LEAF 64                   // points per leaf, leaves per node, nodes per top
 #define ME_SAMPLE_CAP 16777216.0     // n1 * n2 above 2^24: the triangle is refused
 #define ME_MIS_BATCH 8               // rounds between two read-backs of the "any undecided" word
-#define ME_MEAN_BLOCKS 1024
 
 // ---------------------------------------------------------------- EVAL_SAMPLE
 struct MeTri {
@@ -136,36 +134,23 @@ struct MeSampleWs {
 
 static MeSampleWs me_sample_layout(void* base, int64_t F) {
     MeSampleWs w{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += gsr_align(bytes); return q; };
+    GsrWsCursor c(base);
     const size_t f = size_t(F > 0 ? F : 1);
-    w.info = reinterpret_cast<unsigned long long*>(take(16));
-    w.counts = reinterpret_cast<uint32_t*>(take(f * 4));
-    w.off = reinterpret_cast<uint32_t*>(take((f + 1) * 4));
-    w.scan_ws = take(gsr_scan_workspace_bytes((int64_t)f));
-    w.bytes = off;
+    w.info = c.take<unsigned long long>(16);
+    w.counts = c.take<uint32_t>(f * 4);
+    w.off = c.take<uint32_t>((f + 1) * 4);
+    w.scan_ws = c.take(gsr_scan_workspace_bytes((int64_t)f));
+    w.bytes = c.off;
     return w;
-}
-
-static int me_check_count(const char* name, int64_t n) {
-    if (n < 0) { gsr_set_error("%s must be >= 0 (got %lld)", name, (long long)n); return GSR_E_INVALID; }
-    if (n > 0x7fffffffLL) { gsr_set_error("%s %lld exceeds int32 indices", name, (long long)n); return GSR_E_UNSUPPORTED; }
-    return GSR_OK;
-}
-
-static int me_check_thresh(double thresh) {
-    if (!(thresh > 0.0) || !(thresh <= DBL_MAX)) { gsr_set_error("thresh must be > 0 and finite (got %g)", thresh); return GSR_E_INVALID; }
-    return GSR_OK;
 }
 
 static int me_check_sample(const float* verts, const int32_t* tris, int64_t n_tris, int64_t n_verts, double thresh,
                            void* ws, size_t ws_bytes, MeSampleWs& w) {
-    int rc = me_check_count("n_tris", n_tris);
+    int rc = gsr_check_count("n_tris", n_tris);
     if (rc != GSR_OK) return rc;
-    rc = me_check_count("n_verts", n_verts);
+    rc = gsr_check_count("n_verts", n_verts);
     if (rc != GSR_OK) return rc;
-    rc = me_check_thresh(thresh);
+    rc = gsr_check_positive("thresh", thresh);
     if (rc != GSR_OK) return rc;
     if (n_verts > 0 && !verts) { gsr_set_error("verts is null with n_verts %lld", (long long)n_verts); return GSR_E_INVALID; }
     if (n_tris > 0 && !tris) { gsr_set_error("tris is null with n_tris %lld", (long long)n_tris); return GSR_E_INVALID; }
@@ -242,9 +227,9 @@ __global__ void __launch_bounds__(256) me_gather_kernel(const float* __restrict_
 
 extern "C" int32_t gsr_points_gather(const float* points, int64_t n_src, const int32_t* perm, int64_t n, float* out,
                                      gsr_stream_t stream_) {
-    int rc = me_check_count("n_src", n_src);
+    int rc = gsr_check_count("n_src", n_src);
     if (rc != GSR_OK) return rc;
-    rc = me_check_count("n", n);
+    rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
     if (n == 0) return GSR_OK;
     if (!perm || !out) { gsr_set_error("perm / out are null with n %lld", (long long)n); return GSR_E_INVALID; }
@@ -266,65 +251,6 @@ struct MeTree {
     int n, nl, nn, nt;
 };
 
-__device__ __forceinline__ uint32_t me_f2ord(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float me_ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
-
-__global__ void __launch_bounds__(256) me_bounds_kernel(const float* __restrict__ xyz, int n, uint32_t* __restrict__ mm) {
-    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float v = xyz[3 * i + a];
-            lo[a] = fminf(lo[a], v); hi[a] = fmaxf(hi[a], v);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            lo[a] = fminf(lo[a], __shfl_xor(lo[a], d, 64));
-            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], d, 64));
-        }
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            atomicMin(&mm[a], me_f2ord(lo[a]));
-            atomicMax(&mm[3 + a], me_f2ord(hi[a]));
-        }
-    }
-}
-
-__device__ __forceinline__ uint32_t me_spread10(uint32_t x) {
-    x = (x | (x << 16)) & 0x030000FFu;
-    x = (x | (x << 8)) & 0x0300F00Fu;
-    x = (x | (x << 4)) & 0x030C30C3u;
-    x = (x | (x << 2)) & 0x09249249u;
-    return x;
-}
-
-// 30-bit Morton code of a point in the bounds mm, clamped into them (queries may lie anywhere; NaN gives 0)
-__device__ __forceinline__ uint32_t me_code(const float* __restrict__ p, const uint32_t* __restrict__ mm) {
-    uint32_t c = 0;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float lo = me_ord2f(mm[a]), ext = me_ord2f(mm[3 + a]) - lo;
-        const float rel = ext > 0.f ? (p[a] - lo) / ext : 0.f;
-        const uint32_t q = (uint32_t)fminf(fmaxf(rel * 1023.0f, 0.f), 1023.f);
-        c |= me_spread10(q) << a;
-    }
-    return c;
-}
-
-__global__ void __launch_bounds__(256) me_morton_kernel(const float* __restrict__ xyz, int n, const uint32_t* __restrict__ mm,
-                                                        uint32_t* __restrict__ codes) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) codes[i] = me_code(xyz + 3 * i, mm);
-}
-
 // one wave per leaf: gathers its 64 points into Morton order and bounds them
 __global__ void __launch_bounds__(256) me_leaf_kernel(const float* __restrict__ xyz, int n, const uint32_t* __restrict__ order,
                                                       float4* __restrict__ sorted, float* __restrict__ boxes, int nl) {
@@ -339,13 +265,7 @@ __global__ void __launch_bounds__(256) me_leaf_kernel(const float* __restrict__ 
         lo[0] = hi[0] = x; lo[1] = hi[1] = y; lo[2] = hi[2] = z;
     }
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-            lo[a] = fminf(lo[a], __shfl_xor(lo[a], d, 64));
-            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], d, 64));
-        }
-    }
+    for (int a = 0; a < 3; ++a) { lo[a] = wave_min_f32(lo[a]); hi[a] = wave_max_f32(hi[a]); }
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) { boxes[6 * (int64_t)lf + a] = lo[a]; boxes[6 * (int64_t)lf + 3 + a] = hi[a]; }
@@ -508,43 +428,39 @@ struct MeSearchWs {
 
 static MeSearchWs me_search_layout(void* base, int64_t n_cloud, int64_t n_query) {
     MeSearchWs w{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += gsr_align(bytes); return q; };
+    GsrWsCursor c(base);
     const size_t n = size_t(n_cloud > 0 ? n_cloud : 1), nq = size_t(n_query > 0 ? n_query : 1), m = n > nq ? n : nq;
     w.nl = (int)((n + ME_LEAF - 1) / ME_LEAF);
     w.nn = (w.nl + ME_LEAF - 1) / ME_LEAF;
     w.nt = (w.nn + ME_LEAF - 1) / ME_LEAF;
-    w.mm = reinterpret_cast<uint32_t*>(take(32));
-    w.pending = reinterpret_cast<uint32_t*>(take(4));
-    w.codes = reinterpret_cast<uint32_t*>(take(m * 4));
-    w.codes_sorted = reinterpret_cast<uint32_t*>(take(m * 4));
-    w.order = reinterpret_cast<uint32_t*>(take(m * 4));
-    w.kt = reinterpret_cast<uint32_t*>(take(m * 4));
-    w.vt = reinterpret_cast<uint32_t*>(take(m * 4));
-    w.cloud_codes = reinterpret_cast<uint32_t*>(take(n * 4));
-    w.qorder = reinterpret_cast<uint32_t*>(take(nq * 4));
-    w.state = reinterpret_cast<int32_t*>(take(n * 4));
-    w.pts = reinterpret_cast<float4*>(take(n * 16));
-    w.leaf = reinterpret_cast<float*>(take(size_t(w.nl) * 24));
-    w.node = reinterpret_cast<float*>(take(size_t(w.nn) * 24));
-    w.top = reinterpret_cast<float*>(take(size_t(w.nt) * 24));
+    w.mm = c.take<uint32_t>(32);
+    w.pending = c.take<uint32_t>(4);
+    w.codes = c.take<uint32_t>(m * 4);
+    w.codes_sorted = c.take<uint32_t>(m * 4);
+    w.order = c.take<uint32_t>(m * 4);
+    w.kt = c.take<uint32_t>(m * 4);
+    w.vt = c.take<uint32_t>(m * 4);
+    w.cloud_codes = c.take<uint32_t>(n * 4);
+    w.qorder = c.take<uint32_t>(nq * 4);
+    w.state = c.take<int32_t>(n * 4);
+    w.pts = c.take<float4>(n * 16);
+    w.leaf = c.take<float>(size_t(w.nl) * 24);
+    w.node = c.take<float>(size_t(w.nn) * 24);
+    w.top = c.take<float>(size_t(w.nt) * 24);
     // (the sort's workspace is not monotone in n: both sorts must fit)
     const size_t sa = gsr_sort_ws_bytes((int64_t)n), sb = gsr_sort_ws_bytes((int64_t)nq);
-    w.sort_ws = take(sa > sb ? sa : sb);
-    w.bytes = off;
+    w.sort_ws = c.take(sa > sb ? sa : sb);
+    w.bytes = c.off;
     return w;
 }
 
 // builds the structure over `cloud` (n >= 1) in w; the sorted codes end up in w.cloud_codes
 static int me_build_tree(const float* cloud, int64_t n, const MeSearchWs& w, MeTree& T, hipStream_t s) {
-    GSR_HIP_CHECK(hipMemsetAsync(w.mm, 0xFF, 12, s));
-    GSR_HIP_CHECK(hipMemsetAsync(w.mm + 3, 0x00, 12, s));
-    const int nb = (int)((n + 255) / 256);
-    hipLaunchKernelGGL(me_bounds_kernel, dim3(nb < 1024 ? nb : 1024), dim3(256), 0, s, cloud, (int)n, w.mm);
-    hipLaunchKernelGGL(me_morton_kernel, dim3(nb), dim3(256), 0, s, cloud, (int)n, w.mm, w.codes);
+    int rc = cloud_bounds<true>(cloud, n, w.mm, s);
+    if (rc != GSR_OK) return rc;
+    hipLaunchKernelGGL(cloud_morton_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, cloud, n, w.mm, w.codes);
     GSR_LAUNCH_CHECK();
-    int rc = gsr_radix_sort_pairs(w.codes, nullptr, w.cloud_codes, w.order, w.kt, w.vt, n, 0, 30, w.sort_ws, s);
+    rc = gsr_radix_sort_pairs(w.codes, nullptr, w.cloud_codes, w.order, w.kt, w.vt, n, 0, 30, w.sort_ws, s);
     if (rc != GSR_OK) return rc;
     hipLaunchKernelGGL(me_leaf_kernel, dim3((w.nl + 3) / 4), dim3(256), 0, s, cloud, (int)n, w.order, w.pts, w.leaf, w.nl);
     hipLaunchKernelGGL(me_level_kernel, dim3((w.nn + 255) / 256), dim3(256), 0, s, w.leaf, w.nl, w.node, w.nn);
@@ -561,9 +477,9 @@ extern "C" size_t gsr_points_search_workspace_bytes(int64_t n_cloud, int64_t n_q
 extern "C" int32_t gsr_points_downsample(const float* points, int64_t n, double thresh, void* ws, size_t ws_bytes,
                                          uint8_t* keep_out, int32_t* rounds_out, gsr_stream_t stream_) {
     if (rounds_out) *rounds_out = 0;
-    int rc = me_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
-    rc = me_check_thresh(thresh);
+    rc = gsr_check_positive("thresh", thresh);
     if (rc != GSR_OK) return rc;
     if (n == 0) return GSR_OK;
     if (!points || !keep_out) { gsr_set_error("points / keep_out are null with n %lld", (long long)n); return GSR_E_INVALID; }
@@ -606,9 +522,9 @@ extern "C" int32_t gsr_points_downsample(const float* points, int64_t n, double 
 
 extern "C" int32_t gsr_points_nearest(const float* query, int64_t n_query, const float* cloud, int64_t n_cloud, double max_dist,
                                       void* ws, size_t ws_bytes, double* dist_out, int32_t* idx_out, gsr_stream_t stream_) {
-    int rc = me_check_count("n_query", n_query);
+    int rc = gsr_check_count("n_query", n_query);
     if (rc != GSR_OK) return rc;
-    rc = me_check_count("n_cloud", n_cloud);
+    rc = gsr_check_count("n_cloud", n_cloud);
     if (rc != GSR_OK) return rc;
     if (!(max_dist > 0.0)) { gsr_set_error("max_dist must be > 0 (got %g; +inf: no limit)", max_dist); return GSR_E_INVALID; }
     if (n_query == 0) return GSR_OK;
@@ -633,7 +549,7 @@ extern "C" int32_t gsr_points_nearest(const float* query, int64_t n_query, const
     rc = me_build_tree(cloud, n_cloud, w, T, s);
     if (rc != GSR_OK) return rc;
     // the queries in their own Morton order (codes in the cloud's bounds, clamped): neighbouring lanes walk the same boxes
-    hipLaunchKernelGGL(me_morton_kernel, grid, dim3(256), 0, s, query, (int)n_query, w.mm, w.codes);
+    hipLaunchKernelGGL(cloud_morton_kernel, grid, dim3(256), 0, s, query, n_query, w.mm, w.codes);
     GSR_LAUNCH_CHECK();
     rc = gsr_radix_sort_pairs(w.codes, nullptr, w.codes_sorted, w.qorder, w.kt, w.vt, n_query, 0, 30, w.sort_ws, s);
     if (rc != GSR_OK) return rc;
@@ -680,16 +596,14 @@ struct MeObsWs {
 
 static MeObsWs me_obs_layout(void* base, int64_t n_) {
     MeObsWs w{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += gsr_align(bytes); return q; };
+    GsrWsCursor c(base);
     const size_t n = size_t(n_ > 0 ? n_ : 1);
-    w.inbound = reinterpret_cast<uint8_t*>(take(n));
-    w.in_obs = reinterpret_cast<uint8_t*>(take(n));
-    w.off_in = reinterpret_cast<uint32_t*>(take((n + 1) * 4));
-    w.off_obs = reinterpret_cast<uint32_t*>(take((n + 1) * 4));
-    w.scan_ws = take(gsr_scan_workspace_bytes((int64_t)n));
-    w.bytes = off;
+    w.inbound = c.take<uint8_t>(n);
+    w.in_obs = c.take<uint8_t>(n);
+    w.off_in = c.take<uint32_t>((n + 1) * 4);
+    w.off_obs = c.take<uint32_t>((n + 1) * 4);
+    w.scan_ws = c.take(gsr_scan_workspace_bytes((int64_t)n));
+    w.bytes = c.off;
     return w;
 }
 
@@ -701,7 +615,7 @@ extern "C" int32_t gsr_points_obs_filter_count(const float* points, int64_t n, c
                                                int64_t* n_in_obs_out, gsr_stream_t stream_) {
     if (!n_in_out || !n_in_obs_out) { gsr_set_error("n_in_out / n_in_obs_out are required"); return GSR_E_INVALID; }
     *n_in_out = *n_in_obs_out = 0;
-    int rc = me_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
     if (!shape_host || !bb_host) { gsr_set_error("shape_host and bb_host are required"); return GSR_E_INVALID; }
     if (shape_host[0] < 1 || shape_host[1] < 1 || shape_host[2] < 1) {
@@ -742,7 +656,7 @@ extern "C" int32_t gsr_points_obs_filter_count(const float* points, int64_t n, c
 
 extern "C" int32_t gsr_points_obs_filter_emit(const float* points, int64_t n, void* ws, size_t ws_bytes, float* data_in_out,
                                               float* data_in_obs_out, gsr_stream_t stream_) {
-    int rc = me_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
     if (n == 0) return GSR_OK;
     if (!points) { gsr_set_error("points is null with n %lld", (long long)n); return GSR_E_INVALID; }
@@ -778,7 +692,7 @@ __global__ void __launch_bounds__(256) me_plane_kernel(const float* __restrict__
 
 extern "C" int32_t gsr_points_plane_filter(const float* points, int64_t n, const double* plane_host, uint8_t* keep_out,
                                            gsr_stream_t stream_) {
-    int rc = me_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
     if (!plane_host) { gsr_set_error("plane_host (P0..P3) is required"); return GSR_E_INVALID; }
     if (n == 0) return GSR_OK;
@@ -792,51 +706,41 @@ extern "C" int32_t gsr_points_plane_filter(const float* points, int64_t n, const
 }
 
 // ---------------------------------------------------------------- EVAL_MEAN
-// Fixed order: thread t of workgroup b adds elements b * 256 + t, + blocks * 256, ... in index order; the 256 sums of a
-// workgroup are added by a fixed tree; the partials likewise in one workgroup.  The grid depends on n alone.
-__device__ __forceinline__ void me_block_sum(double& sum, unsigned long long& cnt, double* s_sum, unsigned long long* s_cnt) {
-    s_sum[threadIdx.x] = sum; s_cnt[threadIdx.x] = cnt;
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) { s_sum[threadIdx.x] += s_sum[threadIdx.x + d]; s_cnt[threadIdx.x] += s_cnt[threadIdx.x + d]; }
-        __syncthreads();
-    }
-    sum = s_sum[0]; cnt = s_cnt[0];
-}
-
+// The fixed order of gsr_block_sum_256 (cloud_common.h) for the sum and, in the same pass, the count: below 2^31, so exact as a
+// double in any order.
 __global__ void __launch_bounds__(256) me_mean_partial_kernel(const double* __restrict__ dist, int64_t n, double* __restrict__ psum,
                                                               unsigned long long* __restrict__ pcnt) {
-    __shared__ double s_sum[256];
-    __shared__ unsigned long long s_cnt[256];
+    __shared__ double s_val[2 * 256];
     double sum = 0.0;
     unsigned long long cnt = 0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const double d = dist[i];
         if (d <= DBL_MAX) { sum += d; ++cnt; }          // finite distances only (they are never negative)
     }
-    me_block_sum(sum, cnt, s_sum, s_cnt);
-    if (threadIdx.x == 0) { psum[blockIdx.x] = sum; pcnt[blockIdx.x] = cnt; }
+    double v[2] = {sum, (double)cnt};
+    gsr_block_sum_256(v, s_val);
+    if (threadIdx.x == 0) { psum[blockIdx.x] = v[0]; pcnt[blockIdx.x] = (unsigned long long)v[1]; }
 }
 
 __global__ void __launch_bounds__(256) me_mean_final_kernel(const double* __restrict__ psum, const unsigned long long* __restrict__ pcnt,
                                                             int blocks, double* __restrict__ mean_out, int64_t* __restrict__ count_out) {
-    __shared__ double s_sum[256];
-    __shared__ unsigned long long s_cnt[256];
+    __shared__ double s_val[2 * 256];
     double sum = 0.0;
     unsigned long long cnt = 0;
     for (int b = threadIdx.x; b < blocks; b += 256) { sum += psum[b]; cnt += pcnt[b]; }
-    me_block_sum(sum, cnt, s_sum, s_cnt);
+    double v[2] = {sum, (double)cnt};
+    gsr_block_sum_256(v, s_val);
     if (threadIdx.x == 0) {
-        *mean_out = cnt ? sum / (double)cnt : __longlong_as_double(0x7ff8000000000000LL);     // empty: NaN, like numpy's mean
-        if (count_out) *count_out = (int64_t)cnt;
+        *mean_out = v[1] > 0.0 ? v[0] / v[1] : __longlong_as_double(0x7ff8000000000000LL);    // empty: NaN, like numpy's mean
+        if (count_out) *count_out = (int64_t)v[1];
     }
 }
 
-extern "C" size_t gsr_dist_mean_workspace_bytes(int64_t n) { (void)n; return gsr_align(ME_MEAN_BLOCKS * 8) * 2; }
+extern "C" size_t gsr_dist_mean_workspace_bytes(int64_t n) { (void)n; return gsr_align(GSR_PARTIAL_BLOCKS * 8) * 2; }
 
 extern "C" int32_t gsr_dist_mean(const double* dist, int64_t n, void* ws, size_t ws_bytes, double* mean_out, int64_t* count_out,
                                  gsr_stream_t stream_) {
-    int rc = me_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
     if (!mean_out) { gsr_set_error("mean_out is required"); return GSR_E_INVALID; }
     if (n > 0 && !dist) { gsr_set_error("dist is null with n %lld", (long long)n); return GSR_E_INVALID; }
@@ -844,13 +748,13 @@ extern "C" int32_t gsr_dist_mean(const double* dist, int64_t n, void* ws, size_t
         gsr_set_error("ws_bytes: mean workspace too small (%zu < %zu bytes)", ws_bytes, gsr_dist_mean_workspace_bytes(n));
         return GSR_E_INVALID;
     }
-    double* psum = static_cast<double*>(ws);
-    unsigned long long* pcnt = reinterpret_cast<unsigned long long*>(static_cast<char*>(ws) + gsr_align(ME_MEAN_BLOCKS * 8));
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > ME_MEAN_BLOCKS) blocks = ME_MEAN_BLOCKS;
+    GsrWsCursor c(ws);
+    double* psum = c.take<double>(GSR_PARTIAL_BLOCKS * 8);
+    unsigned long long* pcnt = c.take<unsigned long long>(GSR_PARTIAL_BLOCKS * 8);
+    const unsigned blocks = gsr_partial_blocks(n);
     hipStream_t s = static_cast<hipStream_t>(stream_);
     if (blocks > 0) {
-        hipLaunchKernelGGL(me_mean_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dist, n, psum, pcnt);
+        hipLaunchKernelGGL(me_mean_partial_kernel, dim3(blocks), dim3(256), 0, s, dist, n, psum, pcnt);
         GSR_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(me_mean_final_kernel, dim3(1), dim3(256), 0, s, psum, pcnt, (int)blocks, mean_out, count_out);

@@ -19,6 +19,7 @@
 
 #define MP_MIN_CLUSTER 50u            // utils/mesh_utils.py:36: never keep a cluster below 50 triangles
 #define MP_MAX_EDGES 0x7fffffffLL     // the sort's element count is an int32
+#define MP_TRIS_EXCEED_SORT "n_tris %lld: the 3 n_tris edge records exceed the sort's 2^31 - 1 elements"
 
 static inline int mp_bits(uint64_t max_value) {
     int b = 0;
@@ -47,27 +48,25 @@ struct MpWs {
 // V < 0: the clustering part only
 static MpWs mp_layout(void* base, int64_t F, int64_t V) {
     MpWs w{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += gsr_align(bytes); return q; };
+    GsrWsCursor c(base);
     const size_t f = size_t(F > 0 ? F : 1), e = 3 * f;
-    w.header = reinterpret_cast<uint32_t*>(take(64 * 4));
+    w.header = c.take<uint32_t>(64 * 4);
     uint32_t** eb[] = {&w.lo, &w.hi, &w.ka, &w.va, &w.kb, &w.vb, &w.kt, &w.vt};
-    for (uint32_t** q : eb) *q = reinterpret_cast<uint32_t*>(take(e * 4));
-    w.sort_ws = take(gsr_sort_ws_bytes((int64_t)e));
-    w.parent = reinterpret_cast<int32_t*>(take(f * 4));
-    w.count = reinterpret_cast<uint32_t*>(take(f * 4));
+    for (uint32_t** q : eb) *q = c.take<uint32_t>(e * 4);
+    w.sort_ws = c.take(gsr_sort_ws_bytes((int64_t)e));
+    w.parent = c.take<int32_t>(f * 4);
+    w.count = c.take<uint32_t>(f * 4);
     if (V >= 0) {
         const size_t v = size_t(V > 0 ? V : 1);
-        w.labels = reinterpret_cast<int32_t*>(take(f * 4));
-        w.csize = reinterpret_cast<int32_t*>(take(f * 4));
-        w.emit = reinterpret_cast<uint8_t*>(take(f));
-        w.used = reinterpret_cast<uint8_t*>(take(v));
-        w.vert_off = reinterpret_cast<uint32_t*>(take((v + 1) * 4));
-        w.tri_off = reinterpret_cast<uint32_t*>(take((f + 1) * 4));
-        w.scan_ws = take(gsr_scan_workspace_bytes((int64_t)(v > f ? v : f)));
+        w.labels = c.take<int32_t>(f * 4);
+        w.csize = c.take<int32_t>(f * 4);
+        w.emit = c.take<uint8_t>(f);
+        w.used = c.take<uint8_t>(v);
+        w.vert_off = c.take<uint32_t>((v + 1) * 4);
+        w.tri_off = c.take<uint32_t>((f + 1) * 4);
+        w.scan_ws = c.take(gsr_scan_workspace_bytes((int64_t)(v > f ? v : f)));
     }
-    w.bytes = off;
+    w.bytes = c.off;
     return w;
 }
 
@@ -193,20 +192,6 @@ static int mp_run_clusters(const int32_t* tris, int64_t F, int64_t V, int32_t* l
     return GSR_OK;
 }
 
-static int mp_check_counts(int64_t n_tris, int64_t n_verts) {
-    if (n_tris < 0) { gsr_set_error("n_tris must be >= 0 (got %lld)", (long long)n_tris); return GSR_E_INVALID; }
-    if (n_verts < 0) { gsr_set_error("n_verts must be >= 0 (got %lld)", (long long)n_verts); return GSR_E_INVALID; }
-    if (n_verts > 0x7fffffffLL) {
-        gsr_set_error("n_verts %lld exceeds int32 vertex indices", (long long)n_verts);
-        return GSR_E_UNSUPPORTED;
-    }
-    if (n_tris > MP_MAX_EDGES / 3) {
-        gsr_set_error("n_tris %lld: the 3 n_tris edge records exceed the sort's 2^31 - 1 elements", (long long)n_tris);
-        return GSR_E_UNSUPPORTED;
-    }
-    return GSR_OK;
-}
-
 extern "C" size_t gsr_mesh_clusters_workspace_bytes(int64_t n_tris) { return mp_layout(nullptr, n_tris, -1).bytes; }
 
 extern "C" size_t gsr_mesh_filter_workspace_bytes(int64_t n_tris, int64_t n_verts) {
@@ -215,7 +200,7 @@ extern "C" size_t gsr_mesh_filter_workspace_bytes(int64_t n_tris, int64_t n_vert
 
 extern "C" int32_t gsr_mesh_clusters(const int32_t* tris, int64_t n_tris, int64_t n_verts, int32_t* labels,
                                      int32_t* cluster_size, void* ws, size_t ws_bytes, gsr_stream_t stream_) {
-    int rc = mp_check_counts(n_tris, n_verts);
+    int rc = gsr_check_mesh_counts(n_tris, n_verts, MP_MAX_EDGES / 3, MP_TRIS_EXCEED_SORT);
     if (rc != GSR_OK) return rc;
     if (n_tris == 0) return GSR_OK;
     if (!tris) { gsr_set_error("tris is null with n_tris %lld", (long long)n_tris); return GSR_E_INVALID; }
@@ -262,7 +247,7 @@ extern "C" int32_t gsr_mesh_filter_count(const int32_t* tris, int64_t n_tris, in
                                          gsr_stream_t stream_) {
     if (!n_verts_out || !n_tris_out) { gsr_set_error("n_verts_out / n_tris_out are required"); return GSR_E_INVALID; }
     *n_verts_out = *n_tris_out = 0;
-    int rc = mp_check_counts(n_tris, n_verts);
+    int rc = gsr_check_mesh_counts(n_tris, n_verts, MP_MAX_EDGES / 3, MP_TRIS_EXCEED_SORT);
     if (rc != GSR_OK) return rc;
     if (cluster_to_keep < 1) { gsr_set_error("cluster_to_keep must be >= 1 (got %d)", cluster_to_keep); return GSR_E_INVALID; }
     if (n_tris == 0) return GSR_OK;
@@ -307,7 +292,7 @@ extern "C" int32_t gsr_mesh_filter_count(const int32_t* tris, int64_t n_tris, in
 extern "C" int32_t gsr_mesh_filter_emit(const float* verts, const float* colors, const int32_t* tris, int64_t n_tris,
                                         int64_t n_verts, void* ws, size_t ws_bytes, float* verts_out, float* colors_out,
                                         int32_t* tris_out, gsr_stream_t stream_) {
-    int rc = mp_check_counts(n_tris, n_verts);
+    int rc = gsr_check_mesh_counts(n_tris, n_verts, MP_MAX_EDGES / 3, MP_TRIS_EXCEED_SORT);
     if (rc != GSR_OK) return rc;
     if (n_tris == 0) return GSR_OK;
     if (!verts || !colors || !tris) { gsr_set_error("verts, colors and tris are required"); return GSR_E_INVALID; }

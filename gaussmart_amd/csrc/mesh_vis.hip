@@ -192,14 +192,12 @@ struct MvDepthWs {
 
 static MvDepthWs mv_depth_layout(void* base, int64_t F, int32_t n_views) {
     MvDepthWs w{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += gsr_align(bytes); return q; };
+    GsrWsCursor c(base);
     const size_t f = size_t(F > 0 ? F : 0), n = size_t(n_views > 0 ? n_views : 0);
-    w.count = reinterpret_cast<uint32_t*>(take(4));
-    w.w2c = reinterpret_cast<float*>(take((n ? n : 1) * 48));
-    w.list = reinterpret_cast<uint32_t*>(take((f * n ? f * n : 1) * 4));
-    w.bytes = off;
+    w.count = c.take<uint32_t>(4);
+    w.w2c = c.take<float>((n ? n : 1) * 48);
+    w.list = c.take<uint32_t>((f * n ? f * n : 1) * 4);
+    w.bytes = c.off;
     return w;
 }
 
@@ -214,20 +212,6 @@ static int mv_check_image(int32_t n_views, int32_t H, int32_t W) {
     return GSR_OK;
 }
 
-static int mv_check_counts(int64_t n_tris, int64_t n_verts) {
-    if (n_tris < 0) { gsr_set_error("n_tris must be >= 0 (got %lld)", (long long)n_tris); return GSR_E_INVALID; }
-    if (n_verts < 0) { gsr_set_error("n_verts must be >= 0 (got %lld)", (long long)n_verts); return GSR_E_INVALID; }
-    if (n_verts > 0x7fffffffLL) {
-        gsr_set_error("n_verts %lld exceeds int32 vertex indices", (long long)n_verts);
-        return GSR_E_UNSUPPORTED;
-    }
-    if (n_tris > 0x7fffffffLL) {
-        gsr_set_error("n_tris %lld exceeds the scan's 2^31 - 1 elements", (long long)n_tris);
-        return GSR_E_UNSUPPORTED;
-    }
-    return GSR_OK;
-}
-
 extern "C" size_t gsr_mesh_depth_workspace_bytes(int64_t n_tris, int32_t n_views) {
     return mv_depth_layout(nullptr, n_tris, n_views).bytes;
 }
@@ -236,7 +220,7 @@ extern "C" int32_t gsr_mesh_depth_render(const float* verts, const int32_t* tris
                                          const float* w2c_host, int32_t n_views, int32_t H, int32_t W, float fx, float fy,
                                          float cx, float cy, float near, float far, float* depth_out, void* ws, size_t ws_bytes,
                                          gsr_stream_t stream_) {
-    int rc = mv_check_counts(n_tris, n_verts);
+    int rc = gsr_check_mesh_counts(n_tris, n_verts);
     if (rc != GSR_OK) return rc;
     rc = mv_check_image(n_views, H, W);
     if (rc != GSR_OK) return rc;
@@ -315,7 +299,7 @@ __global__ void __launch_bounds__(256) mv_vote_kernel(const float* __restrict__ 
 extern "C" int32_t gsr_mesh_vis_count(const float* verts, int64_t n_verts, const float* depths, int32_t n_views, int32_t H,
                                       int32_t W, const float* w2c_host, const float* intrinsics, float eps, int32_t min_views,
                                       int32_t* counts_inout, gsr_stream_t stream_) {
-    int rc = mv_check_counts(0, n_verts);
+    int rc = gsr_check_mesh_counts(0, n_verts);
     if (rc != GSR_OK) return rc;
     rc = mv_check_image(n_views, H, W);
     if (rc != GSR_OK) return rc;
@@ -352,17 +336,15 @@ struct MvWs {
 
 static MvWs mv_layout(void* base, int64_t F, int64_t V) {
     MvWs w{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += gsr_align(bytes); return q; };
+    GsrWsCursor c(base);
     const size_t f = size_t(F > 0 ? F : 1), v = size_t(V > 0 ? V : 1);
-    w.keep = reinterpret_cast<uint8_t*>(take(v));
-    w.used = reinterpret_cast<uint8_t*>(take(v));
-    w.emit = reinterpret_cast<uint8_t*>(take(f));
-    w.vert_off = reinterpret_cast<uint32_t*>(take((v + 1) * 4));
-    w.tri_off = reinterpret_cast<uint32_t*>(take((f + 1) * 4));
-    w.scan_ws = take(gsr_scan_workspace_bytes((int64_t)(v > f ? v : f)));
-    w.bytes = off;
+    w.keep = c.take<uint8_t>(v);
+    w.used = c.take<uint8_t>(v);
+    w.emit = c.take<uint8_t>(f);
+    w.vert_off = c.take<uint32_t>((v + 1) * 4);
+    w.tri_off = c.take<uint32_t>((f + 1) * 4);
+    w.scan_ws = c.take(gsr_scan_workspace_bytes((int64_t)(v > f ? v : f)));
+    w.bytes = c.off;
     return w;
 }
 
@@ -395,7 +377,7 @@ extern "C" int32_t gsr_mesh_vis_compact_count(const int32_t* tris, int64_t n_tri
                                               int64_t* n_verts_out, int64_t* n_tris_out, gsr_stream_t stream_) {
     if (!n_verts_out || !n_tris_out) { gsr_set_error("n_verts_out / n_tris_out are required"); return GSR_E_INVALID; }
     *n_verts_out = *n_tris_out = 0;
-    int rc = mv_check_counts(n_tris, n_verts);
+    int rc = gsr_check_mesh_counts(n_tris, n_verts);
     if (rc != GSR_OK) return rc;
     if (n_verts == 0) {
         if (n_tris > 0) { gsr_set_error("n_verts is 0 with n_tris %lld", (long long)n_tris); return GSR_E_INVALID; }
@@ -435,7 +417,7 @@ extern "C" int32_t gsr_mesh_vis_compact_count(const int32_t* tris, int64_t n_tri
 extern "C" int32_t gsr_mesh_vis_emit(const float* verts, const float* colors, const int32_t* tris, int64_t n_tris,
                                      int64_t n_verts, void* ws, size_t ws_bytes, float* verts_out, float* colors_out,
                                      int32_t* tris_out, gsr_stream_t stream_) {
-    int rc = mv_check_counts(n_tris, n_verts);
+    int rc = gsr_check_mesh_counts(n_tris, n_verts);
     if (rc != GSR_OK) return rc;
     if (n_tris == 0) return GSR_OK;
     if (n_verts == 0) { gsr_set_error("n_verts is 0 with n_tris %lld", (long long)n_tris); return GSR_E_INVALID; }

@@ -12,12 +12,10 @@
 //   seg_project_kernel, seg_assign_kernel   SEG_PROJ_*, SEG_ASSIGN: one thread per point
 //   seg_stats_kernel       SEG_STATS: one workgroup per label over the label-sorted order
 //   seg_emit_kernel        SEG_EMIT: one thread per new point
-#include "gsr_common.h"
-#include <cfloat>
+#include "cloud_common.h"
 #include <cmath>
 
 #define SEG_FACET_CHUNK 512          // facet records per LDS chunk (5 doubles each: 20 KB)
-#define SEG_SUM_BLOCKS 1024
 #define SEG_MAX_MASKS 32767
 #define SEG_MAX_VIEWS 4096
 // the reference's hard-coded DTU image size and fallback focal terms (pc_projection.py:48-63)
@@ -26,12 +24,6 @@
 #define SEG_DTU_MIN_FRACTION 0.1
 #define SEG_EPS 1e-10
 #define SEG_TYT_PADDING 0.1
-
-static int seg_check_count(const char* name, int64_t n) {
-    if (n < 0) { gsr_set_error("%s must be >= 0 (got %lld)", name, (long long)n); return GSR_E_INVALID; }
-    if (n > 0x7fffffffLL) { gsr_set_error("%s %lld exceeds int32 indices", name, (long long)n); return GSR_E_UNSUPPORTED; }
-    return GSR_OK;
-}
 
 static int seg_check_dtype(int32_t point_f64) {
     if (point_f64 != 0 && point_f64 != 1) { gsr_set_error("point_f64 must be 0 (f32) or 1 (f64), got %d", point_f64); return GSR_E_INVALID; }
@@ -75,7 +67,7 @@ __global__ void __launch_bounds__(256) seg_hull_kernel(const void* __restrict__ 
 
 extern "C" int32_t gsr_seg_hull_distance(const void* points, int32_t point_f64, int64_t n, const double* equations,
                                          int32_t n_facets, double* out, gsr_stream_t stream_) {
-    int rc = seg_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
     rc = seg_check_dtype(point_f64);
     if (rc != GSR_OK) return rc;
@@ -91,20 +83,7 @@ extern "C" int32_t gsr_seg_hull_distance(const void* points, int32_t point_f64, 
 }
 
 // ---------------------------------------------------------------- SEG_MEANSTD
-// Fixed order: thread t of workgroup b adds elements b * 256 + t, + blocks * 256, ... in index order; the 256 sums of a
-// workgroup are added by a fixed tree; the partials likewise in one workgroup.  The grid depends on n alone.
-__device__ __forceinline__ double seg_block_sum(double v, double* s_sum) {
-    s_sum[threadIdx.x] = v;
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) s_sum[threadIdx.x] += s_sum[threadIdx.x + d];
-        __syncthreads();
-    }
-    const double r = s_sum[0];
-    __syncthreads();
-    return r;
-}
-
+// The fixed order of gsr_block_sum_256 (cloud_common.h), twice: the mean, then the centred squares.
 // centre == NULL: sum of d; else: sum of (d - *centre)^2
 __global__ void __launch_bounds__(256) seg_sum_partial_kernel(const double* __restrict__ d, int64_t n, const double* centre,
                                                               double* __restrict__ partial) {
@@ -115,7 +94,7 @@ __global__ void __launch_bounds__(256) seg_sum_partial_kernel(const double* __re
         const double v = d[i];
         if (centre) { const double e = v - c; sum += e * e; } else sum += v;
     }
-    sum = seg_block_sum(sum, s_sum);
+    sum = gsr_block_sum_256(sum, s_sum);
     if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
@@ -125,17 +104,17 @@ __global__ void __launch_bounds__(256) seg_sum_final_kernel(const double* __rest
     __shared__ double s_sum[256];
     double sum = 0.0;
     for (int b = threadIdx.x; b < blocks; b += 256) sum += partial[b];
-    sum = seg_block_sum(sum, s_sum);
+    sum = gsr_block_sum_256(sum, s_sum);
     if (threadIdx.x == 0) {
         const double m = sum / (double)n;
         *out = root ? sqrt(m) : m;
     }
 }
 
-extern "C" size_t gsr_seg_mean_std_workspace_bytes(int64_t n) { (void)n; return gsr_align(SEG_SUM_BLOCKS * 8); }
+extern "C" size_t gsr_seg_mean_std_workspace_bytes(int64_t n) { (void)n; return gsr_align(GSR_PARTIAL_BLOCKS * 8); }
 
 extern "C" int32_t gsr_seg_mean_std(const double* d, int64_t n, double* out, void* ws, size_t ws_bytes, gsr_stream_t stream_) {
-    int rc = seg_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
     if (!out) { gsr_set_error("out (mean, std) is required"); return GSR_E_INVALID; }
     if (n > 0 && !d) { gsr_set_error("d is null with n %lld", (long long)n); return GSR_E_INVALID; }
@@ -144,12 +123,11 @@ extern "C" int32_t gsr_seg_mean_std(const double* d, int64_t n, double* out, voi
         return GSR_E_INVALID;
     }
     double* partial = static_cast<double*>(ws);
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > SEG_SUM_BLOCKS) blocks = SEG_SUM_BLOCKS;
+    const unsigned blocks = gsr_partial_blocks(n);
     hipStream_t s = static_cast<hipStream_t>(stream_);
     for (int pass = 0; pass < 2; ++pass) {
         if (blocks > 0) {
-            hipLaunchKernelGGL(seg_sum_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, s, d, n,
+            hipLaunchKernelGGL(seg_sum_partial_kernel, dim3(blocks), dim3(256), 0, s, d, n,
                                pass ? out : static_cast<const double*>(nullptr), partial);
             GSR_LAUNCH_CHECK();
         }
@@ -247,23 +225,13 @@ struct SegViewWs {
 
 static SegViewWs seg_view_layout(void* base, int32_t n_views) {
     SegViewWs w{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += gsr_align(bytes); return q; };
+    GsrWsCursor c(base);
     const size_t v = size_t(n_views > 0 ? n_views : 1);
-    w.box = reinterpret_cast<unsigned long long*>(take(64));
-    w.counts = reinterpret_cast<unsigned long long*>(take(v * 8));
-    w.views = reinterpret_cast<GsrSegView*>(take(v * sizeof(GsrSegView)));
-    w.bytes = off;
+    w.box = c.take<unsigned long long>(64);
+    w.counts = c.take<unsigned long long>(v * 8);
+    w.views = c.take<GsrSegView>(v * sizeof(GsrSegView));
+    w.bytes = c.off;
     return w;
-}
-
-__device__ __forceinline__ unsigned long long seg_d2ord(double f) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(f);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double seg_ord2d(unsigned long long u) {
-    return __longlong_as_double((long long)((u >> 63) ? (u & 0x7fffffffffffffffull) : ~u));
 }
 
 __global__ void __launch_bounds__(256) seg_box_kernel(const void* __restrict__ pts, int f64, int64_t n,
@@ -290,8 +258,8 @@ __global__ void __launch_bounds__(256) seg_box_kernel(const void* __restrict__ p
     if ((threadIdx.x & 63) == 0 && valid) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            atomicMin(&box[a], seg_d2ord(lo[a]));
-            atomicMax(&box[3 + a], seg_d2ord(hi[a]));
+            atomicMin(&box[a], gsr_d2ord(lo[a]));
+            atomicMax(&box[3 + a], gsr_d2ord(hi[a]));
         }
         atomicAdd(&box[6], valid);
     }
@@ -354,7 +322,7 @@ __device__ __forceinline__ SegProj seg_project(const GsrSegView& V, double px, d
     }
     // GSR_SEG_TYT
     if (box[6] == 0) return SegProj{0.0, 0.0, 0.0};
-    const double lox = seg_ord2d(box[0]), loy = seg_ord2d(box[1]), hix = seg_ord2d(box[3]), hiy = seg_ord2d(box[4]);
+    const double lox = gsr_ord2d(box[0]), loy = gsr_ord2d(box[1]), hix = gsr_ord2d(box[3]), hiy = gsr_ord2d(box[4]);
     const double span = 1.0 - 2.0 * SEG_TYT_PADDING;
     const double nx = SEG_TYT_PADDING + span * (px - lox) / ((hix - lox) + SEG_EPS);
     const double ny = SEG_TYT_PADDING + span * (py - loy) / ((hiy - loy) + SEG_EPS);
@@ -416,7 +384,7 @@ extern "C" size_t gsr_seg_views_workspace_bytes(int32_t n_views) { return seg_vi
 
 extern "C" int32_t gsr_seg_views_prepare(const void* points, int32_t point_f64, int64_t n, const GsrSegView* views_host,
                                          int32_t n_views, int64_t label_elems, void* ws, size_t ws_bytes, gsr_stream_t stream_) {
-    int rc = seg_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
     rc = seg_check_dtype(point_f64);
     if (rc != GSR_OK) return rc;
@@ -462,14 +430,13 @@ extern "C" int32_t gsr_seg_views_prepare(const void* points, int32_t point_f64, 
     // (pageable source: the copy has left views_host when the call returns)
     GSR_HIP_CHECK(hipMemcpyAsync(w.views, views_host, size_t(n_views) * sizeof(GsrSegView), hipMemcpyHostToDevice, s));
     if (n == 0) return GSR_OK;
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
+    const unsigned blocks = gsr_partial_blocks(n);
     if (any_tyt) {
-        hipLaunchKernelGGL(seg_box_kernel, dim3((unsigned)blocks), dim3(256), 0, s, points, point_f64, n, w.box);
+        hipLaunchKernelGGL(seg_box_kernel, dim3(blocks), dim3(256), 0, s, points, point_f64, n, w.box);
         GSR_LAUNCH_CHECK();
     }
     if (any_dtu) {
-        hipLaunchKernelGGL(seg_dtu_count_kernel, dim3((unsigned)blocks, (unsigned)n_views), dim3(256), 0, s, points, point_f64, n,
+        hipLaunchKernelGGL(seg_dtu_count_kernel, dim3(blocks, (unsigned)n_views), dim3(256), 0, s, points, point_f64, n,
                            w.views, w.counts);
         GSR_LAUNCH_CHECK();
     }
@@ -478,7 +445,7 @@ extern "C" int32_t gsr_seg_views_prepare(const void* points, int32_t point_f64, 
 
 static int seg_check_view_call(const void* points, int32_t point_f64, int64_t n, int32_t n_views, void* ws, size_t ws_bytes,
                                SegViewWs& w) {
-    int rc = seg_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
     rc = seg_check_dtype(point_f64);
     if (rc != GSR_OK) return rc;
@@ -523,7 +490,7 @@ extern "C" int32_t gsr_seg_assign(const void* points, int32_t point_f64, int64_t
 
 // ---------------------------------------------------------------- SEG_STATS
 // One workgroup per label.  order: the point indices sorted by label (stable); seg_off[l] .. seg_off[l + 1]: label l's run.
-// Thread t adds the run's elements t, t + 256, ... in that order, the 256 sums go through seg_block_sum's tree: mean first,
+// Thread t adds the run's elements t, t + 256, ... in that order, the 256 sums go through gsr_block_sum_256's tree: mean first,
 // then the centred moments.  out row: mean.xyz, cov (row-major 3x3), std.xyz, mean colour.rgb
 __global__ void __launch_bounds__(256) seg_stats_kernel(const float* __restrict__ pts, const float* __restrict__ col,
                                                         const int64_t* __restrict__ order, const int64_t* __restrict__ seg_off,
@@ -543,7 +510,7 @@ __global__ void __launch_bounds__(256) seg_stats_kernel(const float* __restrict_
     }
     double mean[6];
 #pragma unroll
-    for (int a = 0; a < 6; ++a) mean[a] = seg_block_sum(acc[a], s_sum) / cnt;
+    for (int a = 0; a < 6; ++a) { mean[a] = gsr_block_sum_256(acc[a], s_sum) / cnt; __syncthreads(); }     // s_sum is written again
     double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};                           // xx xy xz yy yz zz
     for (int64_t k = b + threadIdx.x; k < e; k += 256) {
         const int64_t i = order[k];
@@ -552,7 +519,10 @@ __global__ void __launch_bounds__(256) seg_stats_kernel(const float* __restrict_
         m[0] += dx * dx; m[1] += dx * dy; m[2] += dx * dz; m[3] += dy * dy; m[4] += dy * dz; m[5] += dz * dz;
     }
 #pragma unroll
-    for (int a = 0; a < 6; ++a) m[a] = seg_block_sum(m[a], s_sum) / (cnt > 1.0 ? cnt - 1.0 : 0.0);     // fewer than two points: NaN
+    for (int a = 0; a < 6; ++a) {
+        m[a] = gsr_block_sum_256(m[a], s_sum) / (cnt > 1.0 ? cnt - 1.0 : 0.0);      // fewer than two points: NaN
+        __syncthreads();
+    }
     if (threadIdx.x == 0) {
         count_out[l] = e - b;
         double* o = out + 18 * (int64_t)l;
@@ -567,7 +537,7 @@ __global__ void __launch_bounds__(256) seg_stats_kernel(const float* __restrict_
 
 extern "C" int32_t gsr_seg_stats(const float* points, const float* colors, const int64_t* order, const int64_t* seg_off, int64_t n,
                                  int32_t n_labels, int64_t* count_out, double* stats_out, gsr_stream_t stream_) {
-    int rc = seg_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
     if (n_labels < 0) { gsr_set_error("n_labels must be >= 0 (got %d)", n_labels); return GSR_E_INVALID; }
     if (n_labels == 0) return GSR_OK;
@@ -609,7 +579,7 @@ __global__ void __launch_bounds__(256) seg_emit_kernel(const float* __restrict__
 extern "C" int32_t gsr_seg_augment_emit(const float* eps, const int64_t* offsets, int32_t n_segs, const float* mean,
                                         const float* tril, const float* mean_color, const int64_t* labels, int64_t total,
                                         float* out_xyz, float* out_color, int64_t* out_label, gsr_stream_t stream_) {
-    int rc = seg_check_count("total", total);
+    int rc = gsr_check_count("total", total);
     if (rc != GSR_OK) return rc;
     if (n_segs < 0) { gsr_set_error("n_segs must be >= 0 (got %d)", n_segs); return GSR_E_INVALID; }
     if (total == 0) return GSR_OK;

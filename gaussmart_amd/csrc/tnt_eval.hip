@@ -6,31 +6,18 @@
 //   te_centres_kernel      TNT_CLOUD: one thread per face
 //   te_transform_kernel    TNT_TRANSFORM: one thread per point, the matrix by value
 //   te_crop_kernel         TNT_CROP: the polygon's (u, v) in LDS, one thread per point walks the m edges
-//   te_min_kernel, te_cell_kernel, te_head_kernel, te_voxel_emit_kernel   TNT_VOXEL: minimum, 63-bit cell keys as two words,
+//   cloud_bounds<false> (cloud_common.h), te_cell_kernel, te_head_kernel, te_voxel_emit_kernel   TNT_VOXEL: minimum, 63-bit cell keys as two words,
 //                          (stable two-word sort by gsr_radix_sort_pairs), run heads, (scan), one thread per cell adds its run
 //   te_sums_kernel, te_sums_final_kernel   TNT_ICP_SUMS in EVAL_MEAN's fixed order
 //   te_score_kernel        TNT_SCORE: edges and int32 bins in LDS, integer atomics only
 // No floating-point atomic anywhere: every result has the same bits on every run.
-#include "gsr_common.h"
-#include <cfloat>
+#include "cloud_common.h"
 #include <cmath>
 
 #define TE_MAX_POLY 256
 #define TE_MAX_BINS 4096
 #define TE_CELL_LIMIT 2097152.0      // 2^21 cells per axis: three indices share a 63-bit key
-#define TE_SUM_BLOCKS 1024
 #define TE_SUM_VALUES 10
-
-static int te_check_count(const char* name, int64_t n) {
-    if (n < 0) { gsr_set_error("%s must be >= 0 (got %lld)", name, (long long)n); return GSR_E_INVALID; }
-    if (n > 0x7fffffffLL) { gsr_set_error("%s %lld exceeds int32 indices", name, (long long)n); return GSR_E_UNSUPPORTED; }
-    return GSR_OK;
-}
-
-static int te_check_positive(const char* name, double v) {
-    if (!(v > 0.0) || !(v <= DBL_MAX)) { gsr_set_error("%s must be > 0 and finite (got %g)", name, v); return GSR_E_INVALID; }
-    return GSR_OK;
-}
 
 // ---------------------------------------------------------------- TNT_CLOUD
 // An index outside [0, V) gives a NaN row, never a wild read; the caller checks the range and raises.
@@ -54,9 +41,9 @@ __global__ void __launch_bounds__(256) te_centres_kernel(const float* __restrict
 
 extern "C" int32_t gsr_mesh_face_centres(const float* verts, const int32_t* tris, int64_t n_tris, int64_t n_verts,
                                          float* centres_out, gsr_stream_t stream_) {
-    int rc = te_check_count("n_tris", n_tris);
+    int rc = gsr_check_count("n_tris", n_tris);
     if (rc != GSR_OK) return rc;
-    rc = te_check_count("n_verts", n_verts);
+    rc = gsr_check_count("n_verts", n_verts);
     if (rc != GSR_OK) return rc;
     if (n_tris + n_verts > 0x7fffffffLL) {
         gsr_set_error("n_verts %lld + n_tris %lld exceed int32 indices", (long long)n_verts, (long long)n_tris);
@@ -87,7 +74,7 @@ __global__ void __launch_bounds__(256) te_transform_kernel(const float* __restri
 
 extern "C" int32_t gsr_points_transform(const float* points, int64_t n, const double* transform_host, float* out,
                                         gsr_stream_t stream_) {
-    int rc = te_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
     if (!transform_host) { gsr_set_error("transform_host (4x4, row-major) is required"); return GSR_E_INVALID; }
     if (!(transform_host[12] == 0.0 && transform_host[13] == 0.0 && transform_host[14] == 0.0 && transform_host[15] == 1.0)) {
@@ -134,7 +121,7 @@ __global__ void __launch_bounds__(256) te_crop_kernel(const float* __restrict__ 
 
 extern "C" int32_t gsr_points_crop_polygon(const float* points, int64_t n, int32_t orthogonal_axis, double axis_min, double axis_max,
                                            const double* polygon, int32_t n_polygon, uint8_t* keep_out, gsr_stream_t stream_) {
-    int rc = te_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
     if (orthogonal_axis < 0 || orthogonal_axis > 2) {
         gsr_set_error("orthogonal_axis must be 0 (X), 1 (Y) or 2 (Z) (got %d)", orthogonal_axis);
@@ -158,30 +145,8 @@ extern "C" int32_t gsr_points_crop_polygon(const float* points, int64_t n, int32
 }
 
 // ---------------------------------------------------------------- TNT_VOXEL
-__device__ __forceinline__ uint32_t te_f2ord(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float te_ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u); }
-
-// mm[a]: the per-axis minimum as an ordered word (integer atomicMin: the same word whatever the order of arrival)
-__global__ void __launch_bounds__(256) te_min_kernel(const float* __restrict__ xyz, int64_t n, uint32_t* __restrict__ mm) {
-    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX};
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) lo[a] = fminf(lo[a], xyz[3 * i + a]);
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) lo[a] = fminf(lo[a], __shfl_xor(lo[a], d, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) atomicMin(&mm[a], te_f2ord(lo[a]));
-    }
-}
-
+// info[0..2]: the per-axis minimum as ordered words, by cloud_bounds<false> (integer atomicMin: the same word whatever the
+// order of arrival)
 // key = ix << 42 | iy << 21 | iz as two words; info[1] != 0: some index is not in [0, 2^21) (NaN and inf included)
 __global__ void __launch_bounds__(256) te_cell_kernel(const float* __restrict__ xyz, int64_t n, const uint32_t* __restrict__ mm,
                                                       double voxel, uint32_t* __restrict__ key_lo, uint32_t* __restrict__ key_hi,
@@ -192,7 +157,7 @@ __global__ void __launch_bounds__(256) te_cell_kernel(const float* __restrict__ 
     bool bad = false;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        const double lo = (double)te_ord2f(mm[a]) - 0.5 * voxel;
+        const double lo = (double)gsr_ord2f(mm[a]) - 0.5 * voxel;
         const double c = floor(((double)xyz[3 * i + a] - lo) / voxel);
         const bool ok = c >= 0.0 && c < TE_CELL_LIMIT;
         bad = bad || !ok;
@@ -249,26 +214,24 @@ struct TeVoxelWs {
 
 static TeVoxelWs te_voxel_layout(void* base, int64_t n_) {
     TeVoxelWs w{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += gsr_align(bytes); return q; };
+    GsrWsCursor c(base);
     const size_t n = size_t(n_ > 0 ? n_ : 1);
-    auto words = [&]() { return reinterpret_cast<uint32_t*>(take(n * 4)); };
-    w.info = reinterpret_cast<uint32_t*>(take(32));
+    auto words = [&]() { return c.take<uint32_t>(n * 4); };
+    w.info = c.take<uint32_t>(32);
     w.key_lo = words(); w.key_hi = words(); w.k1 = words(); w.o1 = words(); w.h1 = words(); w.kt = words(); w.vt = words();
     w.v2t = words(); w.k2 = words(); w.order = words();
-    w.head = reinterpret_cast<uint8_t*>(take(n));
-    w.off = reinterpret_cast<uint32_t*>(take((n + 1) * 4));
-    w.scan_ws = take(gsr_scan_workspace_bytes((int64_t)n));
-    w.sort_ws = take(gsr_sort_ws_bytes((int64_t)n));
-    w.bytes = off;
+    w.head = c.take<uint8_t>(n);
+    w.off = c.take<uint32_t>((n + 1) * 4);
+    w.scan_ws = c.take(gsr_scan_workspace_bytes((int64_t)n));
+    w.sort_ws = c.take(gsr_sort_ws_bytes((int64_t)n));
+    w.bytes = c.off;
     return w;
 }
 
 static int te_check_voxel(const float* points, int64_t n, double voxel_size, void* ws, size_t ws_bytes, TeVoxelWs& w) {
-    int rc = te_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
-    rc = te_check_positive("voxel_size", voxel_size);
+    rc = gsr_check_positive("voxel_size", voxel_size);
     if (rc != GSR_OK) return rc;
     if (n > 0 && !points) { gsr_set_error("points is null with n %lld", (long long)n); return GSR_E_INVALID; }
     w = te_voxel_layout(ws, n);
@@ -292,11 +255,10 @@ extern "C" int32_t gsr_points_voxel_count(const float* points, int64_t n, double
     unsigned long long* host = gsr_pinned_words(1);
     if (!host) { gsr_set_error("pinned host allocation failed"); return GSR_E_HIP; }
     hipStream_t s = static_cast<hipStream_t>(stream_);
-    const int64_t nb = (n + 255) / 256;
-    const dim3 grid((unsigned)nb);
-    GSR_HIP_CHECK(hipMemsetAsync(w.info, 0xFF, 16, s));
+    const dim3 grid((unsigned)((n + 255) / 256));
+    rc = cloud_bounds<false>(points, n, w.info, s);
+    if (rc != GSR_OK) return rc;
     GSR_HIP_CHECK(hipMemsetAsync(w.info + 4, 0, 16, s));
-    hipLaunchKernelGGL(te_min_kernel, dim3((unsigned)(nb < 1024 ? nb : 1024)), dim3(256), 0, s, points, n, w.info);
     hipLaunchKernelGGL(te_cell_kernel, grid, dim3(256), 0, s, points, n, w.info, voxel_size, w.key_lo, w.key_hi, w.info + 4);
     GSR_LAUNCH_CHECK();
     // stable sort on the 63-bit key, low word first; the high word rides along as the second value of the first sort
@@ -336,25 +298,8 @@ extern "C" int32_t gsr_points_voxel_emit(const float* points, int64_t n, double 
 }
 
 // ---------------------------------------------------------------- TNT_ICP_SUMS
-// EVAL_MEAN's order for NV sums at once: thread t of workgroup b adds its pairs in index order, a fixed tree adds the 256
-// partial sums of each value, one workgroup adds the workgroups' partials the same way.
+// The fixed order of gsr_block_sum_256 (cloud_common.h) for TE_SUM_VALUES sums at once.
 struct TeMeans { double s[3], t[3]; };
-
-template <int NV>
-__device__ __forceinline__ void te_block_sum(double (&v)[NV], double* s_val) {
-#pragma unroll
-    for (int q = 0; q < NV; ++q) s_val[q * 256 + threadIdx.x] = v[q];
-    __syncthreads();
-    for (int d = 128; d > 0; d >>= 1) {
-        if ((int)threadIdx.x < d) {
-#pragma unroll
-            for (int q = 0; q < NV; ++q) s_val[q * 256 + threadIdx.x] += s_val[q * 256 + threadIdx.x + d];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int q = 0; q < NV; ++q) v[q] = s_val[q * 256];
-}
 
 // PASS2 false: v = (count, sum s.xyz, sum t.xyz, sum d^2, 0, 0); true: v = (sum (t - tm)(s - sm)^T row-major, sum |s - sm|^2)
 template <bool PASS2>
@@ -387,7 +332,7 @@ __global__ void __launch_bounds__(256) te_sums_kernel(const float* __restrict__ 
             v[9] += (ds[0] * ds[0] + ds[1] * ds[1]) + ds[2] * ds[2];
         }
     }
-    te_block_sum<TE_SUM_VALUES>(v, s_val);
+    gsr_block_sum_256(v, s_val);
     if (threadIdx.x < TE_SUM_VALUES) partial[(int64_t)blockIdx.x * TE_SUM_VALUES + threadIdx.x] = s_val[threadIdx.x * 256];
 }
 
@@ -400,18 +345,18 @@ __global__ void __launch_bounds__(256) te_sums_final_kernel(const double* __rest
 #pragma unroll
         for (int q = 0; q < TE_SUM_VALUES; ++q) v[q] += partial[(int64_t)b * TE_SUM_VALUES + q];
     }
-    te_block_sum<TE_SUM_VALUES>(v, s_val);
+    gsr_block_sum_256(v, s_val);
     if (threadIdx.x < TE_SUM_VALUES) out[threadIdx.x] = s_val[threadIdx.x * 256];
 }
 
-extern "C" size_t gsr_icp_sums_workspace_bytes(int64_t n) { (void)n; return gsr_align(size_t(TE_SUM_BLOCKS) * TE_SUM_VALUES * 8); }
+extern "C" size_t gsr_icp_sums_workspace_bytes(int64_t n) { (void)n; return gsr_align(size_t(GSR_PARTIAL_BLOCKS) * TE_SUM_VALUES * 8); }
 
 extern "C" int32_t gsr_icp_sums(const float* source, int64_t n_source, const float* target, int64_t n_target, const double* dist,
                                 const int32_t* idx, const double* means_host, void* ws, size_t ws_bytes, double* out,
                                 gsr_stream_t stream_) {
-    int rc = te_check_count("n_source", n_source);
+    int rc = gsr_check_count("n_source", n_source);
     if (rc != GSR_OK) return rc;
-    rc = te_check_count("n_target", n_target);
+    rc = gsr_check_count("n_target", n_target);
     if (rc != GSR_OK) return rc;
     if (!out) { gsr_set_error("out (device f64 [10]) is required"); return GSR_E_INVALID; }
     if (n_source > 0 && (!source || !dist || !idx)) {
@@ -428,15 +373,14 @@ extern "C" int32_t gsr_icp_sums(const float* source, int64_t n_source, const flo
         for (int a = 0; a < 3; ++a) { mu.s[a] = means_host[a]; mu.t[a] = means_host[3 + a]; }
     }
     double* partial = static_cast<double*>(ws);
-    int64_t blocks = (n_source + 255) / 256;
-    if (blocks > TE_SUM_BLOCKS) blocks = TE_SUM_BLOCKS;
+    const unsigned blocks = gsr_partial_blocks(n_source);
     hipStream_t s = static_cast<hipStream_t>(stream_);
     if (blocks > 0) {
         if (means_host)
-            hipLaunchKernelGGL(te_sums_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, source, target, n_source, n_target, dist,
+            hipLaunchKernelGGL(te_sums_kernel<true>, dim3(blocks), dim3(256), 0, s, source, target, n_source, n_target, dist,
                                idx, mu, partial);
         else
-            hipLaunchKernelGGL(te_sums_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, source, target, n_source, n_target,
+            hipLaunchKernelGGL(te_sums_kernel<false>, dim3(blocks), dim3(256), 0, s, source, target, n_source, n_target,
                                dist, idx, mu, partial);
         GSR_LAUNCH_CHECK();
     }
@@ -489,9 +433,9 @@ extern "C" size_t gsr_dist_score_workspace_bytes(int32_t n_bins) {
 
 extern "C" int32_t gsr_dist_score(const double* dist, int64_t n, const double* edges_host, int32_t n_bins, double tau, void* ws,
                                   size_t ws_bytes, int64_t* count_out, int64_t* hist_out, gsr_stream_t stream_) {
-    int rc = te_check_count("n", n);
+    int rc = gsr_check_count("n", n);
     if (rc != GSR_OK) return rc;
-    rc = te_check_positive("tau", tau);
+    rc = gsr_check_positive("tau", tau);
     if (rc != GSR_OK) return rc;
     if (n_bins < 1) { gsr_set_error("n_bins must be >= 1 (got %d)", n_bins); return GSR_E_INVALID; }
     if (n_bins > TE_MAX_BINS) { gsr_set_error("n_bins %d exceeds %d", n_bins, TE_MAX_BINS); return GSR_E_UNSUPPORTED; }
@@ -516,10 +460,8 @@ extern "C" int32_t gsr_dist_score(const double* dist, int64_t n, const double* e
     double* edges = static_cast<double*>(ws);
     // (pageable source: the copy has left edges_host when the call returns)
     GSR_HIP_CHECK(hipMemcpyAsync(edges, edges_host, size_t(n_bins + 1) * 8, hipMemcpyHostToDevice, s));
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
     const size_t lds = size_t(n_bins + 1) * 8 + size_t(n_bins) * 4;
-    hipLaunchKernelGGL(te_score_kernel, dim3((unsigned)blocks), dim3(256), lds, s, dist, n, edges, n_bins, tau,
+    hipLaunchKernelGGL(te_score_kernel, dim3(gsr_partial_blocks(n)), dim3(256), lds, s, dist, n, edges, n_bins, tau,
                        reinterpret_cast<unsigned long long*>(count_out), reinterpret_cast<unsigned long long*>(hist_out));
     GSR_LAUNCH_CHECK();
     return GSR_OK;

@@ -13,7 +13,6 @@ struct TsdfGrid {
     float vs;
 };
 
-static inline size_t tsdf_align(size_t x) { return (x + 255) & ~size_t(255); }
 __host__ __device__ static inline int64_t scan_tiles(int64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }
 
 // linear block id -> grid block coordinates, and back (x fastest)
@@ -52,18 +51,16 @@ struct TsdfWs {
 
 static inline TsdfWs tsdf_ws_layout(void* base, int64_t n) {
     TsdfWs w{};
-    char* p = static_cast<char*>(base);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* q = p ? p + off : nullptr; off += tsdf_align(bytes); return q; };
-    w.header = reinterpret_cast<uint32_t*>(take(64 * 4));
-    w.stamp = reinterpret_cast<int*>(take(n * 4));
-    w.slot_block_offset = off;
-    w.slot_block = reinterpret_cast<int*>(take(n * 4));
-    w.touched = reinterpret_cast<int*>(take(n * 4));
-    w.flags = reinterpret_cast<uint8_t*>(take(2 * n));
-    w.scans = reinterpret_cast<uint32_t*>(take(2 * (n + 1) * 4));
-    w.partial = reinterpret_cast<uint32_t*>(take(2 * scan_tiles(n) * 4 + 4));
-    w.bytes = off;
+    GsrWsCursor c(base);
+    w.header = c.take<uint32_t>(64 * 4);
+    w.stamp = c.take<int>(n * 4);
+    w.slot_block_offset = c.off;
+    w.slot_block = c.take<int>(n * 4);
+    w.touched = c.take<int>(n * 4);
+    w.flags = c.take<uint8_t>(2 * n);
+    w.scans = c.take<uint32_t>(2 * (n + 1) * 4);
+    w.partial = c.take<uint32_t>(2 * scan_tiles(n) * 4 + 4);
+    w.bytes = c.off;
     return w;
 }
 

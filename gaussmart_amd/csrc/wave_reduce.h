@@ -1,4 +1,4 @@
-// DPP-row (16-lane) reductions shared by the backward kernels, and whole-wave min / max (tsdf.hip) (gfx950 only).
+// DPP-row (16-lane) reductions shared by the backward kernels, and whole-wave min / max (tsdf.hip, cloud_common.h) (gfx950 only).
 #pragma once
 #include "gsr_common.h"
 

@@ -13,7 +13,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _dev, _lib
 from .fused_regularizer import camera_kinv
 
 
@@ -37,7 +37,7 @@ class _Objective(torch.autograd.Function):
             # (with defer_value the five scalars are only written during the backward: until then they read NaN -- the loss
             # forward's launch fills them in -- so a value taken without a backward, or before it, is visibly invalid)
             out = torch.empty(5, dtype=torch.float32, device=dev)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _dev.stream(dev)
             # the scan the rasterizer's backward starts with rides along with these launches, if the forward that produced
             # `image` offered it (training_objective took the job from image.grad_fn)
             if not ctx.needs_input_grad[0]:
@@ -94,7 +94,7 @@ class _Objective(torch.autograd.Function):
         dam = None
         with torch.cuda.device(dev):
             scale = g_total.detach().float().reshape(1).contiguous()
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _dev.stream(dev)
             dimg = torch.empty_like(img)
             from .rasterizer import row_scan_job_usable
             job, ctx.row_scan_job = ctx.row_scan_job, None

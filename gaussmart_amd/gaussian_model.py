@@ -390,9 +390,9 @@ class GaussianModel:
             self.add_densification_stats(viewspace_point_tensor, vis)
             return
         import ctypes as C
-        from . import _lib
+        from . import _dev, _lib
         with torch.cuda.device(radii.device):
             _lib.check(_lib.lib().gsr_densify_stats(
                 radii.shape[0], C.c_void_p(radii.data_ptr()), C.c_void_p(grad.data_ptr()), C.c_void_p(self.max_radii2D.data_ptr()),
                 C.c_void_p(self.xyz_gradient_accum.data_ptr()), C.c_void_p(self.denom.data_ptr()),
-                C.c_void_p(torch.cuda.current_stream(radii.device).cuda_stream)))
+                _dev.stream(radii.device)))

@@ -1,9 +1,7 @@
 """`simple_knn._C.distCUDA2` on top of libgsr_hip.so (call site scene/gaussian_model.py:22,261)."""
-import ctypes as C
-
 import torch
 
-from . import _lib
+from . import _dev, _lib
 
 
 def distCUDA2(points: torch.Tensor) -> torch.Tensor:
@@ -20,11 +18,8 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
     if n == 0:
         return out
     with torch.cuda.device(pts.device):
-        nbytes = L.gsr_knn3_workspace_bytes(n)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
-        stream = torch.cuda.current_stream(pts.device).cuda_stream
-        _lib.check(L.gsr_knn3(C.c_void_p(pts.data_ptr()), n, C.c_void_p(out.data_ptr()),
-                              C.c_void_p(ws.data_ptr()), nbytes, C.c_void_p(stream)))
+        ws = _dev.workspace(L.gsr_knn3_workspace_bytes(n), pts.device)
+        _lib.check(L.gsr_knn3(_dev.ptr(pts), n, _dev.ptr(out), _dev.ptr(ws), ws.numel(), _dev.stream(pts.device)))
     return out
 
 
@@ -40,10 +35,7 @@ def sort_pairs_u32(keys: torch.Tensor, vals, begin_bit=0, end_bit=32):
     if n == 0:
         return ko, vo
     with torch.cuda.device(k.device):
-        nbytes = L.gsr_sort_workspace_bytes(n)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=k.device)
-        stream = torch.cuda.current_stream(k.device).cuda_stream
-        _lib.check(L.gsr_sort_pairs_u32(C.c_void_p(k.data_ptr()), C.c_void_p(v.data_ptr()) if v is not None else None,
-                                        C.c_void_p(ko.data_ptr()), C.c_void_p(vo.data_ptr()), n, begin_bit,
-                                        end_bit, C.c_void_p(ws.data_ptr()), nbytes, C.c_void_p(stream)))
+        ws = _dev.workspace(L.gsr_sort_workspace_bytes(n), k.device)
+        _lib.check(L.gsr_sort_pairs_u32(_dev.ptr(k), _dev.ptr(v) if v is not None else None, _dev.ptr(ko), _dev.ptr(vo), n,
+                                        begin_bit, end_bit, _dev.ptr(ws), ws.numel(), _dev.stream(k.device)))
     return ko, vo

@@ -22,7 +22,7 @@ from functools import partial
 import numpy as np
 import torch
 
-from . import _lib
+from . import _dev, _lib
 from .tsdf import DepthBounds, TSDFVolume, block_aabb_of_points
 
 
@@ -137,9 +137,9 @@ def mesh_clusters_device(triangles, n_verts):
     F, dev = len(tris), tris.device
     labels = torch.empty(F, dtype=torch.int32, device=dev)
     sizes = torch.empty(F, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(1, L.gsr_mesh_clusters_workspace_bytes(F)), dtype=torch.uint8, device=dev)
+    ws = _dev.workspace(L.gsr_mesh_clusters_workspace_bytes(F), dev)
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _dev.stream(dev)
         _lib.check(L.gsr_mesh_clusters(C.c_void_p(tris.data_ptr()), F, int(n_verts), C.c_void_p(labels.data_ptr()),
                                        C.c_void_p(sizes.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(), stream))
     return labels, sizes
@@ -164,9 +164,9 @@ def post_process_mesh_device(mesh, cluster_to_keep=1000, device=None):
     if F == 0:
         return DeviceTriangleMesh(torch.zeros((0, 3), device=dev), torch.zeros((0, 3), dtype=torch.int32, device=dev),
                                   torch.zeros((0, 3), device=dev))
-    ws = torch.empty(max(1, L.gsr_mesh_filter_workspace_bytes(F, V)), dtype=torch.uint8, device=dev)
+    ws = _dev.workspace(L.gsr_mesh_filter_workspace_bytes(F, V), dev)
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _dev.stream(dev)
         nv, nt = C.c_int64(), C.c_int64()
         tp = C.c_void_p(mesh.triangles.data_ptr())
         _lib.check(L.gsr_mesh_filter_count(tp, F, V, int(cluster_to_keep), C.c_void_p(ws.data_ptr()), ws.numel(),

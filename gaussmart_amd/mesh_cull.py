@@ -16,7 +16,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _dev, _lib
 from .mesh import DeviceTriangleMesh, TriangleMesh
 
 DEFAULT_RADIUS = 24          # the reference's disk(24)
@@ -122,9 +122,9 @@ def dilate_masks(masks, radius=DEFAULT_RADIUS):
     if n == 0 or H == 0 or W == 0:
         return out
     dev = masks.device
-    ws = torch.empty(L.gsr_mask_dilate_workspace_bytes(n, H, W), dtype=torch.uint8, device=dev)
+    ws = _dev.workspace(L.gsr_mask_dilate_workspace_bytes(n, H, W), dev)
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _dev.stream(dev)
         _lib.check(L.gsr_mask_dilate_disk(C.c_void_p(masks.data_ptr()), n, H, W, int(radius), C.c_void_p(out.data_ptr()),
                                           C.c_void_p(ws.data_ptr()), ws.numel(), stream))
     return out
@@ -160,9 +160,9 @@ def cull_mesh_by_masks(mesh, proj, masks, radius=DEFAULT_RADIUS, norm_size=None,
     per_view = (2 if masks.is_cuda else 3) * H * W
     chunk = max(1, budget // max(per_view, 1))
     keep = torch.ones(V, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(1, L.gsr_mesh_cull_workspace_bytes(F, V, min(chunk, n))), dtype=torch.uint8, device=dev)
+    ws = _dev.workspace(L.gsr_mesh_cull_workspace_bytes(F, V, min(chunk, n)), dev)
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _dev.stream(dev)
         nv, nt = C.c_int64(), C.c_int64()
         vp, tp = C.c_void_p(mesh.vertices.data_ptr()), C.c_void_p(mesh.triangles.data_ptr())
         for a in ([0] if n == 0 else range(0, n, chunk)):        # zero views: one call that keeps everything

@@ -18,6 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._dev import (device_points as _device_points, points64 as _points64, ptr as _ptr, stream as _stream,
+                   workspace as _workspace)
 from .compaction import compact_rows
 from .mesh import DeviceTriangleMesh, TriangleMesh
 
@@ -31,27 +33,6 @@ def default_order(n, seed=0):
 
 
 # ---------------------------------------------------------------- device path
-def _ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _device_points(points, device, who):
-    if isinstance(points, np.ndarray):
-        if device is None:
-            raise ValueError(f"{who}: a host array needs device=")
-        points = torch.from_numpy(np.ascontiguousarray(points, np.float32)).to(device)
-    if not isinstance(points, torch.Tensor) or not points.is_cuda:
-        raise _lib.GsrError(f"{who}: points must live on the device (no CPU path; see {who}_host)")
-    points = points.to(torch.float32).contiguous()
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"{who}: points must be [n,3], got {list(points.shape)}")
-    return points
-
-
 def _check_thresh(thresh, who):
     thresh = float(thresh)
     if not (0 < thresh < np.inf):
@@ -70,7 +51,7 @@ def sample_mesh_points(mesh, thresh=DEFAULT_DENSITY, device=None):
         raise _lib.GsrError("sample_mesh_points: the mesh must live on the device (no CPU path; see sample_mesh_points_host)")
     L = _lib.lib()
     dev, F, V = mesh.device, len(mesh.triangles), len(mesh.vertices)
-    ws = torch.empty(L.gsr_mesh_sample_workspace_bytes(F), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.gsr_mesh_sample_workspace_bytes(F), dev)
     with torch.cuda.device(dev):
         n = C.c_int64()
         args = (_ptr(mesh.vertices), _ptr(mesh.triangles), F, V, thresh, _ptr(ws), ws.numel())
@@ -104,7 +85,7 @@ def downsample_points(points, thresh=DEFAULT_DENSITY, device=None, return_rounds
     L = _lib.lib()
     dev, n = points.device, len(points)
     keep = torch.zeros(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(L.gsr_points_search_workspace_bytes(n, 0), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.gsr_points_search_workspace_bytes(n, 0), dev)
     rounds = C.c_int32()
     with torch.cuda.device(dev):
         _lib.check(L.gsr_points_downsample(_ptr(points), n, thresh, _ptr(ws), ws.numel(), _ptr(keep), C.byref(rounds), _stream(dev)))
@@ -124,7 +105,7 @@ def nearest_distance(query, cloud, max_dist=np.inf, device=None):
     dev, nq, nc = query.device, len(query), len(cloud)
     dist = torch.empty(nq, dtype=torch.float64, device=dev)
     idx = torch.empty(nq, dtype=torch.int32, device=dev)
-    ws = torch.empty(L.gsr_points_search_workspace_bytes(nc, nq), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.gsr_points_search_workspace_bytes(nc, nq), dev)
     with torch.cuda.device(dev):
         _lib.check(L.gsr_points_nearest(_ptr(query), nq, _ptr(cloud), nc, max_dist, _ptr(ws), ws.numel(), _ptr(dist), _ptr(idx),
                                         _stream(dev)))
@@ -153,7 +134,7 @@ def filter_by_obs_mask(points, obs_mask, bb, res, patch_size=DEFAULT_PATCH, devi
     shape = np.array(obs.shape, np.int32)
     inb = torch.zeros(n, dtype=torch.uint8, device=dev)
     ino = torch.zeros(n, dtype=torch.uint8, device=dev)
-    ws = torch.empty(L.gsr_points_obs_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.gsr_points_obs_workspace_bytes(n), dev)
     with torch.cuda.device(dev):
         n_in, n_obs = C.c_int64(), C.c_int64()
         _lib.check(L.gsr_points_obs_filter_count(_ptr(points), n, _ptr(obs_d), shape.ctypes.data_as(C.c_void_p),
@@ -184,7 +165,7 @@ def distance_mean(dist):
     dist = dist.contiguous().reshape(-1)
     L = _lib.lib()
     dev, n = dist.device, dist.numel()
-    ws = torch.empty(L.gsr_dist_mean_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.gsr_dist_mean_workspace_bytes(n), dev)
     mean = torch.empty(1, dtype=torch.float64, device=dev)
     cnt = torch.empty(1, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
@@ -247,12 +228,6 @@ def evaluate_dtu_mesh(mesh, stl_points, obs_mask, bb, res, plane, *, downsample_
 
 
 # ---------------------------------------------------------------- host path (numpy float64 + cKDTree)
-def _points64(points):
-    p = np.asarray(points.detach().cpu().numpy() if isinstance(points, torch.Tensor) else points)
-    p = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
-    return p.astype(np.float64)
-
-
 def _dist2(a, b):
     """EVAL_DIST on float64 copies of float32 points."""
     d = a - b

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._dev import stream as _stream
 from .mesh import DeviceTriangleMesh, GaussianExtractor, TriangleMesh
 from .tsdf import BLOCK, TSDFVolume
 
@@ -125,10 +126,6 @@ def _frame(center, radius, voxel_size):
         raise ValueError("center needs 3 values")
     # UNB_TRUNC: 5 voxel_size in double, rounded once to f32
     return (C.c_float * 3)(*c.tolist()), float(radius), float(np.float32(5.0 * float(voxel_size)))
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 @torch.no_grad()

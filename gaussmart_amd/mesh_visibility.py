@@ -20,7 +20,7 @@ import re
 import numpy as np
 import torch
 
-from . import _lib
+from . import _dev, _lib
 from .mesh import DeviceTriangleMesh, TriangleMesh
 from .mesh_cull import VIEW_CHUNK_BYTES, _fma32
 
@@ -147,9 +147,9 @@ def render_mesh_depth(mesh, w2c, H, W, fx, fy, cx, cy, near=DEFAULT_NEAR, far=DE
         return out
     budget = VIEW_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
     chunk = max(1, min(budget // max(4 * F, 1), (2 ** 32 - 1) // max(F, 1)))
-    ws = torch.empty(L.gsr_mesh_depth_workspace_bytes(F, min(chunk, n)), dtype=torch.uint8, device=dev)
+    ws = _dev.workspace(L.gsr_mesh_depth_workspace_bytes(F, min(chunk, n)), dev)
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _dev.stream(dev)
         for a in range(0, n, chunk):
             b = min(a + chunk, n)
             m = np.ascontiguousarray(w2c[a:b]).reshape(-1)
@@ -185,7 +185,7 @@ def visibility_counts(vertices, w2c, depths, fx, fy, cx, cy, eps=DEFAULT_EPS, mi
     L = _lib.lib()
     intr = np.array([fx, fy, cx, cy], np.float32)
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _dev.stream(dev)
         _lib.check(L.gsr_mesh_vis_count(C.c_void_p(vertices.data_ptr()), V, C.c_void_p(depths.data_ptr()), n, H, W,
                                         w2c.ctypes.data_as(C.c_void_p), intr.ctypes.data_as(C.c_void_p), eps, int(min_views),
                                         C.c_void_p(counts.data_ptr()), stream))
@@ -198,9 +198,9 @@ def compact_by_counts(mesh, counts, min_views=DEFAULT_MIN_VIEWS, return_keep=Fal
     dev = mesh.device
     F, V = len(mesh.triangles), len(mesh.vertices)
     keep = torch.empty(V, dtype=torch.uint8, device=dev)
-    ws = torch.empty(max(1, L.gsr_mesh_vis_workspace_bytes(F, V)), dtype=torch.uint8, device=dev)
+    ws = _dev.workspace(L.gsr_mesh_vis_workspace_bytes(F, V), dev)
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _dev.stream(dev)
         nv, nt = C.c_int64(), C.c_int64()
         vp, tp = C.c_void_p(mesh.vertices.data_ptr()), C.c_void_p(mesh.triangles.data_ptr())
         _lib.check(L.gsr_mesh_vis_compact_count(tp, F, V, C.c_void_p(counts.data_ptr()), int(min_views), C.c_void_p(ws.data_ptr()),

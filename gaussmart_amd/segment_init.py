@@ -20,6 +20,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._dev import (device_points as _device_points, points64 as _points64, ptr as _ptr, stream as _stream,
+                   workspace as _workspace)
 from .compaction import compact_rows
 
 KINDS = {"dtu": 0, "nerf": 1, "tyt": 2}
@@ -40,43 +42,11 @@ MIN_TARGET = 10
 VIEW_CHUNK_BYTES = 1 << 30
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _device_points(points, device, who):
-    """-> (contiguous device tensor f32 or f64 [n,3], point_f64 flag).  f64 stays f64, anything else becomes f32."""
-    if isinstance(points, np.ndarray):
-        if device is None:
-            raise ValueError(f"{who}: a host array needs device=")
-        points = torch.from_numpy(np.ascontiguousarray(points, np.float64 if points.dtype == np.float64 else np.float32)).to(device)
-    if not isinstance(points, torch.Tensor) or not points.is_cuda:
-        raise _lib.GsrError(f"{who}: points must live on the device (no CPU path; see {who}_host)")
-    if points.dtype != torch.float64:
-        points = points.to(torch.float32)
-    points = points.contiguous()
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"{who}: points must be [n,3], got {list(points.shape)}")
-    return points, int(points.dtype == torch.float64)
-
-
-def _points64(points):
-    p = points.detach().cpu().numpy() if isinstance(points, torch.Tensor) else np.asarray(points)
-    if p.dtype != np.float64:
-        p = p.astype(np.float32)
-    p = p.astype(np.float64).reshape(-1, 3)
-    return np.ascontiguousarray(p)
-
-
 # ---------------------------------------------------------------- SEG_HULL, SEG_MEANSTD, SEG_FILTER
 def hull_equations(points):
     """scipy's ConvexHull.equations f64 [F,4] of a host or device cloud.  Fewer than 4 points or a degenerate hull: ValueError."""
     from scipy.spatial import ConvexHull, QhullError
-    p = _points64(points)
+    p = _points64(points, keep_f64=True)
     if len(p) < 4:
         raise ValueError(f"hull_filter: a convex hull needs at least 4 points, got {len(p)}")
     try:
@@ -94,7 +64,7 @@ def _equations(equations, who):
 
 def hull_distances(points, equations=None, device=None):
     """SEG_HULL on the device: device f64 [n].  equations: [F,4] (default: scipy's hull of the points)."""
-    points, f64 = _device_points(points, device, "hull_distances")
+    points, f64 = _device_points(points, device, "hull_distances", keep_f64=True)
     eq = _equations(hull_equations(points) if equations is None else equations, "hull_distances")
     dev, n = points.device, len(points)
     eq_d = torch.from_numpy(eq).to(dev)
@@ -112,7 +82,7 @@ def mean_std(d):
     dev, n = d.device, d.numel()
     L = _lib.lib()
     out = torch.empty(2, dtype=torch.float64, device=dev)
-    ws = torch.empty(L.gsr_seg_mean_std_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.gsr_seg_mean_std_workspace_bytes(n), dev)
     with torch.cuda.device(dev):
         _lib.check(L.gsr_seg_mean_std(_ptr(d), n, _ptr(out), _ptr(ws), ws.numel(), _stream(dev)))
     return out
@@ -120,7 +90,7 @@ def mean_std(d):
 
 def hull_filter(points, theta=THETA, colors=None, normals=None, device=None, equations=None):
     """SEG_FILTER on the device: (keep bool [n], points, colors, normals) with the three arrays compacted (None stays None)."""
-    pts, _ = _device_points(points, device, "hull_filter")
+    pts, _ = _device_points(points, device, "hull_filter", keep_f64=True)
     d = hull_distances(pts, equations)
     ms = mean_std(d)
     keep = (d - ms[0]) / ms[1] >= -float(theta)
@@ -137,7 +107,7 @@ def hull_filter(points, theta=THETA, colors=None, normals=None, device=None, equ
 
 def hull_distances_host(points, equations=None):
     """SEG_HULL in numpy, facet by facet (no N x F matrix): f64 [n]."""
-    p = _points64(points)
+    p = _points64(points, keep_f64=True)
     eq = _equations(hull_equations(p) if equations is None else equations, "hull_distances_host")
     best = np.full(len(p), np.inf)
     with np.errstate(invalid="ignore", divide="ignore"):
@@ -285,14 +255,14 @@ def _seg_views(cameras, kind, shapes):
 def _prepare(points, f64, arr, n_views, label_elems):
     L = _lib.lib()
     dev = points.device
-    ws = torch.empty(L.gsr_seg_views_workspace_bytes(n_views), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.gsr_seg_views_workspace_bytes(n_views), dev)
     _lib.check(L.gsr_seg_views_prepare(_ptr(points), f64, len(points), arr, n_views, label_elems, _ptr(ws), ws.numel(), _stream(dev)))
     return ws
 
 
 def project_points(points, camera, kind, device=None):
     """SEG_PROJ_* of one view on the device: (uv f64 [n,2], z f64 [n])."""
-    points, f64 = _device_points(points, device, "project_points")
+    points, f64 = _device_points(points, device, "project_points", keep_f64=True)
     dev, n = points.device, len(points)
     arr = _seg_views([camera], kind, [(0, 0, 0, 0)])
     uv = torch.empty((n, 2), dtype=torch.float64, device=dev)
@@ -306,7 +276,7 @@ def project_points(points, camera, kind, device=None):
 def assign_segments(points, cameras, kind, label_maps, n_masks=None, device=None):
     """SEG_ASSIGN on the device: int32 [n].  label_maps: per view a device int16 [H,W] map (build_label_map) or None for a
     view without masks; n_masks: per view the number of masks (default: 1 where a map is given, which is all (a) asks)."""
-    points, f64 = _device_points(points, device, "assign_segments")
+    points, f64 = _device_points(points, device, "assign_segments", keep_f64=True)
     dev, n = points.device, len(points)
     if len(cameras) != len(label_maps):
         raise ValueError(f"assign_segments: {len(cameras)} cameras for {len(label_maps)} label maps")
@@ -334,7 +304,7 @@ def assign_segments(points, cameras, kind, label_maps, n_masks=None, device=None
 def label_points(points, cameras, kind, masks_per_view, device=None, chunk_bytes=None):
     """Step 2 of the reference on the device: the label maps view by view, then one assignment.  masks_per_view: per view
     [M,H,W] masks (or None / an empty list).  Returns (labels int32 [n] on the device, mask_areas dict)."""
-    points, _ = _device_points(points, device, "label_points")
+    points, _ = _device_points(points, device, "label_points", keep_f64=True)
     maps, areas, counts = [], [], []
     for masks in masks_per_view:
         if masks is None or len(masks) == 0:
@@ -351,7 +321,7 @@ def _nan_to_num(a):
 
 def project_points_host(points, camera, kind):
     """SEG_PROJ_* in numpy, term by term as the rules state them: (uv f64 [n,2], z f64 [n])."""
-    p = _points64(points)
+    p = _points64(points, keep_f64=True)
     t = camera_terms(camera, kind)
     x, y, z = p[:, 0], p[:, 1], p[:, 2]
     Wm, K = t["world_mat"], t["camera_mat"]
@@ -387,7 +357,7 @@ def project_points_host(points, camera, kind):
 
 def assign_segments_host(points, cameras, kind, label_maps, n_masks=None):
     """SEG_ASSIGN in numpy: int32 [n].  label_maps: per view an int16 [H,W] array or None."""
-    p = _points64(points)
+    p = _points64(points, keep_f64=True)
     out = np.full(len(p), -1, np.int32)
     for i, (cam, lm) in enumerate(zip(cameras, label_maps)):
         m = (0 if lm is None else 1) if n_masks is None else int(n_masks[i])

@@ -23,6 +23,8 @@ import torch
 
 from . import _lib
 from . import mesh_eval as ME
+from ._dev import (device_points as _device_points, points64 as _points64, ptr as _ptr, stream as _stream,
+                   workspace as _workspace)
 from .mesh import DeviceTriangleMesh, TriangleMesh
 
 MAX_POINT_NUMBER = 4e6
@@ -32,7 +34,6 @@ AXES = {"X": 0, "Y": 1, "Z": 2}
 SCENE_TAU = {"Barn": 0.01, "Caterpillar": 0.005, "Church": 0.025, "Courthouse": 0.025, "Ignatius": 0.003, "Meetingroom": 0.01,
              "Truck": 0.005}
 
-_ptr, _stream, _device_points, _points64 = ME._ptr, ME._stream, ME._device_points, ME._points64
 
 
 def _hp(a):
@@ -140,7 +141,7 @@ def voxel_down_sample(points, voxel_size, device=None, return_cells=False):
     points = _device_points(points, device, "voxel_down_sample")
     L = _lib.lib()
     dev, n = points.device, len(points)
-    ws = torch.empty(L.gsr_points_voxel_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.gsr_points_voxel_workspace_bytes(n), dev)
     cells = torch.empty(n, dtype=torch.int32, device=dev) if return_cells else None
     with torch.cuda.device(dev):
         m = C.c_int64()
@@ -171,7 +172,7 @@ def icp_sums(source, target, dist, idx, means=None):
     L = _lib.lib()
     dev, n = source.device, len(source)
     mu = None if means is None else np.ascontiguousarray(np.asarray(means, np.float64).reshape(6))
-    ws = torch.empty(L.gsr_icp_sums_workspace_bytes(n), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.gsr_icp_sums_workspace_bytes(n), dev)
     out = torch.empty(10, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         _lib.check(L.gsr_icp_sums(_ptr(source), n, _ptr(target), len(target), _ptr(dist), _ptr(idx),
@@ -193,7 +194,7 @@ def score_distances(dist, tau, edges):
     dist = dist.contiguous().reshape(-1)
     L = _lib.lib()
     dev, n = dist.device, dist.numel()
-    ws = torch.empty(L.gsr_dist_score_workspace_bytes(B), dtype=torch.uint8, device=dev)
+    ws = _workspace(L.gsr_dist_score_workspace_bytes(B), dev)
     out = torch.empty(1 + B, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         _lib.check(L.gsr_dist_score(_ptr(dist), n, _hp(edges), B, tau, _ptr(ws), ws.numel(), _ptr(out), _ptr(out[1:]), _stream(dev)))

@@ -15,7 +15,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _dev, _lib
 
 BLOCK = 16
 
@@ -97,7 +97,7 @@ class TSDFVolume:
             raise _lib.GsrError("the TSDF block AABB is empty but the view has valid depth")
         mp = C.c_void_p(m.data_ptr()) if m is not None else None
         with torch.cuda.device(self.device):
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            stream = _dev.stream(self.device)
             n_touched = C.c_int64()
             _lib.check(L.gsr_tsdf_touch(C.byref(self._v), C.c_void_p(d.data_ptr()), mp, H, W, intr, M, float(depth_trunc),
                                         C.byref(n_touched), stream))
@@ -173,9 +173,9 @@ class TSDFVolume:
         from .mesh import DeviceTriangleMesh, TriangleMesh
         L = _lib.lib()
         A = self.n_alloc
-        ws = torch.empty(max(1, L.gsr_mcubes_workspace_bytes(A)), dtype=torch.uint8, device=self.device)
+        ws = _dev.workspace(L.gsr_mcubes_workspace_bytes(A), self.device)
         with torch.cuda.device(self.device):
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            stream = _dev.stream(self.device)
             nv, nt = C.c_int64(), C.c_int64()
             _lib.check(L.gsr_mcubes_count(C.byref(self._v), C.c_void_p(ws.data_ptr()), ws.numel(), C.byref(nv), C.byref(nt),
                                           stream))

@@ -1,7 +1,8 @@
 """TEST-ONLY vectorised float64 restatements of EVAL_DOWNSAMPLE and TNT_VOXEL (include/gsr.h) for clouds of hundreds of
 thousands of points, where the scalar loops of tests/mesh_eval_ref.py and tests/tnt_eval_ref.py take minutes.  They state the
 same rules with the same float64 expressions; tests/test_cloud_scale_ref_cpu.py holds them to the scalar ones bit for bit on
-every fixture of the two GPU modules.  (EVAL_NN needs nothing new: mesh_eval_ref.nearest is cKDTree's own query.)"""
+every fixture of the two GPU modules.  (EVAL_NN needs nothing new: mesh_eval_ref.nearest is cKDTree's own query.)
+fixed_order_sum states the one summation order of EVAL_MEAN, SEG_MEANSTD and TNT_ICP_SUMS, held to a scalar loop there too."""
 import numpy as np
 from scipy.spatial import cKDTree
 
@@ -55,3 +56,42 @@ def voxel_fast(points, voxel_size):
         np.add.at(acc[:, a], row, p[:, a])                          # unbuffered: element by element, k = 0, 1, 2, ...
     count = np.bincount(row, minlength=cells).astype(np.float64)
     return (acc / count[:, None]).astype(np.float32), row.astype(np.int32)
+
+
+def wide_values(n, seed):
+    """finite, non-negative, seventeen decades wide: the low bits of any sum depend on its order"""
+    rng = np.random.default_rng(seed)
+    return rng.random(n) * 10.0 ** rng.integers(-8, 9, size=n)
+
+
+def _tree_256(acc):
+    """acc [rows, 256] -> [rows]: column t += column t + d for d = 128, 64, ..., 1"""
+    acc = acc.copy()
+    d = 128
+    while d:
+        acc[:, :d] += acc[:, d:2 * d]
+        d //= 2
+    return acc[:, 0]
+
+
+def fixed_order_sum(x):
+    """The fixed-order float64 sum of the device (include/gsr.h, EVAL_MEAN): min(1024, ceil(n / 256)) workgroups of 256 threads,
+    thread t of workgroup b adds x[b * 256 + t], x[b * 256 + t + blocks * 256], ... to 0.0 in that order; a tree adds the 256
+    values of a workgroup; one workgroup adds the partials the same way (thread t takes partials t, t + 256, ...).  The
+    missing elements of the last trip are +0.0, which changes no sum of values that are not -0.0."""
+    x = np.asarray(x, np.float64).reshape(-1)
+    n = len(x)
+    blocks = min(1024, -(-n // 256))
+    if blocks == 0:
+        return 0.0
+
+    def threads(v, width):                                  # [trips, width] added trip after trip
+        trips = -(-len(v) // width)
+        rows = np.concatenate([v, np.zeros(trips * width - len(v))]).reshape(trips, width)
+        acc = np.zeros(width)
+        for r in rows:
+            acc = acc + r
+        return acc
+
+    partial = _tree_256(threads(x, blocks * 256).reshape(blocks, 256))
+    return float(_tree_256(threads(partial, 256).reshape(1, 256))[0])

@@ -56,3 +56,35 @@ def test_voxel_fast_sums_in_input_order():
     assert len(want) == 1 and not row.any() and np.array_equal(got.view(np.uint32), want.view(np.uint32))
     pairwise = np.array([np.ascontiguousarray(pts[:, a].astype(np.float64)).sum() / len(pts) for a in range(3)]).astype(np.float32)
     assert (pairwise.view(np.uint32) != want.view(np.uint32)).all()
+
+
+@pytest.mark.parametrize("n", [0, 1, 255, 257, 4099, 262145 + 513])
+def test_fixed_order_sum_equals_scalar(n):
+    """the scalar statement: every thread's own loop, the tree as a loop over threads, the partials the same way"""
+    x = F.wide_values(n, 7 + n)
+
+    def tree(v):
+        v, d = list(v), 128
+        while d:
+            for t in range(d):
+                v[t] += v[t + d]
+            d //= 2
+        return v[0]
+
+    def group(v, first, stride):                            # the workgroup whose thread t starts at first + t
+        out = []
+        for t in range(256):
+            acc = 0.0
+            for e in v[first + t::stride]:
+                acc += e
+            out.append(acc)
+        return tree(out)
+
+    v = x.tolist()
+    blocks = min(1024, -(-n // 256))
+    partial = [group(v, b * 256, blocks * 256) for b in range(blocks)]
+    want = group(partial, 0, 256) if blocks else 0.0
+    got = F.fixed_order_sum(x)
+    assert np.float64(got).view(np.uint64) == np.float64(want).view(np.uint64)
+    if n >= 255:
+        assert got != float(np.cumsum(x)[-1])               # a sequential sum is another number: the order shows

@@ -9,33 +9,37 @@ here = this module):
 
   constant / grid                        path changes at                      below                             above
   -------------------------------------  -----------------------------------  --------------------------------  ------------------------------------
+  cloud_common.h (one copy for knn.hip, mesh_eval.hip, tnt_eval.hip and seg_init.hip)
+    cloud_bounds_kernel<true> on         262 145 points                       KN knn 200 000, here knn N_TOP,   here knn N_TOP + 1, 300 * 1024 + 1,
+      gsr_partial_blocks, 1 024 x 256                                         here nearest N_TOP                nearest N_TOP + 1 (corner point last)
+    cloud_bounds_kernel<false>           262 145 points                       TN voxel n20000                   here voxel N_TOP + 1, 2 N_TOP + 3
+    gsr_block_sum_256: second thread     2 values                             here fixed_order_sums 1           here fixed_order_sums 255
+      second workgroup                   257 values                           ME distance_mean 255, 256         here fixed_order_sums 257, ME distance_mean 257
+      final workgroup's second trip      257 partials = 65 537 values         TN icp_sums 20000                 here fixed_order_sums 65 537, icp_sums N_TOP
+      gsr_partial_blocks, 1 024 x 256    262 145 values                       ME distance_mean N_TOP            here fixed_order_sums N_TOP + 1; ME distance_mean
+                                                                                                                N_TOP + 1, 300 001
   mesh_eval.hip
     ME_LEAF: second leaf                 65 points                            ME downsample n63, n64            ME downsample n65
     ME_LEAF^2: second node               4 097 points                         ME random_3000                    ME downsample n4097, nearest 4097 x 5000
     ME_LEAF^3: second top box            262 145 points (nt = 2)              here nearest N_TOP                here nearest / downsample N_TOP + 1
     ne = min(T.nn, ...): ragged last     a last top box that is not full      here nearest N_TOP (full box)     here nearest N_TOP + 1 (one node, one leaf,
       top box                                                                                                   one point), 2 N_TOP + 4096 + 65 (nt = 3)
-    me_bounds_kernel, 1 024 x 256        262 145 cloud points                 here nearest N_TOP                here nearest N_TOP + 1 (corner point last)
     queries: m = max(n, nq), qorder      nq > n; 262 145 queries              ME nearest 4097 x 5000, 5000 x 1  here 300 000 queries x N_TOP + 1
     ME_MIS_BATCH: second read-back       9 rounds                             ME downsample n1 (one round)      ME sorted_line_2000 (>= 100 rounds)
-    ME_MEAN_BLOCKS (gsr_dist_mean)       262 145 distances                    ME distance_mean 257, N_TOP       ME distance_mean N_TOP + 1, 300 001
     ext > 0 ? ... : 0 (flat axis)        an axis without extent               every other cloud                 here collapse flat_z, line_x; ME nearest 5000 x 1
   knn.hip
     KNN_BOX: second box                  1 025 points                         KN knn 4, 1000                    KN knn 3000, 20 000, 200 000
-    knn_bounds_kernel, 1 024 x 256       262 145 points                       KN knn 200 000, here knn N_TOP    here knn N_TOP + 1, 300 * 1024 + 1
     ragged last box beyond one trip      300 * 1024 + 1 points                here knn N_TOP (full boxes)       here knn 300 * 1024 + 1
     ext > 0 ? ... : 0 (flat axis)        an axis without extent               every other cloud                 KN knn planar; here collapse flat_z, line_x
   tnt_eval.hip
-    te_min_kernel, 1 024 x 256           262 145 points                       TN voxel n20000                   here voxel N_TOP + 1, 2 N_TOP + 3
-    te_sums_kernel, TE_SUM_BLOCKS        262 145 source points                TN icp_sums 20000, here N_TOP     here icp_sums N_TOP + 1, 2 N_TOP + 257
-    te_sums_final_kernel, 256 threads    257 partials = 65 537 points         TN icp_sums 20000                 here icp_sums N_TOP
+    te_sums_kernel's own loop            262 145 source points                TN icp_sums 20000, here N_TOP     here icp_sums N_TOP + 1, 2 N_TOP + 257
     te_score_kernel, 1 024 x 256         262 145 distances                    TN score 20000                    here score N_TOP + 1, 2 N_TOP + 3
     TE_MAX_BINS                          4 097 bins (refused)                 TN score B = 4096                 TN score_refuses_too_many_bins
     TE_MAX_POLY                          257 vertices (refused)               TN crop_polygon_sizes 256         TN crop_polygon_sizes 257
     TE_CELL_LIMIT                        2^21 cells on an axis (refused)      TN voxel 10 / 2^20                TN voxel_refuses_too_many_cells
   seg_init.hip
-    seg_sum_partial_kernel,              262 145 distances                    SI mean_std filter (20 300)       SI mean_std_edges 300 000;
-      SEG_SUM_BLOCKS                                                                                            here mean_std N_TOP + 1, 2 N_TOP + 3
+    seg_sum_partial_kernel's own loop    262 145 distances                    SI mean_std filter (20 300)       SI mean_std_edges 300 000;
+                                                                                                                here mean_std N_TOP + 1, 2 N_TOP + 3
     seg_box_kernel, 1 024 x 256          262 145 points                       SI project_points_sizes tyt       here project tyt N_TOP + 1, 2 N_TOP + 3
     seg_dtu_count_kernel, 1 024 x 256    262 145 points                       SI project_points_sizes dtu       here project dtu N_TOP + 1, 2 N_TOP + 3
     SEG_FACET_CHUNK                      513 facets                           SI hull gauss (600 points)        SI hull sphere, filter
@@ -45,10 +49,11 @@ here = this module):
     MV_VOTE_VIEWS                        65 views                             MV vote n = 8                     MV vote_special_vertices (72 views)
 
 The search results never depend on how good the Morton codes are -- only the time does -- so the far outlier and the flat
-clouds hold that exactness to the same bars.  For the same reason no result can tell whether me_bounds_kernel and
-knn_bounds_kernel saw the whole cloud (a point outside the bounds is clamped into them): these cases run their second trip
-with the box's corner in it, and hold what is computed from it to the bars; the second trips of te_min_kernel,
-te_sums_kernel, te_score_kernel, seg_sum_partial_kernel, seg_box_kernel and seg_dtu_count_kernel each decide a result here.  The last 200 points of the nearest-neighbour clouds are placed in the corner
+clouds hold that exactness to the same bars.  For the same reason no result of a search can tell whether
+cloud_bounds_kernel<true> saw the whole cloud (a point outside the bounds is clamped into them): these cases run their second trip
+with the box's corner in it, and hold what is computed from it to the bars; the voxel grid runs the same loop and does show it.
+The second trips of cloud_bounds_kernel<false>, te_sums_kernel, te_score_kernel, seg_sum_partial_kernel, seg_box_kernel and
+seg_dtu_count_kernel each decide a result here.  The last 200 points of the nearest-neighbour clouds are placed in the corner
 cell of the box: they have the highest codes, so they are the ragged tail of the sorted order, which the test asserts."""
 import numpy as np
 import pytest
@@ -255,6 +260,26 @@ def test_score_beyond_one_grid_trip(B):
             assert hist[-1] >= 5 and hist.sum() < n
         assert TE.score_distances(dd, tau, edges)[1].tolist() == hist.tolist()
         assert TE.score_distances_host(d, tau, edges)[0] == count
+
+
+# ---------------------------------------------------------------- one fixed-order sum behind EVAL_MEAN and SEG_MEANSTD
+@pytest.mark.parametrize("n", [1, 255, 257, 65537, N_TOP + 1])
+def test_fixed_order_sums_agree(n):
+    """gsr_dist_mean and gsr_seg_mean_std add the same vector in the same order (gsr_block_sum_256): their means are one bit
+    pattern, and it is the one of the restated order.  n: one thread, one short workgroup, two workgroups, 257 partials (the
+    final workgroup's second trip), the capped grid's second trip."""
+    from gaussmart_amd.mesh_eval import distance_mean
+    x = F.wide_values(n, 501 + n)                          # change the seed if the last assertion fails, never the bar
+    d = _dev(x, np.float64)
+    mean, count = distance_mean(d)
+    seg = float(SI.mean_std(d).cpu().numpy()[0])
+    want = F.fixed_order_sum(x) / n
+    bits = lambda v: int(np.float64(v).view(np.uint64))
+    print(f"fixed order {n}: dist_mean {mean!r}, seg_mean_std {seg!r}, restated {want!r}, sequential {np.cumsum(x)[-1] / n!r}")
+    assert count == n
+    assert bits(mean) == bits(seg) == bits(want)
+    if n >= 255:
+        assert float(np.cumsum(x)[-1]) != F.fixed_order_sum(x)       # the vector tells one order from another
 
 
 # ---------------------------------------------------------------- segment init: mean / std, bounding box, DTU in-view count
