@@ -16,7 +16,8 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSR_LIB_PATH: developer aid for same-box A/B runs of two builds of the library (scripts/ab_builds.sh)
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "lib", "libgsr_hip.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
+GSR_LPIPS_ALEX, GSR_LPIPS_VGG = 0, 1
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_SCRATCH, GSR_BUF_SCRATCH2 = range(5)
 GSR_BUF_SYNC_SH = 100     # not a buffer: "the SH colour pass is about to be enqueued" (GSR_FLAG_DEFER_COLOR)
@@ -316,7 +317,14 @@ def lib():
                 ("gsr_unb_block_flags", C.c_int32, [vp, C.c_int32, f64, C.c_int32, C.c_int32, fp, C.c_float, C.c_float, vp, vp]),
                 ("gsr_unb_alloc", C.c_int32, [V, C.c_int32, C.c_int32, vp, vp]),
                 ("gsr_unb_fill", C.c_int32, [V, vp, C.c_int32, f64, C.c_int32, C.c_int32, fp, C.c_float, C.c_float, vp]),
-                ("gsr_unb_finish", C.c_int32, [vp, i64, f64, C.c_int32, C.c_int32, fp, C.c_float, C.c_float, vp])):
+                ("gsr_unb_finish", C.c_int32, [vp, i64, f64, C.c_int32, C.c_int32, fp, C.c_float, C.c_float, vp]),
+                ("gsr_lpips_conv", C.c_int32, [vp, vp, vp] + [C.c_int32] * 9 + [vp, vp]),
+                ("gsr_lpips_pool", C.c_int32, [vp, i64, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
+                ("gsr_lpips_head_workspace_bytes", sz, []),
+                ("gsr_lpips_head", C.c_int32, [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, sz, vp, vp]),
+                ("gsr_lpips_workspace_bytes", sz, [C.c_int32, C.c_int32, C.c_int32]),
+                ("gsr_lpips_forward", C.c_int32, [C.c_int32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, C.c_int32,
+                                                  C.c_int32, C.c_int32, vp, sz, vp, vp])):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]

@@ -1,6 +1,7 @@
 """Command-line training entry: the build's counterpart of the reference's train.py / render.py
 front ends for the hot path (scene in -> optimised surfels + PSNR out).  SAM / DINO preprocessing,
-LPIPS, TensorBoard and the viewer socket of the reference are out of scope.
+TensorBoard and the viewer socket of the reference are out of scope; SSIM, PSNR
+and LPIPS of the rendered test views come from gaussmart_amd.metrics_cli, not from this command.
 
     python -m gaussmart_amd.train_cli -s <colmap-or-blender-scene> -m <output dir> [--iterations 30000] [--eval]
     torchrun --nproc-per-node 8 -m gaussmart_amd.train_cli -s ... -m ...        # view-parallel

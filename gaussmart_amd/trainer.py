@@ -3,8 +3,10 @@
 Counterpart of training() in the reference (train.py:45-243): random view, render, loss
 0.8*L1 + 0.2*(1-SSIM) + lambda_normal*normal + lambda_dist*dist, backward, densification
 bookkeeping, Adam step.  The reference's per-iteration `.item()` calls, CSV append, TensorBoard,
-DINO scalar (no gradient, needs a network fetch), LPIPS and the viewer socket are left out: none
-of them reaches the rasterizer, and the host syncs they cause are a throughput hazard.
+DINO scalar (no gradient, needs a network fetch), the LPIPS of its test report and the viewer socket
+are left out of the loop: none of them reaches the rasterizer, and the host syncs they cause are a
+throughput hazard.  LPIPS itself is built (gaussmart_amd.lpips, from local weight files) and is
+reported by metrics_cli.
 """
 import random
 import time

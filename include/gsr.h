@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 14  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
+#define GSR_ABI_VERSION 15  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
                                 6: gsr_surface_maps_forward / _backward;
                                 7: TSDF fusion and marching cubes (GsrTsdfVolume, gsr_tsdf_*, gsr_mcubes_*);
                                 8: mesh post-processing (gsr_mesh_*) and gsr_depth_aabb;
@@ -44,7 +44,8 @@ extern "C" {
                                 12: Tanks-and-Temples mesh evaluation (gsr_mesh_face_centres, gsr_points_transform / _crop_polygon /
                                     _voxel_*, gsr_icp_sums, gsr_dist_score);
                                 13: segment-aware initialisation of the point cloud (GsrSegView, gsr_seg_*);
-                                14: unbounded mesh export (GsrUnbView, gsr_unb_*) */
+                                14: unbounded mesh export (GsrUnbView, gsr_unb_*);
+                                15: LPIPS (gsr_lpips_*) */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -996,6 +997,56 @@ int32_t gsr_unb_fill(const GsrTsdfVolume* vol, const GsrUnbView* views, int32_t 
                      int32_t crop, const float* center_host, float radius, float trunc, gsr_stream_t stream);
 int32_t gsr_unb_finish(float* verts, int64_t n, double R, int32_t resolution, int32_t crop, const float* center_host,
                        float radius, float max_range, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- LPIPS
+ * The reference's lpipsPyTorch (modules/lpips.py, networks.py, utils.py; called at metrics.py:73 and train.py:326) as kernels
+ * (lpips.hip; Python: gaussmart_amd/lpips.py): the AlexNet / VGG16 trunk on the pair of images as a batch of 2, and after each
+ * tapped layer the distance of the two unit-normalised feature maps.  fp32 throughout, no reduced-precision format.  Rules:
+ *   LP_CONV     y[b,co,oy,ox] = relu(bias[co] + sum_k w[co,k] x[b,ci,oy s - p + ky,ox s - p + kx]); x, y NCHW f32, w
+ *               [C_out,C_in,ks,ks] as torch lays it out, zero padding.  The sum is ONE f32 fma chain from 0 over
+ *               k = (ci ks + ky) ks + kx ascending (the f32-input matrix instruction), then + bias, then relu; no split over k
+ *               and no atomics, so the bits do not depend on the run, the tile or the image's place in the batch.  ks in
+ *               {3, 5, 11}; any stride >= 1, pad >= 0, C_in, C_out >= 1 and any output plane >= 1x1.  zscore != 0 (C_in == 3
+ *               only): every element read from inside the image is first taken through BaseNet.z_score, (x - mean[ci]) /
+ *               std[ci] with mean (-.030, -.088, -.188) and std (.458, .448, .450) as f32 and a true division; the padding
+ *               stays 0.
+ *   LP_POOL     torch's max_pool2d(ks, stride 2) in floor mode without padding, ks 2 (VGG) or 3 (AlexNet): out = (n - ks) / 2
+ *               + 1 per axis; the maximum starts at -inf and a NaN wins.  H, W >= ks.
+ *   LP_HEAD     feat f32 [2,C,H,W] (the pair), lin_w f32 [C]; per pixel nx = sqrt(sum_c x_c^2) + 1e-10 (ny likewise) and
+ *               v = sum_c w_c (x_c / nx - y_c / ny)^2, every operation in f32 (modules/utils.py:6-8, modules/lpips.py:33-36).
+ *               The 256 threads of a workgroup are 8 channel groups x 32 consecutive pixels; a thread adds its C / 8
+ *               channels in ascending order and the 8 groups' norms are added in order 0..7.  The mean over H W is the fixed
+ *               order of EVAL_MEAN: a thread adds the values of its pixels in index order, the tree d = 128 .. 1 adds the 256
+ *               threads, ONE workgroup adds the min(ceil(H W / 32), 1024) partials the same way and divides by H W.  C a
+ *               multiple of 8 in [8, 512] (else GSR_E_UNSUPPORTED).  The maps are read once.
+ *   LP_FORWARD  taps: VGG after the relus of conv 1_2, 2_2, 3_3, 4_3, 5_3; AlexNet after each of its five relus (its last pool
+ *               is never computed).  A head runs as soon as its layer exists; the five values are added in layer order,
+ *               (((l0 + l1) + l2) + l3) + l4.  The workspace is two activation buffers of 2 x 64 x (first layer's output
+ *               plane) floats, the head's partials and five floats.  Minimum image: 16x16 for VGG (four pools), 31x31 for
+ *               AlexNet (11x11 stride 4 pad 2, then two 3x3 pools).
+ *
+ *   gsr_lpips_conv  : LP_CONV; y device f32 [B,C_out,OH,OW], OH = (H + 2 pad - ks) / stride + 1.
+ *   gsr_lpips_pool  : LP_POOL on `planes` planes of H x W.
+ *   gsr_lpips_head  : LP_HEAD; out device f32 [1]; ws: gsr_lpips_head_workspace_bytes().
+ *   gsr_lpips_forward : conv_w_host / conv_b_host: HOST arrays of the trunk's device pointers in layer order (5 for AlexNet,
+ *                     13 for VGG16); lin_w_host: host array of 5 device pointers f32 [C_l]; img0, img1 device f32 [3,H,W],
+ *                     taken as they are (the caller's value range); out device f32 [1]; ws: gsr_lpips_workspace_bytes(net, H,
+ *                     W) (0 for an unknown net or an empty image).
+ * None of these calls synchronises.  An image below the minimum, channels != 3, a null pointer, an unknown net or kernel
+ * size, a workspace that is too small: GSR_E_INVALID / GSR_E_UNSUPPORTED before anything is launched, with a message.  All
+ * element offsets are 64-bit. */
+#define GSR_LPIPS_ALEX 0
+#define GSR_LPIPS_VGG 1
+int32_t gsr_lpips_conv(const float* x, const float* w, const float* bias, int32_t B, int32_t C_in, int32_t H, int32_t W,
+                       int32_t C_out, int32_t ksize, int32_t stride, int32_t pad, int32_t zscore, float* y, gsr_stream_t stream);
+int32_t gsr_lpips_pool(const float* x, int64_t planes, int32_t H, int32_t W, int32_t ksize, float* y, gsr_stream_t stream);
+size_t gsr_lpips_head_workspace_bytes(void);
+int32_t gsr_lpips_head(const float* feat, const float* lin_w, int32_t C, int32_t H, int32_t W, void* ws, size_t ws_bytes,
+                       float* out, gsr_stream_t stream);
+size_t gsr_lpips_workspace_bytes(int32_t net, int32_t H, int32_t W);
+int32_t gsr_lpips_forward(int32_t net, const float* const* conv_w_host, const float* const* conv_b_host,
+                          const float* const* lin_w_host, const float* img0, const float* img1, int32_t channels, int32_t H,
+                          int32_t W, void* ws, size_t ws_bytes, float* out, gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only
