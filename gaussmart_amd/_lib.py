@@ -16,7 +16,7 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSR_LIB_PATH: developer aid for same-box A/B runs of two builds of the library (scripts/ab_builds.sh)
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "lib", "libgsr_hip.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 GSR_LPIPS_ALEX, GSR_LPIPS_VGG = 0, 1
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_SCRATCH, GSR_BUF_SCRATCH2 = range(5)
@@ -324,7 +324,14 @@ def lib():
                 ("gsr_lpips_head", C.c_int32, [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, sz, vp, vp]),
                 ("gsr_lpips_workspace_bytes", sz, [C.c_int32, C.c_int32, C.c_int32]),
                 ("gsr_lpips_forward", C.c_int32, [C.c_int32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, C.c_int32,
-                                                  C.c_int32, C.c_int32, vp, sz, vp, vp])):
+                                                  C.c_int32, C.c_int32, vp, sz, vp, vp]),
+                ("gsr_frame_to_u8", C.c_int32, [vp] + [C.c_int32] * 4 + [vp, vp]),
+                ("gsr_frame_order_stats_workspace_bytes", sz, [i64]),
+                ("gsr_frame_order_stats", C.c_int32, [vp, i64, C.POINTER(i64), C.c_int32, fp, vp, sz, vp]),
+                ("gsr_frame_depth_vis", C.c_int32, [vp, C.c_int32, C.c_int32, C.c_int32, f64, f64, vp, vp, vp, vp]),
+                ("gsr_frame_sobel", C.c_int32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
+                ("gsr_frame_minmax", C.c_int32, [vp, i64, vp, vp]),
+                ("gsr_frame_colormap", C.c_int32, [vp, C.c_int32, C.c_int32, vp, vp, vp, vp])):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]

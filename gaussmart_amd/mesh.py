@@ -356,10 +356,25 @@ class GaussianExtractor:
             "implemented yet; it is the follow-up of the bounded mesh export.  Use extract_mesh_bounded.")
 
     @torch.no_grad()
-    def export_image(self, path):
+    def export_image(self, path, host=False):
+        """renders/NNNNN.png, gt/NNNNN.png and vis/depth_NNNNN.tiff of every view.  Default: the colours become u8 and the
+        depth is cleaned on the device (gaussmart_amd/frames.py) and only those bytes are copied down; host=True copies the
+        fp32 maps and converts with numpy.  Both write the same files, byte for byte."""
         render_path, gts_path, vis_path = (os.path.join(path, d) for d in ("renders", "gt", "vis"))
         for d in (render_path, vis_path, gts_path):
             os.makedirs(d, exist_ok=True)
+        if not host:
+            from PIL import Image
+            from .frames import clean_depth, to_u8
+            for idx, cam in enumerate(self.viewpoint_stack):
+                dev = self.rgbmaps[idx].device
+                if cam.original_image is not None:
+                    Image.fromarray(to_u8(cam.original_image[0:3].to(dev)).cpu().numpy()).save(
+                        os.path.join(gts_path, f"{idx:05d}.png"), "PNG")
+                Image.fromarray(to_u8(self.rgbmaps[idx]).cpu().numpy()).save(os.path.join(render_path, f"{idx:05d}.png"), "PNG")
+                Image.fromarray(clean_depth(self.depthmaps[idx][0]).cpu().numpy()).save(
+                    os.path.join(vis_path, f"depth_{idx:05d}.tiff"), "TIFF")
+            return
         for idx, cam in enumerate(self.viewpoint_stack):
             if cam.original_image is not None:
                 _save_img_u8(cam.original_image[0:3].permute(1, 2, 0).cpu().numpy(), os.path.join(gts_path, f"{idx:05d}.png"))

@@ -1,13 +1,19 @@
-"""Command-line rendering and mesh export, the counterpart of the reference's render.py (bounded TSDF path):
+"""Command-line rendering, mesh export and trajectory videos, the counterpart of the reference's render.py (bounded TSDF path):
 
     python -m gaussmart_amd.render_cli -s <scene> -m <model dir> [--iteration -1] [--skip_train] [--skip_test]
         [--skip_mesh] [--voxel_size V] [--depth_trunc D] [--sdf_trunc S] [--num_cluster 50] [--mesh_res 1024]
-        [--depth_ratio R] [--host_post_process]
+        [--depth_ratio R] [--host_post_process] [--render_path [--n_frames 240] [--host]]
 
 Writes MODEL/{train,test}/ours_<it>/{renders,gt,vis} and MODEL/train/ours_<it>/fuse.ply, fuse_post.ply (what the reference's
 scripts/dtu_eval_mesh.py reads).  The mesh stays on the device from marching cubes to the PLY writer (cluster filter as
-kernels); --host_post_process runs the numpy + scipy filter instead and writes the same bytes.  --unbounded and --render_path
-are not supported here; `python -m gaussmart_amd.unbounded_cli` meshes unbounded scenes.
+kernels); --host_post_process runs the numpy + scipy filter instead and writes the same bytes.
+
+--render_path (render.py:73-84) renders --n_frames views on an ellipse through the training cameras
+(gaussmart_amd/render_path.py) and writes MODEL/traj/ours_<it>/{renders,vis}, render_traj_color.avi and render_traj_depth.avi
+(Motion-JPEG; the reference's .mp4 where mediapy is installed).  The frames are converted by kernels next to the maps
+(gaussmart_amd/frames.py); --host converts with numpy and makes the videos from the files, like the reference.
+
+--unbounded is not supported here; `python -m gaussmart_amd.unbounded_cli` meshes unbounded scenes.
 """
 import argparse
 import os
@@ -19,7 +25,9 @@ from .gaussian_model import GaussianModel
 from .gaussian_renderer import render
 from .mesh import GaussianExtractor, post_process_mesh, post_process_mesh_device
 from .params import PipelineParams
+from .render_path import generate_path
 from .scene_io import Scene
+from .video import export_trajectory
 
 
 def main(argv=None):
@@ -37,7 +45,10 @@ def main(argv=None):
     ap.add_argument("--skip_test", action="store_true")
     ap.add_argument("--skip_mesh", action="store_true")
     ap.add_argument("--quiet", action="store_true")
-    ap.add_argument("--render_path", action="store_true")
+    ap.add_argument("--render_path", action="store_true", help="render a fly-around of the scene and make videos of it")
+    ap.add_argument("--n_frames", default=240, type=int, help="Trajectory: number of frames")
+    ap.add_argument("--host", action="store_true",
+                    help="Trajectory: convert the frames on the host and make the videos from the written files")
     ap.add_argument("--voxel_size", default=-1.0, type=float, help="Mesh: voxel size for TSDF")
     ap.add_argument("--depth_trunc", default=-1.0, type=float, help="Mesh: Max depth range for TSDF")
     ap.add_argument("--sdf_trunc", default=-1.0, type=float, help="Mesh: truncation value for TSDF")
@@ -50,8 +61,6 @@ def main(argv=None):
     if args.unbounded:
         sys.exit("render_cli: --unbounded is not supported (only the bounded TSDF mesh path is implemented here); "
                  "`python -m gaussmart_amd.unbounded_cli` with the same arguments meshes an unbounded scene")
-    if args.render_path:
-        sys.exit("render_cli: --render_path (trajectory videos) is not supported")
     print("Rendering " + args.model_path)
 
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -75,6 +84,13 @@ def main(argv=None):
         os.makedirs(test_dir, exist_ok=True)
         ex.reconstruction(scene.getTestCameras())
         ex.export_image(test_dir)
+
+    if args.render_path:
+        print("render videos ...")
+        traj_dir = os.path.join(args.model_path, "traj", f"ours_{scene.loaded_iter}")
+        os.makedirs(traj_dir, exist_ok=True)
+        ex.reconstruction(generate_path(scene.getTrainCameras(), n_frames=args.n_frames))
+        export_trajectory(ex, traj_dir, "render_traj", host=args.host)
 
     if not args.skip_mesh:
         print("export mesh ...")

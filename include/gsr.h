@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 15  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
+#define GSR_ABI_VERSION 16  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
                                 6: gsr_surface_maps_forward / _backward;
                                 7: TSDF fusion and marching cubes (GsrTsdfVolume, gsr_tsdf_*, gsr_mcubes_*);
                                 8: mesh post-processing (gsr_mesh_*) and gsr_depth_aabb;
@@ -45,7 +45,8 @@ extern "C" {
                                     _voxel_*, gsr_icp_sums, gsr_dist_score);
                                 13: segment-aware initialisation of the point cloud (GsrSegView, gsr_seg_*);
                                 14: unbounded mesh export (GsrUnbView, gsr_unb_*);
-                                15: LPIPS (gsr_lpips_*) */
+                                15: LPIPS (gsr_lpips_*);
+                                16: frame kernels of the trajectory and viewer pictures (gsr_frame_*) */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -1047,6 +1048,56 @@ size_t gsr_lpips_workspace_bytes(int32_t net, int32_t H, int32_t W);
 int32_t gsr_lpips_forward(int32_t net, const float* const* conv_w_host, const float* const* conv_b_host,
                           const float* const* lin_w_host, const float* img0, const float* img1, int32_t channels, int32_t H,
                           int32_t W, void* ws, size_t ws_bytes, float* out, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- frame kernels
+ * The reference's utils/render_utils.py (save_img_u8, save_img_f32, create_videos:219-266) and utils/image_utils.py
+ * (gradient_map, colormap) on maps that already sit in device memory (frame.hip; Python: gaussmart_amd/frames.py): only u8
+ * frames, and the fp32 depth a TIFF needs, have to cross to the host.  Rules:
+ *   FRAME_U8        uint8(clip(nan_to_num(x), 0, 1) * 255.0f): NaN -> 0, +inf -> 255, -inf -> 0, ONE fp32 multiply, truncation.
+ *                   in f32 [B,C,H,W], C in {1, 3, 4}; out u8 [B,H,W,C].  W % 4 == 0 (and a 16-byte aligned input): a thread
+ *                   takes four consecutive pixels of a row, one 16-byte load per channel plane, its 4 C bytes stored as whole
+ *                   dwords; otherwise one pixel per thread.  Both paths give the same bytes.
+ *   FRAME_STATS     the elements at k <= 8 given ranks (0-based) of the ascending nan_to_num(values): values become
+ *                   order-preserving u32 keys (sign bit set: all bits flipped, else the sign bit set; -0 sorts below +0),
+ *                   gsr_sort_pairs_u32 sorts them, one kernel picks the k keys and turns them back.  ONE read-back (the k
+ *                   floats, one stream synchronisation).  1 <= n <= 2^31 - 1.
+ *   FRAME_DEPTH     d = nan_to_num(depth) (NaN -> 0, +-inf -> +-FLT_MAX) is written as fp32 where `clean` is not NULL (the
+ *                   TIFF payload).  The video frame (where `frame` is not NULL; one of the two is required): t = ((double)logf(d) - min(lo, hi)) / |hi - lo| in fp64 (numpy 2 promotes
+ *                   the reference's normalisation to fp64 through its float64 limits), a NaN t (d < 0, or hi == lo with
+ *                   log d == lo) gives (0, 0, 0); otherwise t is clipped to [0, 1], the index is trunc(t * 256) with 256 ->
+ *                   255, and the pixel is that row of `table` (device u8 [256,3], staged once per workgroup).  d == 0 gives
+ *                   t = -inf, index 0; hi == lo gives +-inf, index 0 or 255: IEEE, as numpy.  depth f32 [B,1,H,W], frame u8
+ *                   [B,H,W,3].  Four pixels per thread with one 16-byte load, one 16-byte store and three dword stores where
+ *                   the pointers are 16-byte aligned; a scalar tail.
+ *   FRAME_SOBEL     gradient_map: per channel, with zero padding and a = row y - 1, m = row y, b = row y + 1 at columns
+ *                   x - 1, x, x + 1 (indices 0, 1, 2):
+ *                     gx = ((((-.25 a0 + .25 a2) + -.5 m0) + .5 m2) + -.25 b0) + .25 b2
+ *                     gy = ((((-.25 a0 + -.5 a1) + -.25 a2) + .25 b0) + .5 b1) + .25 b2
+ *                   (the non-zero weights of the 3x3 kernel / 4 in row-major order, added left to right; the weights are
+ *                   powers of two, so the products are exact and this order alone decides the bits), mag_c = sqrt(gx gx +
+ *                   gy gy), out = sqrt(sum_c mag_c mag_c) with c ascending from 0.  fp32, no fused multiply-add.  image f32
+ *                   [C,H,W] -> out f32 [1,H,W], one launch, C looped inside; four pixels of a row per thread.
+ *   FRAME_MINMAX    bounds device u32 [2]: the minimum and the maximum of x as order-preserving words (FRAME_STATS' key).
+ *                   The call resets them itself; 16-byte loads, wave reduction, one integer atomic per wave and bound, no
+ *                   read-back.  A NaN in x is skipped (fminf / fmaxf).
+ *   FRAME_COLORMAP  colormap: index = rint((x - min) / (max - min) * 255) in fp32, each operation rounded on its own, IEEE
+ *                   division, half to even (torch.round); out[c] = table[index][c] with table device f32 [256,3] staged once
+ *                   per workgroup; x f32 [H,W] -> out f32 [3,H,W].  DEVIATION: max == min gives index 0 everywhere (the
+ *                   reference converts NaN to an integer there).  A NaN in x: unspecified colour, never an access outside
+ *                   the table.
+ * Only gsr_frame_order_stats synchronises.  Empty inputs launch nothing (order_stats and minmax need n >= 1).  Bad sizes,
+ * null pointers, a workspace that is too small: GSR_E_INVALID / GSR_E_UNSUPPORTED before anything is launched.  All element
+ * offsets are 64-bit; no floating-point atomics. */
+int32_t gsr_frame_to_u8(const float* in, int32_t B, int32_t C, int32_t H, int32_t W, uint8_t* out, gsr_stream_t stream);
+size_t gsr_frame_order_stats_workspace_bytes(int64_t n);
+int32_t gsr_frame_order_stats(const float* values, int64_t n, const int64_t* ranks_host, int32_t k, float* out_host, void* ws,
+                              size_t ws_bytes, gsr_stream_t stream);
+int32_t gsr_frame_depth_vis(const float* depth, int32_t B, int32_t H, int32_t W, double lo, double hi, const uint8_t* table,
+                            float* clean, uint8_t* frame, gsr_stream_t stream);
+int32_t gsr_frame_sobel(const float* image, int32_t C, int32_t H, int32_t W, float* out, gsr_stream_t stream);
+int32_t gsr_frame_minmax(const float* x, int64_t n, uint32_t* bounds, gsr_stream_t stream);
+int32_t gsr_frame_colormap(const float* x, int32_t H, int32_t W, const uint32_t* bounds, const float* table, float* out,
+                           gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only
