@@ -16,8 +16,10 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSR_LIB_PATH: developer aid for same-box A/B runs of two builds of the library (scripts/ab_builds.sh)
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "lib", "libgsr_hip.so")
-ABI_VERSION = 16
+ABI_VERSION = 17
 GSR_LPIPS_ALEX, GSR_LPIPS_VGG = 0, 1
+GSR_DINO_EPI_BIAS, GSR_DINO_EPI_GELU, GSR_DINO_EPI_RESID = 0, 1, 2
+GSR_DINO_W_LAYER0, GSR_DINO_W_PER_LAYER = 4, 18      # include/gsr.h: the weight table of gsr_dino_forward
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_SCRATCH, GSR_BUF_SCRATCH2 = range(5)
 GSR_BUF_SYNC_SH = 100     # not a buffer: "the SH colour pass is about to be enqueued" (GSR_FLAG_DEFER_COLOR)
@@ -95,6 +97,13 @@ class GsrSegView(C.Structure):
     _fields_ = [("kind", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("n_masks", C.c_int32),
                 ("label_offset", C.c_int64), ("world_mat", C.c_double * 16), ("scale_mat", C.c_double * 16),
                 ("camera_mat", C.c_double * 9), ("cam_pos", C.c_double * 3), ("img_w", C.c_double), ("img_h", C.c_double)]
+
+
+class GsrDinoConfig(C.Structure):
+    """include/gsr.h: the run-time shape of the DINOv3 ViT encoder (gaussmart_amd/dino.py)."""
+    _fields_ = [("hidden", C.c_int32), ("heads", C.c_int32), ("layers", C.c_int32), ("intermediate", C.c_int32),
+                ("registers", C.c_int32), ("rope_theta", C.c_float), ("ln_eps", C.c_float),
+                ("image_mean", C.c_float * 3), ("image_std", C.c_float * 3)]
 
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t)
@@ -331,7 +340,18 @@ def lib():
                 ("gsr_frame_depth_vis", C.c_int32, [vp, C.c_int32, C.c_int32, C.c_int32, f64, f64, vp, vp, vp, vp]),
                 ("gsr_frame_sobel", C.c_int32, [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
                 ("gsr_frame_minmax", C.c_int32, [vp, i64, vp, vp]),
-                ("gsr_frame_colormap", C.c_int32, [vp, C.c_int32, C.c_int32, vp, vp, vp, vp])):
+                ("gsr_frame_colormap", C.c_int32, [vp, C.c_int32, C.c_int32, vp, vp, vp, vp]),
+                ("gsr_dino_embed_workspace_bytes", sz, [C.c_int32] * 3),
+                ("gsr_dino_embed", C.c_int32, [C.POINTER(GsrDinoConfig), vp, vp] + [C.c_int32] * 3 + [vp] * 5 + [sz, vp, vp]),
+                ("gsr_dino_norm", C.c_int32, [vp, i64, C.c_int32, i64, vp, vp, C.c_float, C.c_int32, vp, vp]),
+                ("gsr_dino_linear", C.c_int32, [vp, vp, vp, vp, i64, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
+                ("gsr_dino_rope", C.c_int32, [vp, vp] + [C.c_int32] * 5 + [C.c_float, vp]),
+                ("gsr_dino_attn", C.c_int32, [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
+                ("gsr_dino_workspace_bytes", sz, [C.POINTER(GsrDinoConfig)] + [C.c_int32] * 3),
+                ("gsr_dino_num_weights", C.c_int32, [C.c_int32]),
+                ("gsr_dino_forward", C.c_int32, [C.POINTER(GsrDinoConfig), C.POINTER(vp), C.c_int32, vp, vp] + [C.c_int32] * 3 +
+                 [vp, sz, vp, vp, vp]),
+                ("gsr_dino_cosine", C.c_int32, [vp, vp, C.c_int32, C.c_float, vp, vp])):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]

@@ -1,4 +1,5 @@
-"""HIP-backed stand-ins for the two functions train.py takes from the reference's utils/loss_utils.py:
+"""HIP-backed stand-ins for the functions train.py takes from the reference's utils/loss_utils.py (l1_loss, ssim, and
+dino_loss at the end of this file):
 
     from utils.loss_utils import l1_loss, ssim            # train.py:15
     Ll1 = l1_loss(image, gt_image)                         # train.py:113
@@ -50,3 +51,18 @@ def ssim(img1, img2, window_size=11, size_average=True):
                          "gaussmart_amd.losses.ssim is the general torch formulation")
     a, b = _check(img1, img2, "ssim")
     return 1.0 - photometric_loss(a, b, 1.0)[0]
+
+
+def dino_loss(rendered_image, gt_image, dino_encoder, lambda_dino):
+    """fp16(lambda_dino) * cos(emb(rendered), emb(gt)) as a 0-dim fp16 tensor without gradient (utils/loss_utils.py:77-97).
+    `dino_encoder`: anything with the reference's encode_tensor(image [3,H,W]) -> [hidden]; a gaussmart_amd.dino encoder takes
+    both images in one pass (encode_pair).  Unlike the reference nothing is rounded to fp16 midway: the cosine is computed in
+    fp32 (include/gsr.h, DN_COS) and the product is rounded to fp16 once."""
+    from .dino import scaled_cosine
+    with torch.no_grad():
+        if hasattr(dino_encoder, "encode_pair"):
+            emb = dino_encoder.encode_pair(rendered_image.detach(), gt_image.detach())
+            a, b = emb[0], emb[1]
+        else:
+            a, b = dino_encoder.encode_tensor(rendered_image.detach()), dino_encoder.encode_tensor(gt_image.detach())
+        return scaled_cosine(a, b, lambda_dino).to(torch.float16)

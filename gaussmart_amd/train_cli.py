@@ -1,9 +1,12 @@
 """Command-line training entry: the build's counterpart of the reference's train.py / render.py
-front ends for the hot path (scene in -> optimised surfels + PSNR out).  SAM / DINO preprocessing,
+front ends for the hot path (scene in -> optimised surfels + PSNR out).  SAM preprocessing,
 TensorBoard and the viewer socket of the reference are out of scope; SSIM, PSNR
 and LPIPS of the rendered test views come from gaussmart_amd.metrics_cli, not from this command.
+The reference's DINO feature term is behind --dino_dir (a LOCAL directory with the DINOv3 ViT weights; nothing
+is downloaded): it is logged to MODEL/dino_loss_log.csv and carries no gradient, as in the reference.
 
     python -m gaussmart_amd.train_cli -s <colmap-or-blender-scene> -m <output dir> [--iterations 30000] [--eval]
+        [--dino_dir DIR [--lambda_dino 0.05] [--dino_start_iter 3000] [--host]]
     torchrun --nproc-per-node 8 -m gaussmart_amd.train_cli -s ... -m ...        # view-parallel
 """
 import argparse
@@ -18,7 +21,7 @@ from .gaussian_renderer import render
 from .losses import psnr
 from .params import OptimizationParams, PipelineParams
 from .scene_io import Scene
-from .trainer import train, TrainState
+from .trainer import train, TrainState, DinoTerm
 from .view_parallel import ViewParallel
 
 
@@ -52,6 +55,13 @@ def main(argv=None):
                          "the initial cloud is augmented per segment")
     ap.add_argument("--uniform_upsampling", action="store_true",
                     help="without mask areas: augment the initial cloud as one segment")
+    ap.add_argument("--dino_dir", default=None,
+                    help="local directory with config.json, preprocessor_config.json and model.safetensors of a DINOv3 ViT: adds "
+                         "the reference's DINO feature term to the logged total loss (MODEL/dino_loss_log.csv); never a hub name")
+    ap.add_argument("--lambda_dino", type=float, default=0.05)
+    ap.add_argument("--dino_start_iter", type=int, default=3000)
+    ap.add_argument("--host", action="store_true",
+                    help="with --dino_dir: run the encoder through transformers' model (torch) instead of the HIP kernels")
     args = ap.parse_args(argv)
 
     import torch.distributed as dist
@@ -82,13 +92,18 @@ def main(argv=None):
     vp = ViewParallel(gaussians) if world > 1 else ViewParallel(gaussians, overlap_local=True)
 
     os.makedirs(args.model_path, exist_ok=True)
+    dino = None
+    if args.dino_dir and rank == 0:
+        from .dino import DINOImageEncoder, HostDINOImageEncoder
+        encoder = (HostDINOImageEncoder if args.host else DINOImageEncoder)(args.dino_dir)
+        dino = DinoTerm(encoder, args.lambda_dino, args.dino_start_iter, os.path.join(args.model_path, "dino_loss_log.csv"))
     t0 = time.time()
     done = first_iter
     state = TrainState(seed=0)      # one view sampler for the whole run: saving does not perturb the trajectory
     for stop in sorted(set([i for i in args.save_iterations if first_iter < i <= args.iterations] + [args.iterations])):
         train(gaussians, scene.getTrainCameras(), opt, pipe, background, cameras_extent=scene.cameras_extent,
               first_iter=done, iterations=stop, view_parallel=vp, white_background=args.white_background,
-              log_every=args.log_every if rank == 0 else 0, final_iteration=args.iterations, state=state)
+              log_every=args.log_every if rank == 0 else 0, final_iteration=args.iterations, state=state, dino=dino)
         done = stop
         if vp is not None:
             vp.finish()

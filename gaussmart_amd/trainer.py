@@ -2,12 +2,15 @@
 
 Counterpart of training() in the reference (train.py:45-243): random view, render, loss
 0.8*L1 + 0.2*(1-SSIM) + lambda_normal*normal + lambda_dist*dist, backward, densification
-bookkeeping, Adam step.  The reference's per-iteration `.item()` calls, CSV append, TensorBoard,
-DINO scalar (no gradient, needs a network fetch), the LPIPS of its test report and the viewer socket
-are left out of the loop: none of them reaches the rasterizer, and the host syncs they cause are a
-throughput hazard.  LPIPS itself is built (gaussmart_amd.lpips, from local weight files) and is
-reported by metrics_cli.
+bookkeeping, Adam step.  The reference's per-iteration `.item()` calls, per-iteration CSV append, TensorBoard,
+the LPIPS of its test report and the viewer socket are left out of the loop: none of them reaches the
+rasterizer, and the host syncs they cause are a throughput hazard.  LPIPS itself is built (gaussmart_amd.lpips,
+from local weight files) and is reported by metrics_cli.  The DINO feature term (train.py:119-127: no gradient,
+but part of total_loss and of dino_loss_log.csv) is DinoTerm below: the encoder of gaussmart_amd.dino from a
+local directory, on a side stream, logged into a device buffer and written out when train() returns.
 """
+import csv
+import os
 import random
 import time
 
@@ -159,6 +162,108 @@ def densification_step(gaussians, render_pkg, opt, iteration, cameras_extent, wh
             gaussians.reset_opacity()
 
 
+class DinoTerm:
+    """The reference's DINO scalar (train.py:116-129,143,174-186) without its host syncs.  After `start_iter` the detached
+    render is encoded on a side stream (the ground truth of a camera once: its embedding is cached), the cosine times
+    fp16(lambda) goes into a device log buffer beside the step's other loss parts, and flush() -- train() calls it when it
+    returns -- copies the buffer once and appends MODEL/dino_loss_log.csv with the reference's columns.  The term carries no
+    gradient (the reference computes it under inference_mode), so the trajectory of the parameters does not depend on it.
+    `encoder`: gaussmart_amd.dino.DINOImageEncoder (or anything with encode_tensor); `side_stream=False` keeps the encoder on
+    the training stream (scripts/dino_bench.py times both)."""
+    FIELDS = ("iteration", "dino_loss", "total_loss", "l1_loss", "dist_loss", "normal_loss")
+    IN_FLIGHT = 2       # encodes the training stream may run ahead of: bounds the renders kept alive for the side stream
+
+    def __init__(self, encoder, lambda_dino=0.05, start_iter=3000, csv_path=None, side_stream=True):
+        from .dino import scaled_cosine
+        self._cos = scaled_cosine
+        self.encoder, self.lambda_dino, self.start_iter = encoder, float(lambda_dino), int(start_iter)
+        self.csv_path, self.side_stream = csv_path, side_stream
+        self._gt = {}           # id(camera) -> its ground truth's embedding
+        self._iters, self._log = [], None       # rows of this train() call: (dino, total, l1, dist, normal, photometric)
+        self._side, self._events = None, []
+        self._wrote_header = False
+
+    def begin(self, n_rows, device):
+        self._iters = []
+        self._log = torch.zeros(max(1, n_rows), 6, dtype=torch.float32, device=device)
+
+    def _parts_row(self, parts, opt, iteration):
+        """(total without the term, l1, dist, normal, photometric) as a [5] tensor, from either shape of training_losses' parts."""
+        if "dist" in parts:     # the torch formulation: the terms themselves
+            vals = (parts["total"], parts["l1"], parts["dist"], parts["normal"], parts["loss"])
+        else:                   # the fused objective: the means and the two photometric parts
+            lambda_normal = opt.lambda_normal if iteration > 7000 else 0.0
+            lambda_dist = opt.lambda_dist if iteration > 3000 else 0.0
+            phot = (1.0 - opt.lambda_dssim) * parts["l1"] + opt.lambda_dssim * (1.0 - parts["ssim"])
+            vals = (parts["total"], parts["l1"], lambda_dist * parts["dist_mean"], lambda_normal * parts["normal_mean"], phot)
+        return torch.stack([v.detach().reshape(()).to(torch.float32) for v in vals])
+
+    def _embed_gt(self, cam, gt):
+        e = self._gt.get(id(cam))
+        if e is None:
+            e = self._gt[id(cam)] = self.encoder.encode_tensor(gt).detach()
+        return e
+
+    def _encode(self, row, cam, image, gt):
+        d = self._cos(self.encoder.encode_tensor(image), self._embed_gt(cam, gt), self.lambda_dino)
+        row[0] = d.to(torch.float16).to(torch.float32)      # the reference's term is an fp16 scalar
+        row[1] = row[1] + row[0]
+
+    def step(self, iteration, cam, image, gt, parts, opt):
+        """Called once per iteration after training_step.  Nothing here synchronises with the host."""
+        k = len(self._iters)
+        if self._log is None or k >= self._log.shape[0]:
+            raise RuntimeError("DinoTerm.step: begin(n_rows, device) was not called for this many iterations")
+        self._iters.append(iteration)
+        row = self._log[k]
+        row[1:] = self._parts_row(parts, opt, iteration)
+        if iteration <= self.start_iter:
+            return
+        image = image.detach()
+        if not (image.is_cuda and self.side_stream):
+            self._encode(row, cam, image, gt)
+            return
+        main = torch.cuda.current_stream(image.device)
+        if self._side is None:
+            self._side = torch.cuda.Stream(image.device)
+        if len(self._events) >= self.IN_FLIGHT:
+            main.wait_event(self._events.pop(0))
+        self._side.wait_stream(main)
+        with torch.cuda.stream(self._side):
+            self._encode(row, cam, image, gt)
+            done = torch.cuda.Event()
+            done.record(self._side)
+        # the render and the ground truth were allocated on the training stream: not to be reused before the side stream's read
+        image.record_stream(self._side)
+        gt.record_stream(self._side)
+        self._events.append(done)
+
+    def rows(self):
+        """[(iteration, dino, total, l1, dist, normal, photometric)] of this train() call: ONE copy, after the side stream."""
+        if self._log is None or not self._iters:
+            return []
+        if self._side is not None:
+            self._side.synchronize()
+        host = self._log[:len(self._iters)].cpu().tolist()
+        return [(it, *vals) for it, vals in zip(self._iters, host)]
+
+    def flush(self):
+        rows = self.rows()
+        self._events = []
+        if self.csv_path is None or not rows:
+            return rows
+        os.makedirs(os.path.dirname(os.path.abspath(self.csv_path)), exist_ok=True)
+        with open(self.csv_path, "a" if self._wrote_header else "w", newline="") as f:
+            w = csv.writer(f)
+            if not self._wrote_header:
+                w.writerow(self.FIELDS)
+                self._wrote_header = True
+            for r in rows:
+                w.writerow([r[0]] + [float(v) for v in r[1:6]])
+        self._iters = []
+        return rows
+
+
 class TrainState:
     """What a training run carries from one iteration to the next besides the model: the view sampler (RNG, the
     current epoch's stack of unvisited views, the epoch count).  Pass the same object to consecutive train() calls
@@ -180,7 +285,7 @@ class TrainState:
 
 def train(gaussians, cameras, opt, pipe, background, *, cameras_extent=1.0, first_iter=0, iterations=None,
           view_parallel: ViewParallel = None, white_background=False, seed=0, log_every=0, log_fn=print,
-          final_iteration=None, state: TrainState = None, on_iteration=None):
+          final_iteration=None, state: TrainState = None, on_iteration=None, dino: DinoTerm = None):
     """cameras: objects with .original_image [3,H,W].  Epochs are shuffled stacks popped at random,
     as train.py:99-102; under view parallelism each rank pops from its shard of the same shuffle.
 
@@ -188,7 +293,8 @@ def train(gaussians, cameras, opt, pipe, background, *, cameras_extent=1.0, firs
     only the LAST iteration of the whole schedule skips the optimiser step: `final_iteration` (default: opt.iterations
     when this call ends there, else none) names it, so a run split into several calls -- one per save point -- steps on
     every intermediate stop exactly like an uninterrupted one.  `state` keeps the view sampler across such calls;
-    `on_iteration(iteration)` is called after each iteration's optimiser step (saving / evaluation hooks)."""
+    `on_iteration(iteration)` is called after each iteration's optimiser step (saving / evaluation hooks).
+    `dino`: a DinoTerm; None (the default) changes nothing."""
     iterations = opt.iterations if iterations is None else iterations
     if final_iteration is None:
         final_iteration = opt.iterations
@@ -196,6 +302,8 @@ def train(gaussians, cameras, opt, pipe, background, *, cameras_extent=1.0, firs
     device = gaussians.get_xyz.device
     t0 = time.time()
     last = None
+    if dino is not None:
+        dino.begin(iterations - first_iter, device)
     for iteration in range(first_iter + 1, iterations + 1):
         if iteration % 1000 == 0:
             gaussians.oneupSHdegree()
@@ -221,6 +329,8 @@ def train(gaussians, cameras, opt, pipe, background, *, cameras_extent=1.0, firs
                 optimizer_step(gaussians)      # the exchange of a view-parallel run already happened in training_step
             else:
                 gaussians.optimizer.zero_grad(set_to_none=True)   # the schedule's last iteration: no step (train.py:214)
+        if dino is not None:
+            dino.step(iteration, cam, render_pkg["render"], gt, last, opt)
         if on_iteration is not None:
             on_iteration(iteration)
         if log_every and iteration % log_every == 0:
@@ -230,4 +340,6 @@ def train(gaussians, cameras, opt, pipe, background, *, cameras_extent=1.0, firs
                    f"{(iteration - first_iter) / (time.time() - t0):.2f} it/s")
     if view_parallel is not None:
         view_parallel.finish()       # a pipelined last step may still be updating the SH tensors on its side stream
+    if dino is not None:
+        dino.flush()
     return last

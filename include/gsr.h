@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 16  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
+#define GSR_ABI_VERSION 17  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
                                 6: gsr_surface_maps_forward / _backward;
                                 7: TSDF fusion and marching cubes (GsrTsdfVolume, gsr_tsdf_*, gsr_mcubes_*);
                                 8: mesh post-processing (gsr_mesh_*) and gsr_depth_aabb;
@@ -46,7 +46,8 @@ extern "C" {
                                 13: segment-aware initialisation of the point cloud (GsrSegView, gsr_seg_*);
                                 14: unbounded mesh export (GsrUnbView, gsr_unb_*);
                                 15: LPIPS (gsr_lpips_*);
-                                16: frame kernels of the trajectory and viewer pictures (gsr_frame_*) */
+                                16: frame kernels of the trajectory and viewer pictures (gsr_frame_*);
+                                17: DINOv3 ViT encoder and its cosine term (GsrDinoConfig, gsr_dino_*) */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -1098,6 +1099,95 @@ int32_t gsr_frame_sobel(const float* image, int32_t C, int32_t H, int32_t W, flo
 int32_t gsr_frame_minmax(const float* x, int64_t n, uint32_t* bounds, gsr_stream_t stream);
 int32_t gsr_frame_colormap(const float* x, int32_t H, int32_t W, const uint32_t* bounds, const float* table, float* out,
                            gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- DINOv3 ViT encoder
+ * transformers' DINOv3ViTModel (models/dinov3_vit/modeling_dinov3_vit.py), which the reference's DINOImageEncoder runs in fp16
+ * (identification/feature_extraction.py:18-43) for the cosine term of utils/loss_utils.py:77-97, as inference kernels (dino.hip;
+ * Python: gaussmart_amd/dino.py).  head_dim is 64 and the patch 16 x 16; hidden = 64 heads, layers >= 1, intermediate a multiple
+ * of 64, registers >= 0, B in 1..8, H, W >= 16 are run-time parameters.  EVERY weight is stored in fp16 (the reference's
+ * .half()) and widened exactly where it is used in fp32.  Matrix products take fp16 operands on v_mfma_f32_32x32x16_f16 and
+ * accumulate in fp32: one k-ascending chain per output element, no split-K, no atomics, so the bits are the same on every run
+ * and for an image alone or inside a batch.  DEVIATION, on purpose: the reference keeps the residual stream in fp16; here it is
+ * fp32, as are the LayerNorm statistics, the softmax and the input normalisation.  Rules, with every rounding they perform:
+ *   DN_EMBED   x f32 [B,3,H,W] in the caller's range; xn = (x - mean[c]) / std[c] in fp32 (subtraction, true division), ROUNDED
+ *              TO fp16; the 16x16 stride-16 convolution is a product over K = 768 (k = c 256 + ky 16 + kx) with the fp16 weight
+ *              [hidden,768], fp32 accumulation, + fp32(bias) in fp32, stored as fp32 (no output rounding).  Hp = H / 16,
+ *              Wp = W / 16 in integer division: trailing rows and columns are not read, as Conv2d does.  Token order: CLS,
+ *              registers, patches row-major; CLS and register rows are the fp16 weights widened.  Output: the fp32 residual
+ *              stream [B,T,hidden], T = 1 + registers + Hp Wp.
+ *   DN_NORM    per row, fp32: mean = sum / n; var = sum (x - mean)^2 / n (biased); y = (x - mean) * (1 / sqrt(var + eps)) * g
+ *              + b with g, b the fp16 weights widened; ROUNDED TO fp16 (the next product's operand), or stored as fp32 with
+ *              out_f32 (the final norm).  Sums: a lane adds elements lane, lane + 64, ... in order, the 64 lanes by a xor
+ *              butterfly.  x rows are in_stride elements apart (the pooled rows are T hidden apart).
+ *   DN_LINEAR  acc[m][n] = sum_k x[m][k] w[n][k], x fp16 [M,K], w fp16 [N,K] row-major (torch's Linear), fp32 accumulation,
+ *              K a multiple of 64, any M and N (tails are masked, nothing is padded by the caller).  Epilogues:
+ *                GSR_DINO_EPI_BIAS   y = acc + fp32(bias[n]) (bias NULL: + 0), ROUNDED TO fp16.
+ *                GSR_DINO_EPI_GELU   u = acc + fp32(bias[n]); y = 0.5 u (1 + erf(u / sqrt 2)) in fp32 (erff), ROUNDED TO fp16.
+ *                GSR_DINO_EPI_RESID  resid[m][n] = fma(fp32(lambda[n]), acc + fp32(bias[n]), resid[m][n]) in fp32: LayerScale
+ *                                    and the residual addition, ONE fp32 rounding after the bias addition's.
+ *   DN_ROPE    in place on q and k (fp16 [B,T,hidden]) of the Hp Wp patch tokens (the last ones of each image) only.  fp32:
+ *              coord = 2 ((i + 0.5) / Hp) - 1 for patch row i, likewise over Wp; inv_freq_j = 1 / theta^(j / 16), j < 16;
+ *              angle = 2 pi coord inv_freq, laid out as [y: 16, x: 16] and tiled twice to 64; q' = q cos + rotate_half(q) sin
+ *              with rotate_half(q) = cat(-q[32:], q[:32]): two fp32 products and one fp32 addition per element, ROUNDED TO
+ *              fp16.  (modeling_dinov3_vit.py: get_patches_center_coordinates, DINOv3ViTRopePositionEmbedding,
+ *              apply_rotary_pos_emb.)
+ *   DN_ATTN    per image and head, non-causal, scale 1/8, in base 2: t_j = (sum_d q_d k_jd) * fp32(log2(e) / 8) (fp16 operands, fp32
+ *              accumulation, ONE fp32 rounding for the product), one pass over KV tiles of 64 with a running maximum m and sum
+ *              l in fp32: p_j = 2^(t_j - m) (fp32 subtraction, v_exp_f32: 1 ulp); l adds the UNROUNDED p_j; p_j is ROUNDED TO
+ *              fp16 for the P V product (fp16 v, fp32 accumulation, rescaled by 2^(m_old - m_new) in fp32 when the maximum
+ *              moves); out = acc / l in fp32, ROUNDED TO fp16.  No T x T matrix
+ *              exists in memory.  kv rows past T are never read and their scores are -inf before the maximum; query rows past
+ *              T are not written.  q, k, v, out: fp16 [B,T,hidden], head h in columns 64 h .. 64 h + 63.
+ *   DN_POOL    the final LayerNorm (DN_NORM, fp32 out); pooled[b] is row 0 (CLS) of image b, last_hidden every row.
+ *   DN_COS     out = lambda16 * (dot / (max(sqrt(aa), 1e-8) * max(sqrt(bb), 1e-8))), dot = sum a_i b_i, aa = sum a_i^2,
+ *              bb = sum b_i^2 in fp32: thread t of 256 adds elements t, t + 256, ... in order, then a fixed tree over the
+ *              threads.  lambda16 is the fp16-rounded lambda passed as a float (F.cosine_similarity's definition, times the
+ *              reference's fp16 lambda).
+ * Weight table of gsr_dino_forward: a HOST array of gsr_dino_num_weights(layers) DEVICE pointers to fp16 arrays, in this order
+ * (names: DINOv3ViTModel.state_dict()):
+ *   GSR_DINO_W_CLS embeddings.cls_token [hidden]; _REG embeddings.register_tokens [registers,hidden] (NULL with 0 registers);
+ *   _PATCH_W embeddings.patch_embeddings.weight [hidden,768]; _PATCH_B its bias [hidden];
+ *   then per layer l at GSR_DINO_W_LAYER0 + GSR_DINO_W_PER_LAYER l + GSR_DINO_L_*: norm1.weight, norm1.bias, attention.q_proj
+ *   weight, bias, k_proj weight, bias, v_proj weight, bias, o_proj weight, bias, layer_scale1.lambda1, norm2.weight, norm2.bias,
+ *   mlp.up_proj weight, bias, mlp.down_proj weight, bias, layer_scale2.lambda1; a projection's bias may be NULL (k_proj of ViT-B);
+ *   last: norm.weight, norm.bias.
+ * Entry points (all work on the caller's stream, the caller owns every buffer, nothing synchronises):
+ *   gsr_dino_embed   : DN_EMBED; x1: image 1 where it does not follow image 0 in memory (else NULL; images 2.. follow x1);
+ *                      ws: gsr_dino_embed_workspace_bytes (the fp16 patch rows).
+ *   gsr_dino_norm / _linear / _rope / _attn : one rule each, for the tests.  _rope: q or k may be NULL.
+ *   gsr_dino_forward : the encoder on B images; pooled f32 [B,hidden]; last_hidden f32 [B,T,hidden] or NULL; ws:
+ *                      gsr_dino_workspace_bytes(cfg, B, H, W) (0 for a refused configuration).
+ *   gsr_dino_cosine  : DN_COS; a, b device f32 [n]; out device f32 [1].
+ * hidden != 64 heads, intermediate % 64 != 0, H or W < 16, B outside 1..8, a workspace that is too small, a null required
+ * pointer, a weight table of the wrong length: GSR_E_INVALID before anything is launched, with a message. */
+typedef struct GsrDinoConfig {
+    int32_t hidden, heads, layers, intermediate, registers;
+    float rope_theta, ln_eps;
+    float image_mean[3], image_std[3];
+} GsrDinoConfig;
+enum { GSR_DINO_EPI_BIAS = 0, GSR_DINO_EPI_GELU = 1, GSR_DINO_EPI_RESID = 2 };
+enum { GSR_DINO_W_CLS = 0, GSR_DINO_W_REG, GSR_DINO_W_PATCH_W, GSR_DINO_W_PATCH_B, GSR_DINO_W_LAYER0 };
+enum { GSR_DINO_L_NORM1_W = 0, GSR_DINO_L_NORM1_B, GSR_DINO_L_Q_W, GSR_DINO_L_Q_B, GSR_DINO_L_K_W, GSR_DINO_L_K_B, GSR_DINO_L_V_W,
+       GSR_DINO_L_V_B, GSR_DINO_L_O_W, GSR_DINO_L_O_B, GSR_DINO_L_LS1, GSR_DINO_L_NORM2_W, GSR_DINO_L_NORM2_B, GSR_DINO_L_UP_W,
+       GSR_DINO_L_UP_B, GSR_DINO_L_DOWN_W, GSR_DINO_L_DOWN_B, GSR_DINO_L_LS2, GSR_DINO_W_PER_LAYER };
+size_t gsr_dino_embed_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int32_t gsr_dino_embed(const GsrDinoConfig* cfg, const float* x0, const float* x1, int32_t B, int32_t H, int32_t W, const void* cls,
+                       const void* reg, const void* patch_w, const void* patch_b, void* ws, size_t ws_bytes, float* out,
+                       gsr_stream_t stream);
+int32_t gsr_dino_norm(const float* x, int64_t rows, int32_t hidden, int64_t in_stride, const void* weight, const void* bias,
+                      float eps, int32_t out_f32, void* y, gsr_stream_t stream);
+int32_t gsr_dino_linear(const void* x, const void* w, const void* bias, const void* lambda, int64_t M, int32_t K, int32_t N,
+                        int32_t epilogue, void* out, gsr_stream_t stream);
+int32_t gsr_dino_rope(void* q, void* k, int32_t B, int32_t T, int32_t heads, int32_t Hp, int32_t Wp, float theta,
+                      gsr_stream_t stream);
+int32_t gsr_dino_attn(const void* q, const void* k, const void* v, int32_t B, int32_t T, int32_t heads, void* out,
+                      gsr_stream_t stream);
+size_t gsr_dino_workspace_bytes(const GsrDinoConfig* cfg, int32_t B, int32_t H, int32_t W);
+int32_t gsr_dino_num_weights(int32_t layers);
+int32_t gsr_dino_forward(const GsrDinoConfig* cfg, const void* const* weights_host, int32_t n_weights, const float* x0,
+                         const float* x1, int32_t B, int32_t H, int32_t W, void* ws, size_t ws_bytes, float* pooled,
+                         float* last_hidden, gsr_stream_t stream);
+int32_t gsr_dino_cosine(const float* a, const float* b, int32_t n, float lambda16, float* out, gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only
