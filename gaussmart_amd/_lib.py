@@ -16,10 +16,11 @@ import torch  # noqa: F401  (import order matters)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSR_LIB_PATH: developer aid for same-box A/B runs of two builds of the library (scripts/ab_builds.sh)
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "lib", "libgsr_hip.so")
-ABI_VERSION = 17
+ABI_VERSION = 18
 GSR_LPIPS_ALEX, GSR_LPIPS_VGG = 0, 1
 GSR_DINO_EPI_BIAS, GSR_DINO_EPI_GELU, GSR_DINO_EPI_RESID = 0, 1, 2
 GSR_DINO_W_LAYER0, GSR_DINO_W_PER_LAYER = 4, 18      # include/gsr.h: the weight table of gsr_dino_forward
+GSR_SAM_W_LAYER0, GSR_SAM_W_PER_LAYER, GSR_SAM_W_NECK = 3, 14, 6     # include/gsr.h: the weight table of gsr_sam_encode
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_SCRATCH, GSR_BUF_SCRATCH2 = range(5)
 GSR_BUF_SYNC_SH = 100     # not a buffer: "the SH colour pass is about to be enqueued" (GSR_FLAG_DEFER_COLOR)
@@ -97,6 +98,13 @@ class GsrSegView(C.Structure):
     _fields_ = [("kind", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("n_masks", C.c_int32),
                 ("label_offset", C.c_int64), ("world_mat", C.c_double * 16), ("scale_mat", C.c_double * 16),
                 ("camera_mat", C.c_double * 9), ("cam_pos", C.c_double * 3), ("img_w", C.c_double), ("img_h", C.c_double)]
+
+
+class GsrSamConfig(C.Structure):
+    """include/gsr.h: the run-time shape of SAM's image encoder (gaussmart_amd/sam.py); the two pointers are host arrays."""
+    _fields_ = [("hidden", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32), ("layers", C.c_int32),
+                ("mlp_dim", C.c_int32), ("output_channels", C.c_int32), ("image_size", C.c_int32), ("ln_eps", C.c_float),
+                ("window_host", C.POINTER(C.c_int32)), ("rel_rows_host", C.POINTER(C.c_int32))]
 
 
 class GsrDinoConfig(C.Structure):
@@ -351,7 +359,20 @@ def lib():
                 ("gsr_dino_num_weights", C.c_int32, [C.c_int32]),
                 ("gsr_dino_forward", C.c_int32, [C.POINTER(GsrDinoConfig), C.POINTER(vp), C.c_int32, vp, vp] + [C.c_int32] * 3 +
                  [vp, sz, vp, vp, vp]),
-                ("gsr_dino_cosine", C.c_int32, [vp, vp, C.c_int32, C.c_float, vp, vp])):
+                ("gsr_dino_cosine", C.c_int32, [vp, vp, C.c_int32, C.c_float, vp, vp]),
+                ("gsr_sam_embed_workspace_bytes", sz, [C.c_int32]),
+                ("gsr_sam_embed", C.c_int32, [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, sz, vp, vp]),
+                ("gsr_sam_attn_workspace_bytes", sz, [C.c_int32] * 3),
+                ("gsr_sam_attn", C.c_int32, [vp] * 4 + [C.c_int32] * 5 + [vp, sz, vp, vp]),
+                ("gsr_sam_neck_workspace_bytes", sz, [C.c_int32] * 3),
+                ("gsr_sam_neck", C.c_int32, [vp] + [C.c_int32] * 3 + [vp] * 7 + [sz, vp, vp]),
+                ("gsr_sam_workspace_bytes", sz, [C.POINTER(GsrSamConfig)]),
+                ("gsr_sam_num_weights", C.c_int32, [C.c_int32]),
+                ("gsr_sam_encode", C.c_int32, [C.POINTER(GsrSamConfig), C.POINTER(vp), C.c_int32, vp, vp, sz, vp, vp]),
+                ("gsr_sam_mask_score", C.c_int32, [vp] + [C.c_int32] * 6 + [C.c_float, C.c_float, vp, vp, vp, vp]),
+                ("gsr_sam_mask_emit", C.c_int32, [vp] + [C.c_int32] * 6 + [C.c_float, vp, C.c_int32, vp, vp]),
+                ("gsr_sam_nms_workspace_bytes", sz, [C.c_int32]),
+                ("gsr_sam_nms", C.c_int32, [vp, vp, vp, C.c_int32, C.c_float, vp, sz, vp, vp, vp])):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]

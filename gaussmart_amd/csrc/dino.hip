@@ -5,8 +5,8 @@
 // No split-K and no atomics: every output element is one k-ordered chain, so the bits are the same on every run and for an
 // image alone or inside a batch.
 #include "cloud_common.h"
+#include "dino_internal.h"
 
-typedef _Float16 dn_half;
 typedef _Float16 dn_h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 dn_h4 __attribute__((ext_vector_type(4)));
 typedef float dn_f32x16 __attribute__((ext_vector_type(16)));
@@ -94,8 +94,7 @@ __global__ void __launch_bounds__(256) dn_norm_kernel(const float* __restrict__ 
 #define DN_BM 128
 #define DN_KC 64
 #define DN_LD 72        // halves per LDS row: 144 bytes, 16-byte aligned, consecutive rows 4 banks apart
-
-enum { DN_EPI_BIAS = 0, DN_EPI_GELU = 1, DN_EPI_RESID = 2, DN_EPI_EMBED = 3 };
+// the epilogue values DN_EPI_* are in dino_internal.h (sam.hip launches this kernel too)
 
 template <int EPI>
 __global__ void __launch_bounds__(256) dn_linear_kernel(const dn_half* __restrict__ x, const dn_half* __restrict__ w,
@@ -175,6 +174,13 @@ __global__ void __launch_bounds__(256) dn_linear_kernel(const dn_half* __restric
                 } else if (EPI == DN_EPI_RESID) {
                     float* o = static_cast<float*>(out_) + m * N + n;
                     *o = fmaf(ln, v, *o);
+                } else if (EPI == DN_EPI_RESID1) {      // SAM: no LayerScale, resid += acc + bias (one fp32 addition after the bias's)
+                    float* o = static_cast<float*>(out_) + m * N + n;
+                    *o = *o + v;
+                } else if (EPI == DN_EPI_F32) {         // SAM's neck: acc + bias stored as fp32
+                    static_cast<float*>(out_)[m * N + n] = v;
+                } else if (EPI == DN_EPI_POS) {         // SAM's embedding: (acc + bias) + fp32(pos[m][n]), stored as fp32
+                    static_cast<float*>(out_)[m * N + n] = v + (float)lam[m * N + n];
                 } else {
                     const int64_t b = m / Np, p = m - b * Np;
                     static_cast<float*>(out_)[(b * T + prefix + p) * N + n] = v;
@@ -184,14 +190,14 @@ __global__ void __launch_bounds__(256) dn_linear_kernel(const dn_half* __restric
     }
 }
 
-static int dn_linear(const dn_half* x, const dn_half* w, const dn_half* bias, const dn_half* lam, void* out, int64_t M, int K, int N,
-                     int epi, int64_t Np, int T, int prefix, hipStream_t s) {
+int dn_linear(const dn_half* x, const dn_half* w, const dn_half* bias, const dn_half* lam, void* out, int64_t M, int K, int N,
+              int epi, int64_t Np, int T, int prefix, hipStream_t s) {
     if (M < 1 || K < 64 || N < 1 || K % 64 != 0) {
         gsr_set_error("dino linear: M %lld and N %d must be >= 1 and K %d a positive multiple of 64", (long long)M, N, K);
         return GSR_E_INVALID;
     }
     if (!x || !w || !out) { gsr_set_error("dino linear: x / w / out is null"); return GSR_E_INVALID; }
-    if (epi == DN_EPI_RESID && !lam) { gsr_set_error("dino linear: the residual epilogue needs lambda"); return GSR_E_INVALID; }
+    if ((epi == DN_EPI_RESID || epi == DN_EPI_POS) && !lam) { gsr_set_error("dino linear: the residual epilogue needs lambda"); return GSR_E_INVALID; }
     if ((M + DN_BM - 1) / DN_BM > 0x7fffffffLL || (N + DN_BM - 1) / DN_BM > 65535) {
         gsr_set_error("dino linear: M %lld or N %d exceeds the launch grid", (long long)M, N);
         return GSR_E_UNSUPPORTED;
@@ -203,6 +209,9 @@ static int dn_linear(const dn_half* x, const dn_half* w, const dn_half* bias, co
     case DN_EPI_GELU: DN_LINEAR_LAUNCH(DN_EPI_GELU); break;
     case DN_EPI_RESID: DN_LINEAR_LAUNCH(DN_EPI_RESID); break;
     case DN_EPI_EMBED: DN_LINEAR_LAUNCH(DN_EPI_EMBED); break;
+    case DN_EPI_RESID1: DN_LINEAR_LAUNCH(DN_EPI_RESID1); break;
+    case DN_EPI_F32: DN_LINEAR_LAUNCH(DN_EPI_F32); break;
+    case DN_EPI_POS: DN_LINEAR_LAUNCH(DN_EPI_POS); break;
     default: gsr_set_error("dino linear: epilogue %d is not one of GSR_DINO_EPI_*", epi); return GSR_E_INVALID;
     }
 #undef DN_LINEAR_LAUNCH
@@ -286,8 +295,8 @@ extern "C" int32_t gsr_dino_embed(const GsrDinoConfig* cfg, const float* x0, con
                     static_cast<hipStream_t>(stream_));
 }
 
-static int dn_norm(const float* x, int64_t rows, int hidden, int64_t in_stride, const dn_half* g, const dn_half* b, float eps,
-                   void* y, int out_f32, hipStream_t s) {
+int dn_norm(const float* x, int64_t rows, int hidden, int64_t in_stride, const dn_half* g, const dn_half* b, float eps, void* y,
+            int out_f32, hipStream_t s) {
     if (rows < 1 || hidden < 1 || in_stride < hidden) {
         gsr_set_error("dino norm: rows %lld and hidden %d must be >= 1 and the row stride %lld at least hidden", (long long)rows, hidden,
                       (long long)in_stride);

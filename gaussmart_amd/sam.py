@@ -1,0 +1,643 @@
+"""SAM automatic mask generation on the device: the reference's SAMSegmentation.process_image (identification/sam.py:41-46,
+65-92: SamAutomaticMaskGenerator(vit_h, points_per_side=32, pred_iou_thresh=0.86, stability_score_thresh=0.92)) with the
+image encoder and the mask selection computed by the kernels of csrc/sam.hip (include/gsr.h: SV_EMBED, SV_ATTN, SV_NECK,
+SM_SCORE, SM_NMS, SM_EMIT).  The prompt encoder and the mask decoder are transformers' own torch modules, run on the device
+in fp32 as they are.
+
+    from gaussmart_amd.sam import SamMaskGenerator, load_sam_weights, save_segments_boxes
+    gen = SamMaskGenerator(load_sam_weights("/models/sam_vit_h_4b8939.pth"))     # or a directory, see load_sam_weights
+    masks = gen.generate(image_u8)                    # the reference's list of dicts, in NMS order
+    save_segments_boxes(masks, "out/segments/masks/segments_000.npz")
+    dev = gen.generate_device(image_u8)               # uint8 [m,h,w] on the device, what segment_init.label_points takes
+
+What differs from the reference, on purpose:
+  * nothing is fetched: `load_sam_weights` takes a LOCAL .pth (segment_anything's names) or a LOCAL directory (SamModel's).
+  * the encoder's weights are fp16 and its matrix products take fp16 operands with fp32 accumulation; the residual stream,
+    the LayerNorm statistics and the softmax are fp32.  The reference runs the encoder in fp32.
+  * DEVIATION: the first resize (long side <= 1024) is cv2.INTER_LINEAR in the reference and PIL's bilinear here.
+  * one full-image crop only: no crop layers, no min_mask_region_area, no SAM2.  The crop-edge filter of the reference never
+    fires for the single full-image crop and is left out.
+`sam_host`, `select_host` and `nms_host` are the torch twins (any device): they back `host=True` and the tests.
+"""
+import ctypes as C
+import json
+import math
+import os
+import re
+import time
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+from ._dev import ptr, stream, workspace
+
+PATCH = 16
+MASK_THRESHOLD = 0.0            # segment_anything's Sam.mask_threshold
+IMAGE_MEAN = (123.675, 116.28, 103.53)
+IMAGE_STD = (58.395, 57.12, 57.375)
+MAX_SIDE = 1024                 # identification/sam.py:72
+DECODER_CHANNELS = 256          # the stock prompt encoder and mask decoder
+
+# the weight table of gsr_sam_encode, in the order of include/gsr.h (names under "vision_encoder.")
+ENC_HEAD = ("patch_embed.projection.weight", "patch_embed.projection.bias", "pos_embed")
+ENC_LAYER = ("layer_norm1.weight", "layer_norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.rel_pos_h", "attn.rel_pos_w",
+             "attn.proj.weight", "attn.proj.bias", "layer_norm2.weight", "layer_norm2.bias", "mlp.lin1.weight", "mlp.lin1.bias",
+             "mlp.lin2.weight", "mlp.lin2.bias")
+ENC_NECK = ("neck.conv1.weight", "neck.layer_norm1.weight", "neck.layer_norm1.bias", "neck.conv2.weight",
+            "neck.layer_norm2.weight", "neck.layer_norm2.bias")
+assert (len(ENC_HEAD), len(ENC_LAYER), len(ENC_NECK)) == (_lib.GSR_SAM_W_LAYER0, _lib.GSR_SAM_W_PER_LAYER, _lib.GSR_SAM_W_NECK)
+VISION = "vision_encoder."
+TIED = ("prompt_encoder.shared_embedding.positional_embedding", "shared_image_embedding.positional_embedding")
+
+
+@dataclass
+class SamConfig:
+    """Defaults: ViT-H (sam_vit_h_4b8939), what the reference loads."""
+    hidden_size: int = 1280
+    num_hidden_layers: int = 32
+    num_attention_heads: int = 16
+    mlp_dim: int = 5120
+    window_size: int = 14
+    global_attn_indexes: tuple = (7, 15, 23, 31)
+    output_channels: int = 256
+    image_size: int = 1024
+    layer_norm_eps: float = 1e-6
+
+    @classmethod
+    def preset(cls, model_type):
+        if model_type == "vit_h":
+            return cls()
+        if model_type == "vit_l":
+            return cls(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, mlp_dim=4096, global_attn_indexes=(5, 11, 17, 23))
+        if model_type == "vit_b":
+            return cls(hidden_size=768, num_hidden_layers=12, num_attention_heads=12, mlp_dim=3072, global_attn_indexes=(2, 5, 8, 11))
+        raise ValueError(f"sam: model_type {model_type!r} is not vit_h, vit_l or vit_b")
+
+    @property
+    def grid(self):
+        return self.image_size // PATCH
+
+    @property
+    def head_dim(self):
+        return self.hidden_size // max(1, self.num_attention_heads)
+
+    def windows(self):
+        """Per layer: 0 for a global layer, else the window size."""
+        return [0 if l in tuple(self.global_attn_indexes) else int(self.window_size) for l in range(self.num_hidden_layers)]
+
+    def to_hf(self):
+        from transformers import SamConfig as HfSam, SamVisionConfig, SamPromptEncoderConfig, SamMaskDecoderConfig
+        vision = SamVisionConfig(hidden_size=self.hidden_size, output_channels=self.output_channels,
+                                 num_hidden_layers=self.num_hidden_layers, num_attention_heads=self.num_attention_heads,
+                                 image_size=self.image_size, patch_size=PATCH, layer_norm_eps=self.layer_norm_eps,
+                                 window_size=self.window_size, global_attn_indexes=list(self.global_attn_indexes), mlp_dim=self.mlp_dim)
+        hf = HfSam(vision_config=vision, prompt_encoder_config=SamPromptEncoderConfig(image_size=self.image_size),
+                   mask_decoder_config=SamMaskDecoderConfig())
+        hf.vision_config._attn_implementation = "eager"
+        hf.mask_decoder_config._attn_implementation = "eager"
+        return hf
+
+    def to_json(self):
+        return {"model_type": "sam", "vision_config": {
+            "hidden_size": self.hidden_size, "num_hidden_layers": self.num_hidden_layers, "num_attention_heads": self.num_attention_heads,
+            "mlp_dim": self.mlp_dim, "window_size": self.window_size, "global_attn_indexes": list(self.global_attn_indexes),
+            "output_channels": self.output_channels, "image_size": self.image_size, "layer_norm_eps": self.layer_norm_eps,
+            "patch_size": PATCH}}
+
+    @classmethod
+    def from_json(cls, d):
+        v = d.get("vision_config", d)
+        if v.get("patch_size", PATCH) != PATCH:
+            raise NotImplementedError(f"sam: patch size {v['patch_size']} is not built (16 only)")
+        hidden = int(v.get("hidden_size", 768))
+        mlp = v.get("mlp_dim") or int(hidden * v.get("mlp_ratio", 4.0))
+        return cls(hidden_size=hidden, num_hidden_layers=int(v.get("num_hidden_layers", 12)),
+                   num_attention_heads=int(v.get("num_attention_heads", 12)), mlp_dim=int(mlp), window_size=int(v.get("window_size", 14)),
+                   global_attn_indexes=tuple(v.get("global_attn_indexes", (2, 5, 8, 11))), output_channels=int(v.get("output_channels", 256)),
+                   image_size=int(v.get("image_size", 1024)), layer_norm_eps=float(v.get("layer_norm_eps", 1e-6)))
+
+
+def _shapes(config):
+    """name -> shape of transformers' SamModel.state_dict() for this configuration (built on the meta device)."""
+    from transformers import SamModel
+    with torch.device("meta"):
+        sd = SamModel(config.to_hf()).state_dict()
+    return {k: tuple(v.shape) for k, v in sd.items()}
+
+
+class SamWeights:
+    """config + the tensors under SamModel.state_dict()'s names: the vision encoder in fp16 (what the kernels take), the
+    prompt encoder, the mask decoder and the shared positional embedding in fp32.  decoder=False: the vision encoder alone
+    (any output_channels; the stock decoder needs 256)."""
+
+    def __init__(self, config, tensors, decoder=True):
+        self.config, self.decoder, self.tensors = config, bool(decoder), {}
+        tensors = dict(tensors)
+        for a, b in (TIED, TIED[::-1]):
+            if decoder and a not in tensors and b in tensors:
+                tensors[a] = tensors[b]
+        want = {k: s for k, s in _shapes(config).items() if decoder or k.startswith(VISION)}
+        if decoder and config.output_channels != DECODER_CHANNELS:
+            raise ValueError(f"sam weights: the decoder needs {DECODER_CHANNELS} output channels, the encoder has {config.output_channels}")
+        unknown = sorted(set(tensors) - set(want))
+        if unknown:
+            raise KeyError(f"sam weights: {len(unknown)} tensors have no place, e.g. {unknown[:3]}")
+        missing = sorted(set(want) - set(tensors))
+        if missing:
+            raise KeyError(f"sam weights: {len(missing)} tensors are not filled, e.g. {missing[:3]}")
+        for k, shape in want.items():
+            t = tensors[k].detach()
+            if tuple(t.shape) != shape:
+                raise ValueError(f"sam weights: {k} must be {list(shape)}, got {list(t.shape)}")
+            self.tensors[k] = t.to(torch.float16 if k.startswith(VISION) else torch.float32).contiguous()
+
+    def to(self, device):
+        w = SamWeights.__new__(SamWeights)
+        w.config, w.decoder = self.config, self.decoder
+        w.tensors = {k: t.to(device) for k, t in self.tensors.items()}
+        return w
+
+    def table(self):
+        """The vision encoder's tensors in the order of gsr_sam_encode's weight table."""
+        names = [VISION + k for k in ENC_HEAD]
+        for l in range(self.config.num_hidden_layers):
+            names += [f"{VISION}layers.{l}.{k}" for k in ENC_LAYER]
+        return [self.tensors[k] for k in names + [VISION + k for k in ENC_NECK]]
+
+    def sub(self, prefix):
+        """The tensors under `prefix`, with it removed (a sub-module's state dict), in fp32."""
+        return {k[len(prefix):]: t.to(torch.float32) for k, t in self.tensors.items() if k.startswith(prefix)}
+
+
+# ---------------------------------------------------------------- segment_anything's names <-> SamModel's
+_NECK = {"0": "conv1", "1": "layer_norm1", "2": "conv2", "3": "layer_norm2"}
+_DOWN = {"0": "conv1", "1": "layer_norm1", "3": "conv2", "4": "layer_norm2", "6": "conv3"}
+_UP = {"0": "upscale_conv1", "1": "upscale_layer_norm", "3": "upscale_conv2"}
+_MLP = {"0": "proj_in", "1": "layers.0", "2": "proj_out"}
+_GAUSS = "prompt_encoder.pe_layer.positional_encoding_gaussian_matrix"
+
+
+def _inv(d):
+    return {v: k for k, v in d.items()}
+
+
+def pth_to_hf(name):
+    """A key of segment_anything's Sam.state_dict() -> the key of transformers' SamModel.state_dict(); None: no place."""
+    if name == _GAUSS:
+        return TIED[1]
+    if name.startswith("image_encoder."):
+        k = name[len("image_encoder."):]
+        k = re.sub(r"^blocks\.(\d+)\.norm([12])\.", r"layers.\1.layer_norm\2.", k)
+        k = re.sub(r"^blocks\.", "layers.", k)
+        k = re.sub(r"^patch_embed\.proj\.", "patch_embed.projection.", k)
+        m = re.match(r"^neck\.(\d)\.(.*)$", k)
+        if m:
+            if m.group(1) not in _NECK:
+                return None
+            k = f"neck.{_NECK[m.group(1)]}.{m.group(2)}"
+        return VISION + k
+    if name.startswith("prompt_encoder."):
+        k = name[len("prompt_encoder."):]
+        k = re.sub(r"^point_embeddings\.", "point_embed.", k)
+        m = re.match(r"^mask_downscaling\.(\d)\.(.*)$", k)
+        if m:
+            if m.group(1) not in _DOWN:
+                return None
+            k = f"mask_embed.{_DOWN[m.group(1)]}.{m.group(2)}"
+        return "prompt_encoder." + k
+    if name.startswith("mask_decoder."):
+        k = name[len("mask_decoder."):]
+        k = re.sub(r"^(transformer\.layers\.\d+)\.norm([1-4])\.", r"\1.layer_norm\2.", k)
+        k = re.sub(r"^transformer\.norm_final_attn\.", "transformer.layer_norm_final_attn.", k)
+        m = re.match(r"^output_upscaling\.(\d)\.(.*)$", k)
+        if m:
+            if m.group(1) not in _UP:
+                return None
+            k = f"{_UP[m.group(1)]}.{m.group(2)}"
+        m = re.match(r"^(output_hypernetworks_mlps\.\d+|iou_prediction_head)\.layers\.(\d)\.(.*)$", k)
+        if m:
+            if m.group(2) not in _MLP:
+                return None
+            k = f"{m.group(1)}.{_MLP[m.group(2)]}.{m.group(3)}"
+        return "mask_decoder." + k
+    return None
+
+
+def hf_to_pth(name):
+    """The inverse of pth_to_hf (the tied copy of the positional embedding has no key of its own: None)."""
+    if name == TIED[1]:
+        return _GAUSS
+    if name == TIED[0]:
+        return None
+    if name.startswith(VISION):
+        k = name[len(VISION):]
+        k = re.sub(r"^layers\.(\d+)\.layer_norm([12])\.", r"blocks.\1.norm\2.", k)
+        k = re.sub(r"^layers\.", "blocks.", k)
+        k = re.sub(r"^patch_embed\.projection\.", "patch_embed.proj.", k)
+        m = re.match(r"^neck\.(conv1|layer_norm1|conv2|layer_norm2)\.(.*)$", k)
+        if m:
+            k = f"neck.{_inv(_NECK)[m.group(1)]}.{m.group(2)}"
+        return "image_encoder." + k
+    if name.startswith("prompt_encoder."):
+        k = name[len("prompt_encoder."):]
+        k = re.sub(r"^point_embed\.", "point_embeddings.", k)
+        m = re.match(r"^mask_embed\.(\w+)\.(.*)$", k)
+        if m:
+            k = f"mask_downscaling.{_inv(_DOWN)[m.group(1)]}.{m.group(2)}"
+        return "prompt_encoder." + k
+    if name.startswith("mask_decoder."):
+        k = name[len("mask_decoder."):]
+        k = re.sub(r"^(transformer\.layers\.\d+)\.layer_norm([1-4])\.", r"\1.norm\2.", k)
+        k = re.sub(r"^transformer\.layer_norm_final_attn\.", "transformer.norm_final_attn.", k)
+        m = re.match(r"^(upscale_conv1|upscale_layer_norm|upscale_conv2)\.(.*)$", k)
+        if m:
+            k = f"output_upscaling.{_inv(_UP)[m.group(1)]}.{m.group(2)}"
+        m = re.match(r"^(output_hypernetworks_mlps\.\d+|iou_prediction_head)\.(proj_in|layers\.0|proj_out)\.(.*)$", k)
+        if m:
+            k = f"{m.group(1)}.layers.{_inv(_MLP)[m.group(2)]}.{m.group(3)}"
+        return "mask_decoder." + k
+    return None
+
+
+def _config_from_pth(sd):
+    """The encoder's shape read off the tensors of a segment_anything checkpoint."""
+    pos = sd["image_encoder.pos_embed"]
+    g, hidden = int(pos.shape[1]), int(pos.shape[3])
+    layers = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("image_encoder.blocks."))
+    head_dim = int(sd["image_encoder.blocks.0.attn.rel_pos_h"].shape[1])
+    rows = [int(sd[f"image_encoder.blocks.{l}.attn.rel_pos_h"].shape[0]) for l in range(layers)]
+    glob = tuple(l for l in range(layers) if rows[l] == 2 * g - 1)
+    win = [(r + 1) // 2 for l, r in enumerate(rows) if l not in glob]
+    return SamConfig(hidden_size=hidden, num_hidden_layers=layers, num_attention_heads=hidden // head_dim,
+                     mlp_dim=int(sd["image_encoder.blocks.0.mlp.lin1.weight"].shape[0]), window_size=win[0] if win else g,
+                     global_attn_indexes=glob, output_channels=int(sd["image_encoder.neck.0.weight"].shape[0]), image_size=PATCH * g)
+
+
+def load_sam_weights(path):
+    """A LOCAL directory with config.json and model.safetensors under SamModel's names, or a LOCAL .pth under
+    segment_anything's Sam.state_dict() names (identification/weights/sam_vit_h_4b8939.pth).  Nothing here opens a URL.
+    Raises on any key it cannot place and on any key left unfilled."""
+    path = os.fspath(path)
+    if os.path.isdir(path):
+        with open(os.path.join(path, "config.json")) as f:
+            cfg = SamConfig.from_json(json.load(f))
+        from safetensors.torch import load_file
+        return SamWeights(cfg, load_file(os.path.join(path, "model.safetensors"), device="cpu"))
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"sam: {path!r} is neither a local directory nor a local .pth file.  The weights are never downloaded")
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    tensors = {}
+    for k, v in sd.items():
+        name = pth_to_hf(k)
+        if name is None:
+            raise KeyError(f"sam weights: {k} of {path} has no place in SamModel")
+        tensors[name] = v
+    return SamWeights(_config_from_pth(sd), tensors)
+
+
+def save_sam_weights(weights, directory):
+    """Writes what load_sam_weights reads from a directory (config.json, model.safetensors)."""
+    from safetensors.torch import save_file
+    if not weights.decoder:
+        raise ValueError("sam: only weights with a decoder can be saved")
+    os.makedirs(directory, exist_ok=True)
+    with open(os.path.join(directory, "config.json"), "w") as f:
+        json.dump(weights.config.to_json(), f, indent=1)
+    save_file({k: t.cpu().clone().contiguous() for k, t in weights.tensors.items()}, os.path.join(directory, "model.safetensors"))
+
+
+def random_sam_weights(config=None, seed=0, decoder=None):
+    """Seeded stand-ins at a scale where every part of the network shows in the output: linear, convolution and patch
+    weights N(0, 1/fan_in), pos_embed and the embeddings N(0, 1), relative-position tables N(0, 1/head_dim), LayerNorm gains
+    U(0.5, 1.5), biases N(0, 0.1^2), everything rounded to fp16.  decoder: default, whenever the encoder has 256 channels."""
+    cfg = config or SamConfig()
+    decoder = cfg.output_channels == DECODER_CHANNELS if decoder is None else decoder
+    g = torch.Generator().manual_seed(seed)
+    tensors = {}
+    for name, shape in _shapes(cfg).items():
+        if not (decoder or name.startswith(VISION)) or name == TIED[0]:
+            continue
+        if "rel_pos_" in name:
+            t = torch.randn(shape, generator=g) / math.sqrt(cfg.head_dim)
+        elif name.endswith("pos_embed") or name.endswith("positional_embedding") or len(shape) == 2 and shape[0] <= 8 and "embed" in name \
+                or name.endswith("_token.weight") or name.endswith("_tokens.weight"):
+            t = torch.randn(shape, generator=g)
+        elif "norm" in name and name.endswith(".weight"):
+            t = 0.5 + torch.rand(shape, generator=g)
+        elif name.endswith(".bias"):
+            t = 0.1 * torch.randn(shape, generator=g)
+        else:
+            t = torch.randn(shape, generator=g) / math.sqrt(math.prod(shape[1:]))
+        tensors[name] = t.to(torch.float16)
+    return SamWeights(cfg, tensors, decoder=decoder)
+
+
+# ---------------------------------------------------------------- the twin
+def host_encoder(weights, dtype=torch.float64, device="cpu"):
+    """transformers' SamVisionEncoder holding these tensors, in `dtype` on `device`, in eval mode."""
+    from transformers.models.sam.modeling_sam import SamVisionEncoder
+    model = SamVisionEncoder(weights.config.to_hf().vision_config)
+    model.load_state_dict(weights.sub(VISION), strict=True)
+    return model.to(device=device, dtype=dtype).eval()
+
+
+@torch.no_grad()
+def sam_host(weights, pixel_values, dtype=torch.float64, device=None, model=None):
+    """[C,g,g] of pixel_values [3,S,S] through the library's own encoder."""
+    device = pixel_values.device if device is None else device
+    model = host_encoder(weights, dtype, device) if model is None else model
+    x = pixel_values.reshape(1, 3, *pixel_values.shape[-2:]).to(device=device, dtype=dtype)
+    return model(x).last_hidden_state[0]
+
+
+# ---------------------------------------------------------------- the encoder
+class SamImageEncoder:
+    """encode(pixel_values f32 [3,S,S] on the device) -> f32 [C,g,g], on the kernels."""
+
+    def __init__(self, weights):
+        self.weights, self.config = weights, weights.config
+        self._on = {}
+
+    def _device(self, dev):
+        hit = self._on.get(dev)
+        if hit is None:
+            cfg = self.config
+            w = self.weights.to(dev)
+            tensors = w.table()
+            table = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+            windows = (C.c_int32 * cfg.num_hidden_layers)(*cfg.windows())
+            rows = (C.c_int32 * cfg.num_hidden_layers)(*[int(w.tensors[f"{VISION}layers.{l}.attn.rel_pos_h"].shape[0])
+                                                         for l in range(cfg.num_hidden_layers)])
+            for l in range(cfg.num_hidden_layers):
+                a, b = (w.tensors[f"{VISION}layers.{l}.attn.rel_pos_{x}"] for x in "hw")
+                if a.shape != b.shape:
+                    raise ValueError(f"sam: rel_pos_h and rel_pos_w of layer {l} differ in shape")
+            c = _lib.GsrSamConfig(cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers, cfg.mlp_dim,
+                                  cfg.output_channels, cfg.image_size, cfg.layer_norm_eps, windows, rows)
+            L = _lib.lib()
+            nbytes = L.gsr_sam_workspace_bytes(C.byref(c))
+            hit = self._on[dev] = dict(w=w, table=table, n=len(tensors), cfg=c, keep=(windows, rows), nbytes=nbytes,
+                                       ws=workspace(nbytes, dev) if nbytes else None)
+        return hit
+
+    @torch.no_grad()
+    def encode(self, pixel_values):
+        if not isinstance(pixel_values, torch.Tensor) or not pixel_values.is_cuda:
+            raise _lib.GsrError("sam: pixel_values must live on the device (no CPU path; see sam_host)")
+        S, cfg = self.config.image_size, self.config
+        x = pixel_values.detach().reshape(-1, S, S) if pixel_values.numel() == 3 * S * S else pixel_values
+        if tuple(x.shape) != (3, S, S):
+            raise ValueError(f"sam: expected [3,{S},{S}], got {list(pixel_values.shape)}")
+        x = x.to(torch.float32).contiguous()
+        dev = x.device
+        d = self._device(dev)
+        out = torch.empty(cfg.output_channels, cfg.grid, cfg.grid, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().gsr_sam_encode(C.byref(d["cfg"]), d["table"], d["n"], ptr(x), ptr(d["ws"]), d["nbytes"], ptr(out),
+                                             stream(dev)))
+        return out
+
+
+def preprocess(image_u8, image_size=1024):
+    """HxWx3 uint8 -> (pixel_values f32 [3,S,S] on the host, input_size (ih, iw), mask_size (oh, ow)).  The reference's
+    resize to a long side <= 1024 (identification/sam.py:71-76; mask_size is that picture's size, which the masks come out
+    at), ResizeLongestSide to `image_size`, normalisation, then zero padding."""
+    from PIL import Image
+    img = Image.fromarray(np.ascontiguousarray(image_u8, np.uint8)[..., :3])
+    w, h = img.size
+    if max(h, w) > MAX_SIDE:
+        scale = MAX_SIDE / max(h, w)
+        img = img.resize((int(w * scale), int(h * scale)), Image.BILINEAR)
+    ow, oh = img.size
+    scale = image_size * 1.0 / max(oh, ow)
+    ih, iw = int(oh * scale + 0.5), int(ow * scale + 0.5)
+    if (ih, iw) != (oh, ow):
+        img = img.resize((iw, ih), Image.BILINEAR)
+    x = torch.from_numpy(np.asarray(img, np.uint8).copy()).permute(2, 0, 1).to(torch.float32)
+    x = (x - torch.tensor(IMAGE_MEAN).view(3, 1, 1)) / torch.tensor(IMAGE_STD).view(3, 1, 1)
+    out = torch.zeros(3, image_size, image_size, dtype=torch.float32)
+    out[:, :ih, :iw] = x
+    return out, (ih, iw), (oh, ow)
+
+
+def point_grid(n, input_size):
+    """f32 [n n,2] (x, y): ((i + 0.5) / n, (j + 0.5) / n) with x fastest, scaled to the input frame (ih, iw)."""
+    c = (torch.arange(n, dtype=torch.float64) + 0.5) / n
+    xy = torch.stack([c[None, :].expand(n, n), c[:, None].expand(n, n)], -1).reshape(-1, 2)
+    return (xy * torch.tensor([input_size[1], input_size[0]], dtype=torch.float64)).to(torch.float32)
+
+
+# ---------------------------------------------------------------- selection: the torch twins
+def nms_host(boxes, scores, keep_in, theta):
+    """SM_NMS in torch: -> int64 indices of the kept boxes, by score descending (ties by index ascending)."""
+    boxes, scores = boxes.to(torch.float32), scores.to(torch.float32)
+    cand = torch.ones_like(scores, dtype=torch.bool) if keep_in is None else keep_in.to(torch.bool)
+    cand = cand & ~torch.isnan(scores)
+    idx = torch.nonzero(cand).reshape(-1)
+    idx = idx[torch.sort(scores[idx], descending=True, stable=True).indices]
+    b = boxes[idx]
+    area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    dead = torch.zeros(len(idx), dtype=torch.bool, device=boxes.device)
+    kept = []
+    for i in range(len(idx)):
+        if dead[i]:
+            continue
+        kept.append(int(idx[i]))
+        w = (torch.minimum(b[i, 2], b[i + 1:, 2]) - torch.maximum(b[i, 0], b[i + 1:, 0])).clamp(min=0)
+        h = (torch.minimum(b[i, 3], b[i + 1:, 3]) - torch.maximum(b[i, 1], b[i + 1:, 1])).clamp(min=0)
+        inter = w * h
+        dead[i + 1:] |= inter / (area[i] + area[i + 1:] - inter) > theta
+    return torch.tensor(kept, dtype=torch.int64, device=boxes.device)
+
+
+def upsample_host(logits, input_size, mask_size, dtype=None):
+    """[n,L,L] -> [n,oh,ow]: F.interpolate(L -> 4 L), the crop to input_size, F.interpolate to mask_size (bilinear,
+    align_corners=False), in `dtype` (default: the logits' own)."""
+    x = logits.to(dtype or logits.dtype)[:, None]
+    S = 4 * logits.shape[-1]
+    x = F.interpolate(x, (S, S), mode="bilinear", align_corners=False)[..., :input_size[0], :input_size[1]]
+    return F.interpolate(x, tuple(mask_size), mode="bilinear", align_corners=False)[:, 0]
+
+
+def mask_stats_host(values, tau=MASK_THRESHOLD, delta=1.0):
+    """(area, inter, union int64 [n], boxes f32 [n,4] inclusive XYXY, zeros when empty) of planes [n,h,w]."""
+    on = values > tau
+    area, inter, union = on.flatten(1).sum(1), (values > tau + delta).flatten(1).sum(1), (values > tau - delta).flatten(1).sum(1)
+    n, h, w = on.shape
+    cols, rows = on.any(1), on.any(2)
+    big = max(h, w)
+    xs, ys = torch.arange(w, device=on.device), torch.arange(h, device=on.device)
+    x0, x1 = torch.where(cols, xs, big).min(1).values, torch.where(cols, xs, -1).max(1).values
+    y0, y1 = torch.where(rows, ys, big).min(1).values, torch.where(rows, ys, -1).max(1).values
+    boxes = torch.stack([x0, y0, x1, y1], 1).to(torch.float32)
+    boxes[area == 0] = 0
+    return area, inter, union, boxes
+
+
+def select_host(low_res, iou, input_size, mask_size, pred_iou_thresh=0.86, stability_score_thresh=0.92, stability_score_offset=1.0,
+                box_nms_thresh=0.7, dtype=None, chunk=64):
+    """SamMaskGenerator.select in torch (any device): the same gates in the same order on up-sampled planes."""
+    L = low_res.shape[-1]
+    logits, scores = low_res.reshape(-1, L, L), iou.reshape(-1).to(torch.float32)
+    n = logits.shape[0]
+    first = scores > pred_iou_thresh
+    area, inter, union = (torch.zeros(n, dtype=torch.int64, device=logits.device) for _ in range(3))
+    boxes = torch.zeros(n, 4, dtype=torch.float32, device=logits.device)
+    todo = torch.nonzero(first).reshape(-1)
+    for part in todo.split(chunk):
+        a, i, u, b = mask_stats_host(upsample_host(logits[part], input_size, mask_size, dtype), MASK_THRESHOLD, stability_score_offset)
+        area[part], inter[part], union[part], boxes[part] = a, i, u, b
+    stab = inter.to(torch.float32) / union.to(torch.float32)
+    keep_in = first & (stab >= stability_score_thresh)            # 0 / 0 is NaN and fails
+    index = nms_host(boxes, scores, keep_in, box_nms_thresh)
+    masks = torch.zeros(len(index), *mask_size, dtype=torch.uint8, device=logits.device)
+    for part in torch.arange(len(index), device=logits.device).split(chunk):
+        masks[part] = (upsample_host(logits[index[part]], input_size, mask_size, dtype) > MASK_THRESHOLD).to(torch.uint8)
+    return dict(masks=masks, index=index, area=area[index], boxes=boxes[index], predicted_iou=scores[index],
+                stability_score=stab[index], keep_in=keep_in, stability_all=stab)
+
+
+# ---------------------------------------------------------------- the generator
+class SamMaskGenerator:
+    """The reference's SamAutomaticMaskGenerator for one full-image crop.  host=True: the encoder through transformers'
+    SamVisionEncoder in fp32 and the selection through select_host, on the same device."""
+
+    def __init__(self, weights, points_per_side=32, points_per_batch=64, pred_iou_thresh=0.86, stability_score_thresh=0.92,
+                 stability_score_offset=1.0, box_nms_thresh=0.7, host=False, device="cuda"):
+        if not weights.decoder:
+            raise ValueError("sam: the mask generator needs weights with the prompt encoder and the mask decoder")
+        self.weights, self.config, self.device, self.host = weights, weights.config, torch.device(device), bool(host)
+        self.points_per_side, self.points_per_batch = int(points_per_side), int(points_per_batch)
+        self.pred_iou_thresh, self.stability_score_thresh = float(pred_iou_thresh), float(stability_score_thresh)
+        self.stability_score_offset, self.box_nms_thresh = float(stability_score_offset), float(box_nms_thresh)
+        self.encoder = None if host else SamImageEncoder(weights)
+        self._host_encoder = self._modules = None
+        self.last_ms = {}
+
+    # -- the torch modules of the decoder
+    def _decoder(self):
+        if self._modules is None:
+            from transformers.models.sam.modeling_sam import SamPromptEncoder, SamMaskDecoder, SamPositionalEmbedding
+            hf = self.config.to_hf()
+            prompt, decoder, shared = SamPromptEncoder(hf), SamMaskDecoder(hf.mask_decoder_config), SamPositionalEmbedding(hf.vision_config)
+            prompt.load_state_dict(self.weights.sub("prompt_encoder."), strict=True)
+            decoder.load_state_dict(self.weights.sub("mask_decoder."), strict=True)
+            shared.load_state_dict(self.weights.sub("shared_image_embedding."), strict=True)
+            prompt, decoder, shared = (m.to(self.device).eval() for m in (prompt, decoder, shared))
+            g = self.config.grid
+            c = (torch.arange(g, device=self.device, dtype=torch.float32) + 0.5) / g      # get_image_wide_positional_embeddings
+            wide = shared(torch.stack([c[None, :].expand(g, g), c[:, None].expand(g, g)], -1)).permute(2, 0, 1)[None]
+            self._modules = (prompt, decoder, wide)
+        return self._modules
+
+    @torch.no_grad()
+    def embed(self, image):
+        """HxWx3 uint8 -> dict(emb f32 [1,C,g,g] on the device, input_size, mask_size)."""
+        x, input_size, mask_size = preprocess(image, self.config.image_size)
+        x = x.to(self.device)
+        if self.host:
+            if self._host_encoder is None:
+                self._host_encoder = host_encoder(self.weights, torch.float32, self.device)
+            emb = sam_host(self.weights, x, torch.float32, self.device, self._host_encoder)
+        else:
+            emb = self.encoder.encode(x)
+        return dict(emb=emb[None].to(torch.float32), input_size=input_size, mask_size=mask_size)
+
+    @torch.no_grad()
+    def decode(self, emb, points):
+        """emb [1,C,g,g], points f32 [P,2] (x, y) in the input frame -> (low_res f32 [P,3,L,L], iou f32 [P,3])."""
+        prompt, decoder, wide = self._decoder()
+        low, iou = [], []
+        for part in points.to(self.device).split(self.points_per_batch):
+            pts = part[None, :, None, :]
+            labels = torch.ones(1, part.shape[0], 1, dtype=torch.int64, device=self.device)
+            sparse, dense = prompt(pts, labels, None, None)
+            m, q = decoder(image_embeddings=emb, image_positional_embeddings=wide, sparse_prompt_embeddings=sparse,
+                           dense_prompt_embeddings=dense, multimask_output=True)
+            low.append(m[0])
+            iou.append(q[0])
+        return torch.cat(low).to(torch.float32).contiguous(), torch.cat(iou).to(torch.float32).contiguous()
+
+    @torch.no_grad()
+    def select(self, low_res, iou, input_size, mask_size):
+        """The reference's gates in its order: iou > pred_iou_thresh; inter / union >= stability_score_thresh (0 / 0 is
+        rejected); SM_NMS; SM_EMIT.  Candidates are ordered point-major, then mask index.  One host synchronisation, for
+        the kept count.  -> dict(masks uint8 [m,oh,ow], index, area, boxes XYXY inclusive, predicted_iou, stability_score)."""
+        args = (self.pred_iou_thresh, self.stability_score_thresh, self.stability_score_offset, self.box_nms_thresh)
+        if self.host:
+            return select_host(low_res, iou, input_size, mask_size, *args)
+        if not low_res.is_cuda:
+            raise _lib.GsrError("sam: select needs device tensors (no CPU path; see select_host)")
+        dev, Lr = low_res.device, int(low_res.shape[-1])
+        logits = low_res.reshape(-1, Lr, Lr).to(torch.float32).contiguous()
+        scores = iou.reshape(-1).to(torch.float32).contiguous()
+        n = logits.shape[0]
+        (ih, iw), (oh, ow) = input_size, mask_size
+        L = _lib.lib()
+        first = scores > self.pred_iou_thresh
+        skip = (~first).to(torch.uint8)
+        counts = torch.empty(n, 3, dtype=torch.int32, device=dev)
+        boxes = torch.empty(n, 4, dtype=torch.float32, device=dev)
+        _lib.check(L.gsr_sam_mask_score(ptr(logits), n, Lr, ih, iw, oh, ow, MASK_THRESHOLD, self.stability_score_offset, ptr(skip),
+                                        ptr(counts), ptr(boxes), stream(dev)))
+        stab = counts[:, 1].to(torch.float32) / counts[:, 2].to(torch.float32)
+        keep_in = (first & (stab >= self.stability_score_thresh)).to(torch.uint8)
+        kept = torch.empty(n, dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        nbytes = L.gsr_sam_nms_workspace_bytes(n)
+        ws = workspace(nbytes, dev)
+        _lib.check(L.gsr_sam_nms(ptr(boxes), ptr(scores), ptr(keep_in), n, self.box_nms_thresh, ptr(ws), nbytes, ptr(kept), ptr(count),
+                                 stream(dev)))
+        m = int(count.item())           # the one synchronisation
+        index = kept[:m].contiguous()
+        masks = torch.empty(m, oh, ow, dtype=torch.uint8, device=dev)
+        _lib.check(L.gsr_sam_mask_emit(ptr(logits), n, Lr, ih, iw, oh, ow, MASK_THRESHOLD, ptr(index), m, ptr(masks), stream(dev)))
+        idx = index.to(torch.int64)
+        return dict(masks=masks, index=idx, area=counts[idx, 0].to(torch.int64), boxes=boxes[idx], predicted_iou=scores[idx],
+                    stability_score=stab[idx], keep_in=keep_in.to(torch.bool), stability_all=stab)
+
+    def _run(self, image):
+        def tick():
+            if self.device.type == "cuda":
+                torch.cuda.synchronize(self.device)
+            return time.perf_counter()
+        t0 = tick()
+        e = self.embed(image)
+        t1 = tick()
+        points = point_grid(self.points_per_side, e["input_size"])
+        low, iou = self.decode(e["emb"], points)
+        t2 = tick()
+        sel = self.select(low, iou, e["input_size"], e["mask_size"])
+        t3 = tick()
+        self.last_ms = {"embed": 1e3 * (t1 - t0), "decode": 1e3 * (t2 - t1), "select": 1e3 * (t3 - t2)}
+        return e, points, sel
+
+    def generate_device(self, image):
+        """uint8 [m,oh,ow] on the device, in NMS order: index k is segment id k in segment_init.label_points."""
+        return self._run(image)[2]["masks"]
+
+    def generate(self, image):
+        """The reference's list of dicts, in NMS order."""
+        e, points, sel = self._run(image)
+        (ih, iw), (oh, ow) = e["input_size"], e["mask_size"]
+        masks = sel["masks"].cpu().numpy().astype(bool)
+        boxes, area = sel["boxes"].cpu().numpy(), sel["area"].cpu().numpy()
+        piou, stab, index = sel["predicted_iou"].cpu().numpy(), sel["stability_score"].cpu().numpy(), sel["index"].cpu().numpy()
+        pts = points.numpy().astype(np.float64) * np.array([ow / iw, oh / ih])
+        out = []
+        for k in range(len(index)):
+            x0, y0, x1, y1 = (int(v) for v in boxes[k])
+            out.append({"segmentation": masks[k], "area": int(area[k]), "bbox": [x0, y0, x1 - x0, y1 - y0],
+                        "predicted_iou": float(piou[k]), "point_coords": [[float(v) for v in pts[index[k] // 3]]],
+                        "stability_score": float(stab[k]), "crop_box": [0, 0, ow, oh]})
+        return out
+
+
+def save_segments_boxes(masks, path):
+    """identification/sam.py:118-134: masks, boxes as XYXY = [x, y, x + w, y + h], areas."""
+    seg = [m["segmentation"] for m in masks]
+    boxes = [[m["bbox"][0], m["bbox"][1], m["bbox"][0] + m["bbox"][2], m["bbox"][1] + m["bbox"][3]] for m in masks]
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.savez(path, masks=np.array(seg), boxes=np.array(boxes), areas=np.array([m["area"] for m in masks]))

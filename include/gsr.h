@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define GSR_ABI_VERSION 17  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
+#define GSR_ABI_VERSION 18  /* 5: BINNING carries row_count / slot_off / the scan workspace, 72-byte gradient rows, GsrRowScanJob;
                                 6: gsr_surface_maps_forward / _backward;
                                 7: TSDF fusion and marching cubes (GsrTsdfVolume, gsr_tsdf_*, gsr_mcubes_*);
                                 8: mesh post-processing (gsr_mesh_*) and gsr_depth_aabb;
@@ -47,7 +47,8 @@ extern "C" {
                                 14: unbounded mesh export (GsrUnbView, gsr_unb_*);
                                 15: LPIPS (gsr_lpips_*);
                                 16: frame kernels of the trajectory and viewer pictures (gsr_frame_*);
-                                17: DINOv3 ViT encoder and its cosine term (GsrDinoConfig, gsr_dino_*) */
+                                17: DINOv3 ViT encoder and its cosine term (GsrDinoConfig, gsr_dino_*);
+                                18: SAM image encoder and mask selection (GsrSamConfig, gsr_sam_*) */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -1188,6 +1189,115 @@ int32_t gsr_dino_forward(const GsrDinoConfig* cfg, const void* const* weights_ho
                          const float* x1, int32_t B, int32_t H, int32_t W, void* ws, size_t ws_bytes, float* pooled,
                          float* last_hidden, gsr_stream_t stream);
 int32_t gsr_dino_cosine(const float* a, const float* b, int32_t n, float lambda16, float* out, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- SAM automatic mask generation
+ * transformers' SamVisionEncoder (models/sam/modeling_sam.py; segment_anything's ImageEncoderViT), which the reference's
+ * SAMSegmentation runs in fp32 inside SamAutomaticMaskGenerator (identification/sam.py:41-46,65-92), and the selection of that
+ * generator's candidate masks, as inference kernels (sam.hip; Python: gaussmart_amd/sam.py).  The prompt encoder and the mask
+ * decoder are not here.  Patch 16 x 16, g = image_size / 16 tokens per side (g <= 256), T = g g; head_dim 64 or 80, hidden =
+ * heads head_dim; hidden, mlp_dim and output_channels multiples of 64; layers >= 1; per layer a window size w (0: global
+ * attention, else w >= 1); ln_eps 1e-6; one image per call.  A layer's two relative-position tables have EXACTLY 2 s - 1
+ * rows, s = g for a global layer and s = w otherwise (then the twin's F.interpolate of the table is the identity); any
+ * other length is refused.  EVERY weight is fp16; the residual stream, the LayerNorm statistics and the softmax are fp32:
+ * the deviation from the twin's fp16 model that DN_* states, and from the reference's fp32 model in the operands'
+ * precision.  Matrix products outside attention are DN_LINEAR (one k-ascending fp32 chain per element) with the epilogues
+ * below, LayerNorms are DN_NORM.  Rules, with every rounding:
+ *   SV_EMBED   pixel_values f32 [3,S,S], normalised and padded by the caller, ROUNDED TO fp16; the 16x16 stride-16
+ *              convolution is a product over K = 768 in DN_EMBED's k order (k = c 256 + ky 16 + kx), fp32 accumulation,
+ *              v = acc + fp32(bias[n]), then v + fp32(pos_embed[y][x][n]): two fp32 additions, stored as fp32.  Output: the
+ *              fp32 stream [T,hidden], row-major over the grid; no prefix tokens.
+ *   layer      xn = DN_NORM(stream) fp16; qkv = DN_LINEAR(xn, qkv.weight, qkv.bias) ROUNDED TO fp16 [T,3 hidden] (q of
+ *              head h in columns h head_dim .., k at hidden + .., v at 2 hidden + ..); SV_ATTN; stream += proj (+ bias):
+ *              resid = resid + (acc + bias), ONE fp32 addition after the bias's (no LayerScale); xn = DN_NORM(stream);
+ *              lin1 with exact GELU (GSR_DINO_EPI_GELU) ROUNDED TO fp16; stream += lin2 (+ bias) likewise.
+ *   SV_ATTN    per head and window.  s = g: one window; s = w: ceil(g / w)^2 windows over the grid zero-padded AFTER
+ *              layer_norm1.  A padded position is a real KEY of its window: its k and v are the k and v thirds of qkv.bias
+ *              (what DN_LINEAR gives on a zero row: fp16(0 + fp32(bias)) = bias), read from the bias; the padded layout is
+ *              synthesised, never stored.  Padded QUERIES are not computed into memory or written.  Bias pre-pass (one
+ *              launch per layer): rh[q][kh] = sum_d fp32(q_d) fp32(Rh[qh - kh + s - 1][d]), rw likewise over columns, q the
+ *              UNSCALED fp16 query, d ascending, the products exact in fp32, one fp32 rounding per addition, STORED AS
+ *              fp32 [T,heads,2,s] (2 s values per query and head, not a score row).  Score, fp32, in this order:
+ *              t = (((sum_d q_d k_d) * fp32(head_dim^-1/2)) + rh[q][kh]) + rw[q][kw], then t2 = t * fp32(log2 e): FOUR fp32
+ *              roundings after the fp32 chain of the product.  One pass over KV tiles of 64 window positions (row-major in
+ *              the window) with a running maximum m and sum l in fp32: p = 2^(t2 - m) (v_exp_f32), l adds the UNROUNDED
+ *              p, p is ROUNDED TO fp16 for the P V product (fp16 v, fp32 accumulation, rescaled by 2^(m_old - m_new)); out =
+ *              acc / l in fp32, ROUNDED TO fp16 [T,hidden].  No score matrix over all keys exists in memory for any layer.
+ *              head_dim 80 is five k-steps of 16; the output tiles cover 96 rows of which rows 80..95 are zeros and never
+ *              stored.  Positions past s s are never read (scores -inf before the maximum).  A window's bits depend on its
+ *              own data only, not on the workgroup that runs it.
+ *   SV_NECK    the stream ROUNDED TO fp16; conv1 (1x1, no bias): DN_LINEAR over K = hidden, stored as fp32; channel
+ *              LayerNorm per token (DN_NORM, eps 1e-6) ROUNDED TO fp16; conv2 (3x3, padding 1, no bias): DN_LINEAR over
+ *              K = 9 C with k = c 9 + ky 3 + kx (Conv2d's own weight layout [C,C,3,3]), zero rows outside the grid, stored
+ *              as fp32; channel LayerNorm in fp32, not rounded.  Output f32 [C,g,g].
+ *   SM_SCORE   logits f32 [n,L,L]; S = 4 L; input size (ih, iw) <= S; output size (oh, ow); threshold tau, offset delta; a
+ *              skip byte per mask (NULL: none).  The value at output pixel (y, x) is F.interpolate(L -> S, bilinear,
+ *              align_corners=False), the crop [:ih,:iw], then F.interpolate((ih, iw) -> (oh, ow)), evaluated on the fly from
+ *              at most 16 taps, all in fp32 without contraction.  One interpolation along an axis: src = max(scale (dst +
+ *              0.5) - 0.5, 0) with scale = 0.25 for the first step and fp32(in) / fp32(out) for the second; i0 = floor(src),
+ *              i1 = min(i0 + 1, in - 1), l = src - i0; value = (1 - ly) ((1 - lx) v00 + lx v01) + ly ((1 - lx) v10 + lx
+ *              v11), where the second step's v are first-step values.  (oh, ow) = (ih, iw): the second step is skipped, as
+ *              it is the identity.  No up-sampled plane exists in memory.  Per mask: int32 counts[3] = {area: values > tau,
+ *              inter: > tau + delta, union: > tau - delta} (tau +- delta one fp32 operation each) and the box of the > tau set
+ *              as inclusive XYXY in f32, [0,0,0,0] when the set is empty.  One workgroup per mask, integer sums: thread t
+ *              takes pixels t, t + 256, ..., then a fixed tree; no float atomics; the same bits on every run.  A mask with
+ *              skip set is not read; its counts and box are zeros.
+ *   SM_NMS     boxes f32 [n,4] XYXY, scores f32 [n], keep_in bytes (NULL: all), theta; n <= 3 64^2.  Candidates: keep_in
+ *              set and a score that is not NaN.  Order: score descending, ties by index ascending.  iou = inter / (a1 + a2
+ *              - inter) in fp32 without contraction, areas (x1 - x0)(y1 - y0) (no + 1: torchvision.ops.box_iou), inter =
+ *              max(min(x1) - max(x0), 0) max(min(y1) - max(y0), 0).  A box is suppressed if a KEPT earlier box has iou >
+ *              theta; NaN compares false (two zero-area boxes keep each other).  Output: the kept indices in that order
+ *              and their count, on the device.
+ *   SM_EMIT    for index[m] (mask numbers; outside 0..n-1: a zero plane) the > tau set as uint8 [m,oh,ow], from the same
+ *              device function as SM_SCORE: a pixel SM_SCORE counted is set here, bit for bit.  m <= 65535.
+ * Weight table of gsr_sam_encode: a HOST array of gsr_sam_num_weights(layers) DEVICE pointers to fp16 arrays (16-byte
+ * aligned), none NULL, in this order (names: SamVisionEncoder.state_dict()):
+ *   GSR_SAM_W_PATCH_W patch_embed.projection.weight [hidden,768]; _PATCH_B its bias; _POS pos_embed [g,g,hidden];
+ *   per layer l at GSR_SAM_W_LAYER0 + GSR_SAM_W_PER_LAYER l + GSR_SAM_L_*: layers.l.layer_norm1.weight, .bias, attn.qkv.weight
+ *   [3 hidden,hidden], attn.qkv.bias, attn.rel_pos_h [2 s - 1,head_dim], attn.rel_pos_w, attn.proj.weight, .bias,
+ *   layer_norm2.weight, .bias, mlp.lin1.weight [mlp_dim,hidden], .bias, mlp.lin2.weight, .bias;
+ *   last (GSR_SAM_W_NECK entries): neck.conv1.weight [C,hidden], neck.layer_norm1.weight, .bias, neck.conv2.weight [C,C,3,3],
+ *   neck.layer_norm2.weight, .bias.
+ * GsrSamConfig.window_host and .rel_rows_host are HOST arrays of `layers` entries: the window size of each layer and the row
+ * count of its two tables (the C side cannot see a device array's length).
+ * Entry points (all on the caller's stream, the caller owns every buffer, nothing synchronises):
+ *   gsr_sam_embed / _attn / _neck / _mask_score / _nms / _mask_emit : one rule each; ws from the *_workspace_bytes beside it.
+ *       _attn: qkv fp16 [g g,3 hidden] as the layer rule lays it out; window 0 = global; out fp16 [g g,hidden].
+ *   gsr_sam_encode : the encoder; pixel_values f32 [3,S,S]; out f32 [C,g,g]; ws: gsr_sam_workspace_bytes(cfg) (0 for a
+ *       refused configuration).
+ * Any other configuration, a null required pointer, a workspace that is too small, a weight table or a relative-position
+ * table of the wrong length: GSR_E_INVALID before anything is launched, with a message. */
+typedef struct GsrSamConfig {
+    int32_t hidden, heads, head_dim, layers, mlp_dim, output_channels, image_size;
+    float ln_eps;
+    const int32_t* window_host;
+    const int32_t* rel_rows_host;
+} GsrSamConfig;
+enum { GSR_SAM_W_PATCH_W = 0, GSR_SAM_W_PATCH_B, GSR_SAM_W_POS, GSR_SAM_W_LAYER0 };
+enum { GSR_SAM_L_NORM1_W = 0, GSR_SAM_L_NORM1_B, GSR_SAM_L_QKV_W, GSR_SAM_L_QKV_B, GSR_SAM_L_REL_H, GSR_SAM_L_REL_W, GSR_SAM_L_PROJ_W,
+       GSR_SAM_L_PROJ_B, GSR_SAM_L_NORM2_W, GSR_SAM_L_NORM2_B, GSR_SAM_L_LIN1_W, GSR_SAM_L_LIN1_B, GSR_SAM_L_LIN2_W, GSR_SAM_L_LIN2_B,
+       GSR_SAM_W_PER_LAYER };
+enum { GSR_SAM_W_NECK = 6 };
+size_t gsr_sam_embed_workspace_bytes(int32_t image_size);
+int32_t gsr_sam_embed(const float* pixel_values, int32_t image_size, int32_t hidden, const void* patch_w, const void* patch_b,
+                      const void* pos_embed, void* ws, size_t ws_bytes, float* out, gsr_stream_t stream);
+size_t gsr_sam_attn_workspace_bytes(int32_t g, int32_t window, int32_t heads);
+int32_t gsr_sam_attn(const void* qkv, const void* qkv_bias, const void* rel_pos_h, const void* rel_pos_w, int32_t rel_rows, int32_t g,
+                     int32_t window, int32_t heads, int32_t head_dim, void* ws, size_t ws_bytes, void* out, gsr_stream_t stream);
+size_t gsr_sam_neck_workspace_bytes(int32_t g, int32_t hidden, int32_t channels);
+int32_t gsr_sam_neck(const float* x, int32_t g, int32_t hidden, int32_t channels, const void* conv1_w, const void* ln1_w,
+                     const void* ln1_b, const void* conv2_w, const void* ln2_w, const void* ln2_b, void* ws, size_t ws_bytes,
+                     float* out, gsr_stream_t stream);
+size_t gsr_sam_workspace_bytes(const GsrSamConfig* cfg);
+int32_t gsr_sam_num_weights(int32_t layers);
+int32_t gsr_sam_encode(const GsrSamConfig* cfg, const void* const* weights_host, int32_t n_weights, const float* pixel_values,
+                       void* ws, size_t ws_bytes, float* out, gsr_stream_t stream);
+int32_t gsr_sam_mask_score(const float* logits, int32_t n, int32_t L, int32_t ih, int32_t iw, int32_t oh, int32_t ow, float tau,
+                           float delta, const uint8_t* skip, int32_t* counts, float* boxes, gsr_stream_t stream);
+int32_t gsr_sam_mask_emit(const float* logits, int32_t n, int32_t L, int32_t ih, int32_t iw, int32_t oh, int32_t ow, float tau,
+                          const int32_t* index, int32_t m, uint8_t* out, gsr_stream_t stream);
+size_t gsr_sam_nms_workspace_bytes(int32_t n);
+int32_t gsr_sam_nms(const float* boxes, const float* scores, const uint8_t* keep_in, int32_t n, float theta, void* ws,
+                    size_t ws_bytes, int32_t* kept, int32_t* count, gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only
