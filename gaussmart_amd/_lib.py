@@ -21,6 +21,8 @@ GSR_LPIPS_ALEX, GSR_LPIPS_VGG = 0, 1
 GSR_DINO_EPI_BIAS, GSR_DINO_EPI_GELU, GSR_DINO_EPI_RESID = 0, 1, 2
 GSR_DINO_W_LAYER0, GSR_DINO_W_PER_LAYER = 4, 18      # include/gsr.h: the weight table of gsr_dino_forward
 GSR_SAM_W_LAYER0, GSR_SAM_W_PER_LAYER, GSR_SAM_W_NECK = 3, 14, 6     # include/gsr.h: the weight table of gsr_sam_encode
+# include/gsr.h: the weight table of gsr_sam_decode (head, per two-way layer, final attention, up-scaling, hypernetworks, IoU head)
+GSR_SAMD_W_LAYER0, GSR_SAMD_W_PER_LAYER, GSR_SAMD_W_FINAL, GSR_SAMD_W_UP, GSR_SAMD_W_HYPER, GSR_SAMD_W_IOU, GSR_SAMD_W_COUNT = 6, 36, 78, 88, 94, 112, 118
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_SCRATCH, GSR_BUF_SCRATCH2 = range(5)
 GSR_BUF_SYNC_SH = 100     # not a buffer: "the SH colour pass is about to be enqueued" (GSR_FLAG_DEFER_COLOR)
@@ -372,7 +374,16 @@ def lib():
                 ("gsr_sam_mask_score", C.c_int32, [vp] + [C.c_int32] * 6 + [C.c_float, C.c_float, vp, vp, vp, vp]),
                 ("gsr_sam_mask_emit", C.c_int32, [vp] + [C.c_int32] * 6 + [C.c_float, vp, C.c_int32, vp, vp]),
                 ("gsr_sam_nms_workspace_bytes", sz, [C.c_int32]),
-                ("gsr_sam_nms", C.c_int32, [vp, vp, vp, C.c_int32, C.c_float, vp, sz, vp, vp, vp])):
+                ("gsr_sam_nms", C.c_int32, [vp, vp, vp, C.c_int32, C.c_float, vp, sz, vp, vp, vp]),
+                ("gsr_sam_dec_prompt", C.c_int32, [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]),
+                ("gsr_sam_dec_t2i", C.c_int32, [vp] * 4 + [C.c_int32] * 3 + [vp, vp]),
+                ("gsr_sam_dec_i2t_workspace_bytes", sz, [C.c_int32] * 2),
+                ("gsr_sam_dec_i2t", C.c_int32, [vp] * 5 + [C.c_int32] * 3 + [vp] * 5 + [sz, vp, vp]),
+                ("gsr_sam_dec_upscale_workspace_bytes", sz, [C.c_int32] * 2),
+                ("gsr_sam_dec_upscale", C.c_int32, [vp, C.c_int32, C.c_int32] + [vp] * 8 + [sz, vp, vp]),
+                ("gsr_sam_dec_num_weights", C.c_int32, []),
+                ("gsr_sam_decode_workspace_bytes", sz, [C.c_int32] * 2),
+                ("gsr_sam_decode", C.c_int32, [C.c_int32, C.POINTER(vp), C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, sz, vp, vp, vp])):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]

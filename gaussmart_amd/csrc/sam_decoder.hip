@@ -1,0 +1,695 @@
+// SAM's prompt encoder and mask decoder (transformers' SamPromptEncoder / SamMaskDecoder with the stock configuration: hidden
+// 256, two two-way layers, 8 heads, 4 mask tokens, one foreground point per prompt, multimask output) as kernels.  The rules
+// are in include/gsr.h (SD_PROMPT, SD_IMAGE, SD_TOKENS, SD_T2I, SD_I2T, SD_UP, SD_HEADS); each has one named place below.
+// Every matrix product with a weight is DN_LINEAR (dino.hip, through dino_internal.h): fp16 operands, one k-ascending fp32
+// chain per output element, rows independent of each other.  The attention cores, the LayerNorms of the image stream and the
+// mask product are the kernels of this file.  No split-K, no float atomics: a point's bits depend on its own data only.
+#include "dino_internal.h"
+
+#define SD_C 256           // hidden
+#define SD_CI 128           // internal width of the cross attentions: 8 heads of 16
+#define SD_HEADS_N 8
+#define SD_TOK 7            // iou, 4 mask tokens, the point, not-a-point
+#define SD_MLP 2048
+#define SD_MAX_GRID 64
+#define SD_MAX_POINTS 65535
+#define SD_EPS 1e-6f        // SamMaskDecoderConfig.layer_norm_eps and SamLayerNorm's default
+#define SD_EPS_FINAL 1e-5f  // layer_norm_final_attn is a plain nn.LayerNorm
+
+typedef _Float16 sd_h4 __attribute__((ext_vector_type(4)));
+typedef _Float16 sd_h8 __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ float sd_wave_sum(float v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ float sd_wave_max(float v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
+    return v;
+}
+__device__ __forceinline__ float sd_gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
+
+// ---------------------------------------------------------------- SD_PROMPT
+// out[p][0][c] = sinf(arg_c) + fp32(point1[c]), out[p][0][128 + c] = cosf(arg_c) + fp32(point1[128 + c]), out[p][1][:] = fp32(nap);
+// arg_c = (ax G[0][c] + ay G[1][c]) * fp32(2 pi), a = 2 ((coordinate + 0.5) / S) - 1: every operation one fp32 rounding.
+__global__ void __launch_bounds__(128) sd_prompt_kernel(const float* __restrict__ points, float S, const float* __restrict__ G,
+                                                        const dn_half* __restrict__ point1, const dn_half* __restrict__ nap,
+                                                        float* __restrict__ out) {
+    const int64_t p = blockIdx.x;
+    const int c = threadIdx.x;
+    const float ax = 2.0f * ((points[2 * p] + 0.5f) / S) - 1.0f, ay = 2.0f * ((points[2 * p + 1] + 0.5f) / S) - 1.0f;
+    const float arg = (ax * G[c] + ay * G[128 + c]) * 6.28318530717958647692f;
+    float* o = out + p * 2 * SD_C;
+    o[c] = sinf(arg) + (float)point1[c];
+    o[128 + c] = cosf(arg) + (float)point1[128 + c];
+    o[SD_C + c] = (float)nap[c];
+    o[SD_C + 128 + c] = (float)nap[128 + c];
+}
+
+static int sd_prompt(const float* points, int P, int S, const float* G, const dn_half* point1, const dn_half* nap, float* out,
+                     hipStream_t s) {
+    hipLaunchKernelGGL(sd_prompt_kernel, dim3((unsigned)P), dim3(128), 0, s, points, (float)S, G, point1, nap, out);
+    GSR_LAUNCH_CHECK();
+    return GSR_OK;
+}
+
+static int sd_check_points(int P) {
+    if (P < 1 || P > SD_MAX_POINTS) { gsr_set_error("sam decoder: P %d is outside 1 .. %d", P, SD_MAX_POINTS); return GSR_E_INVALID; }
+    return GSR_OK;
+}
+static int sd_check_grid(int g) {
+    if (g < 1 || g > SD_MAX_GRID) { gsr_set_error("sam decoder: grid %d is outside 1 .. %d", g, SD_MAX_GRID); return GSR_E_INVALID; }
+    return GSR_OK;
+}
+
+extern "C" int32_t gsr_sam_dec_prompt(const float* points, int32_t P, int32_t image_size, const float* gauss, const void* point1,
+                                      const void* not_a_point, float* out, gsr_stream_t stream_) {
+    int rc;
+    if ((rc = sd_check_points(P)) != GSR_OK) return rc;
+    if (image_size < 16 || image_size > 16 * SD_MAX_GRID) {
+        gsr_set_error("sam decoder: image_size %d is outside 16 .. %d", image_size, 16 * SD_MAX_GRID);
+        return GSR_E_INVALID;
+    }
+    if (!points || !gauss || !point1 || !not_a_point || !out) {
+        gsr_set_error("sam dec prompt: points / gauss / point1 / not_a_point / out is null");
+        return GSR_E_INVALID;
+    }
+    return sd_prompt(points, P, image_size, gauss, static_cast<const dn_half*>(point1), static_cast<const dn_half*>(not_a_point), out,
+                     static_cast<hipStream_t>(stream_));
+}
+
+// ---------------------------------------------------------------- SD_IMAGE (layout)
+// E16[t][c] = fp16(emb[c][t] + fp32(no_mask[c])), PE16[t][c] = fp16(pe[c][t])
+__global__ void __launch_bounds__(256) sd_image_kernel(const float* __restrict__ emb, const float* __restrict__ pe,
+                                                       const dn_half* __restrict__ no_mask, int T, dn_half* __restrict__ E16,
+                                                       dn_half* __restrict__ PE16) {
+    const int i = (int)blockIdx.x * 256 + threadIdx.x;
+    if (i >= T * SD_C) return;
+    const int t = i / SD_C, c = i - t * SD_C;
+    E16[i] = (dn_half)(emb[(int64_t)c * T + t] + (float)no_mask[c]);
+    PE16[i] = (dn_half)pe[(int64_t)c * T + t];
+}
+
+// ---------------------------------------------------------------- SD_TOKENS (elementwise parts)
+// tok[p][j]: j = 0 iou_token, 1..4 mask_tokens, 5 and 6 the two sparse tokens of the point; written twice (queries and their
+// positional term are the same tensor at the start)
+__global__ void __launch_bounds__(256) sd_tokens_kernel(const dn_half* __restrict__ iou_tok, const dn_half* __restrict__ mask_tok,
+                                                        const float* __restrict__ sparse, float* __restrict__ tok0,
+                                                        float* __restrict__ q) {
+    const int64_t p = blockIdx.x;
+    const int c = threadIdx.x;
+    for (int j = 0; j < SD_TOK; ++j) {
+        float v;
+        if (j == 0) v = (float)iou_tok[c];
+        else if (j < 5) v = (float)mask_tok[(j - 1) * SD_C + c];
+        else v = sparse[(p * 2 + (j - 5)) * SD_C + c];
+        tok0[(p * SD_TOK + j) * SD_C + c] = v;
+        q[(p * SD_TOK + j) * SD_C + c] = v;
+    }
+}
+
+// y = fp16(a + b) (b NULL: fp16(a))
+__global__ void __launch_bounds__(256) sd_addcast_kernel(const float* __restrict__ a, const float* __restrict__ b, int64_t n,
+                                                         dn_half* __restrict__ y) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = (dn_half)(b ? a[i] + b[i] : a[i]);
+}
+
+__global__ void __launch_bounds__(256) sd_relu_kernel(dn_half* __restrict__ x, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && x[i] < (dn_half)0.f) x[i] = (dn_half)0.f;
+}
+
+// token self-attention: 7 queries, 7 keys, 8 heads of 32; q, k, v f32 [P,7,256]; thread = (head, query); out fp16
+__global__ void __launch_bounds__(64) sd_self_attn_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                          const float* __restrict__ v, dn_half* __restrict__ out) {
+    const int64_t p = blockIdx.x;
+    const int t = threadIdx.x;
+    if (t >= SD_HEADS_N * SD_TOK) return;
+    const int h = t / SD_TOK, i = t - h * SD_TOK;
+    const float* qr = q + (p * SD_TOK + i) * SD_C + h * 32;
+    float s[SD_TOK], m = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < SD_TOK; ++j) {
+        const float* kr = k + (p * SD_TOK + j) * SD_C + h * 32;
+        float acc = 0.f;
+        for (int d = 0; d < 32; ++d) acc = fmaf(qr[d], kr[d], acc);
+        s[j] = acc * 0.17677669529663688110f;       // 32^-1/2
+        m = fmaxf(m, s[j]);
+    }
+    float l = 0.f;
+#pragma unroll
+    for (int j = 0; j < SD_TOK; ++j) {
+        s[j] = expf(s[j] - m);
+        l += s[j];
+    }
+    dn_half* o = out + (p * SD_TOK + i) * SD_C + h * 32;
+    for (int d = 0; d < 32; ++d) {
+        float acc = 0.f;
+#pragma unroll
+        for (int j = 0; j < SD_TOK; ++j) acc = fmaf(s[j], v[(p * SD_TOK + j) * SD_C + h * 32 + d], acc);
+        o[d] = (dn_half)(acc / l);
+    }
+}
+
+// ---------------------------------------------------------------- SD_T2I
+// One workgroup per (point, head): 7 queries of 16 over T keys.  Thread t takes keys t, t + 256, ... in order; the key is
+// fp32(kx) + kpe (kpe NULL: fp32(kx)), the score (sum_d q_d k_d, d ascending, fmaf) * scale.  Pass 1: the maximum per query
+// (xor butterfly over the wave, then the four waves).  Pass 2 computes the same scores again, p = expf(s - m), and adds p and
+// p v per thread in key order; the 64 lanes are added by a xor butterfly, the four waves in order.  out = fp16(acc / l).
+__global__ void __launch_bounds__(256) sd_t2i_kernel(const float* __restrict__ q, const dn_half* __restrict__ kx,
+                                                     const float* __restrict__ kpe, const dn_half* __restrict__ v, int T,
+                                                     int64_t kv_stride, float scale, dn_half* __restrict__ out) {
+    __shared__ float qs[SD_TOK][16];
+    __shared__ float red[4][SD_TOK * 17];
+    const int64_t p = blockIdx.x;
+    const int h = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t < SD_TOK * 16) qs[t >> 4][t & 15] = q[(p * SD_TOK + (t >> 4)) * SD_CI + h * 16 + (t & 15)];
+    __syncthreads();
+    const dn_half* kp = kx + p * kv_stride + h * 16;
+    const dn_half* vp = v + p * kv_stride + h * 16;
+    const float* pp = kpe ? kpe + h * 16 : nullptr;
+    auto scores = [&](int key, float* s) {
+        float kk[16];
+        const sd_h8 a = *reinterpret_cast<const sd_h8*>(kp + (int64_t)key * SD_CI), b = *reinterpret_cast<const sd_h8*>(kp + (int64_t)key * SD_CI + 8);
+#pragma unroll
+        for (int d = 0; d < 8; ++d) { kk[d] = (float)a[d]; kk[8 + d] = (float)b[d]; }
+        if (pp) {
+#pragma unroll
+            for (int d = 0; d < 16; ++d) kk[d] = kk[d] + pp[(int64_t)key * SD_CI + d];
+        }
+#pragma unroll
+        for (int j = 0; j < SD_TOK; ++j) {
+            float acc = 0.f;
+#pragma unroll
+            for (int d = 0; d < 16; ++d) acc = fmaf(qs[j][d], kk[d], acc);
+            s[j] = acc * scale;
+        }
+    };
+    float m[SD_TOK];
+#pragma unroll
+    for (int j = 0; j < SD_TOK; ++j) m[j] = -INFINITY;
+    for (int key = t; key < T; key += 256) {
+        float s[SD_TOK];
+        scores(key, s);
+#pragma unroll
+        for (int j = 0; j < SD_TOK; ++j) m[j] = fmaxf(m[j], s[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < SD_TOK; ++j) m[j] = sd_wave_max(m[j]);
+    if (lane == 0)
+#pragma unroll
+        for (int j = 0; j < SD_TOK; ++j) red[wave][j] = m[j];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < SD_TOK; ++j) m[j] = fmaxf(fmaxf(red[0][j], red[1][j]), fmaxf(red[2][j], red[3][j]));
+    __syncthreads();        // red is written again below
+
+    float l[SD_TOK], acc[SD_TOK][16];
+#pragma unroll
+    for (int j = 0; j < SD_TOK; ++j) {
+        l[j] = 0.f;
+#pragma unroll
+        for (int d = 0; d < 16; ++d) acc[j][d] = 0.f;
+    }
+    for (int key = t; key < T; key += 256) {
+        float s[SD_TOK], vv[16];
+        scores(key, s);
+        const sd_h8 a = *reinterpret_cast<const sd_h8*>(vp + (int64_t)key * SD_CI), b = *reinterpret_cast<const sd_h8*>(vp + (int64_t)key * SD_CI + 8);
+#pragma unroll
+        for (int d = 0; d < 8; ++d) { vv[d] = (float)a[d]; vv[8 + d] = (float)b[d]; }
+#pragma unroll
+        for (int j = 0; j < SD_TOK; ++j) {
+            const float pr = expf(s[j] - m[j]);
+            l[j] += pr;
+#pragma unroll
+            for (int d = 0; d < 16; ++d) acc[j][d] = fmaf(pr, vv[d], acc[j][d]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < SD_TOK; ++j) {
+        l[j] = sd_wave_sum(l[j]);
+#pragma unroll
+        for (int d = 0; d < 16; ++d) acc[j][d] = sd_wave_sum(acc[j][d]);
+    }
+    if (lane == 0)
+#pragma unroll
+        for (int j = 0; j < SD_TOK; ++j) {
+            red[wave][j * 17 + 16] = l[j];
+#pragma unroll
+            for (int d = 0; d < 16; ++d) red[wave][j * 17 + d] = acc[j][d];
+        }
+    __syncthreads();
+    if (t < SD_TOK * 16) {
+        const int j = t >> 4, d = t & 15;
+        const float lt = ((red[0][j * 17 + 16] + red[1][j * 17 + 16]) + red[2][j * 17 + 16]) + red[3][j * 17 + 16];
+        const float at = ((red[0][j * 17 + d] + red[1][j * 17 + d]) + red[2][j * 17 + d]) + red[3][j * 17 + d];
+        out[(p * SD_TOK + j) * SD_CI + h * 16 + d] = (dn_half)(at / lt);
+    }
+}
+
+static int sd_t2i(const float* q, const dn_half* kx, const float* kpe, const dn_half* v, int P, int T, int shared, float scale,
+                  dn_half* out, hipStream_t s) {
+    hipLaunchKernelGGL(sd_t2i_kernel, dim3((unsigned)P, SD_HEADS_N), dim3(256), 0, s, q, kx, kpe, v, T,
+                       shared ? (int64_t)0 : (int64_t)T * SD_CI, scale, out);
+    GSR_LAUNCH_CHECK();
+    return GSR_OK;
+}
+
+extern "C" int32_t gsr_sam_dec_t2i(const float* q, const void* kx, const float* kpe, const void* v, int32_t P, int32_t T,
+                                   int32_t shared, void* out, gsr_stream_t stream_) {
+    int rc;
+    if ((rc = sd_check_points(P)) != GSR_OK) return rc;
+    if (T < 1 || T > SD_MAX_GRID * SD_MAX_GRID) { gsr_set_error("sam dec t2i: T %d is outside 1 .. %d", T, SD_MAX_GRID * SD_MAX_GRID); return GSR_E_INVALID; }
+    if (!q || !kx || !v || !out) { gsr_set_error("sam dec t2i: q / kx / v / out is null"); return GSR_E_INVALID; }
+    return sd_t2i(q, static_cast<const dn_half*>(kx), kpe, static_cast<const dn_half*>(v), P, T, shared != 0, 0.25f,
+                  static_cast<dn_half*>(out), static_cast<hipStream_t>(stream_));
+}
+
+// ---------------------------------------------------------------- SD_I2T
+// thread = (image token, head); the 7 keys and values of the point are in LDS.  q = fp32(qx) + qpe; s_j = (sum_d q_d k_jd) *
+// 1/4, d ascending, fmaf; p_j = expf(s_j - max); ctx_d = (sum_j p_j v_jd) / (sum_j p_j), j ascending; stored as fp16.
+__global__ void __launch_bounds__(256) sd_i2t_kernel(const dn_half* __restrict__ qx, const float* __restrict__ qpe,
+                                                     const float* __restrict__ k, const float* __restrict__ v, int T,
+                                                     int64_t q_stride, dn_half* __restrict__ ctx) {
+    __shared__ float ks[SD_TOK * SD_CI], vs[SD_TOK * SD_CI];
+    const int64_t p = blockIdx.y;
+    const int t = threadIdx.x;
+    for (int i = t; i < SD_TOK * SD_CI; i += 256) {
+        ks[i] = k[p * SD_TOK * SD_CI + i];
+        vs[i] = v[p * SD_TOK * SD_CI + i];
+    }
+    __syncthreads();
+    const int tok = (int)blockIdx.x * 32 + (t >> 3), h = t & 7;
+    if (tok >= T) return;
+    const dn_half* qr = qx + p * q_stride + (int64_t)tok * SD_CI + h * 16;
+    const float* pr = qpe + (int64_t)tok * SD_CI + h * 16;
+    const sd_h8 a = *reinterpret_cast<const sd_h8*>(qr), b = *reinterpret_cast<const sd_h8*>(qr + 8);
+    float qq[16];
+#pragma unroll
+    for (int d = 0; d < 8; ++d) { qq[d] = (float)a[d] + pr[d]; qq[8 + d] = (float)b[d] + pr[8 + d]; }
+    float s[SD_TOK], m = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < SD_TOK; ++j) {
+        float acc = 0.f;
+#pragma unroll
+        for (int d = 0; d < 16; ++d) acc = fmaf(qq[d], ks[j * SD_CI + h * 16 + d], acc);
+        s[j] = acc * 0.25f;
+        m = fmaxf(m, s[j]);
+    }
+    float l = 0.f;
+#pragma unroll
+    for (int j = 0; j < SD_TOK; ++j) {
+        s[j] = expf(s[j] - m);
+        l += s[j];
+    }
+    sd_h8 o[2];
+#pragma unroll
+    for (int d = 0; d < 16; ++d) {
+        float acc = 0.f;
+#pragma unroll
+        for (int j = 0; j < SD_TOK; ++j) acc = fmaf(s[j], vs[j * SD_CI + h * 16 + d], acc);
+        o[d >> 3][d & 7] = (dn_half)(acc / l);
+    }
+    dn_half* dst = ctx + (p * T + tok) * SD_CI + h * 16;
+    *reinterpret_cast<sd_h8*>(dst) = o[0];
+    *reinterpret_cast<sd_h8*>(dst + 8) = o[1];
+}
+
+// x_out[row] = fp16(LayerNorm(fp32(x[row]) + a[row])): one wave per row of 256, a lane owns channels 4 lane .. 4 lane + 3;
+// DN_NORM's formula (mean = sum / 256, biased variance of the differences), the lanes added by a xor butterfly.  x may be
+// x_out (a row is read completely before it is written).
+__global__ void __launch_bounds__(256) sd_addnorm_kernel(const dn_half* x, const float* __restrict__ a, int64_t rows, int T,
+                                                         int64_t x_stride, const dn_half* __restrict__ g,
+                                                         const dn_half* __restrict__ beta, float eps, dn_half* x_out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int64_t p = row / T, tok = row - p * T;
+    const sd_h4 xv = *reinterpret_cast<const sd_h4*>(x + p * x_stride + tok * SD_C + 4 * lane);
+    const float4 av = *reinterpret_cast<const float4*>(a + row * SD_C + 4 * lane);
+    float y[4] = {(float)xv[0] + av.x, (float)xv[1] + av.y, (float)xv[2] + av.z, (float)xv[3] + av.w};
+    const float mean = sd_wave_sum(((y[0] + y[1]) + y[2]) + y[3]) / (float)SD_C;
+    float var = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        y[e] = y[e] - mean;
+        var += y[e] * y[e];
+    }
+    const float rstd = 1.0f / sqrtf(sd_wave_sum(var) / (float)SD_C + eps);
+    sd_h4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (dn_half)(y[e] * rstd * (float)g[4 * lane + e] + (float)beta[4 * lane + e]);
+    *reinterpret_cast<sd_h4*>(x_out + row * SD_C + 4 * lane) = o;
+}
+
+// ctx fp16 [P T,128] and att f32 [P T,256] are the caller's
+static int sd_i2t(const dn_half* qx, const float* qpe, const float* k, const float* v, const dn_half* x, int P, int T, int shared,
+                  const dn_half* ow, const dn_half* ob, const dn_half* lw, const dn_half* lb, dn_half* ctx, float* att, dn_half* x_out,
+                  hipStream_t s) {
+    int rc;
+    const int64_t rows = (int64_t)P * T;
+    hipLaunchKernelGGL(sd_i2t_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)P), dim3(256), 0, s, qx, qpe, k, v, T,
+                       shared ? (int64_t)0 : (int64_t)T * SD_CI, ctx);
+    GSR_LAUNCH_CHECK();
+    if ((rc = dn_linear(ctx, ow, ob, nullptr, att, rows, SD_CI, SD_C, DN_EPI_F32, 1, 0, 0, s)) != GSR_OK) return rc;
+    hipLaunchKernelGGL(sd_addnorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, att, rows, T,
+                       shared ? (int64_t)0 : (int64_t)T * SD_C, lw, lb, SD_EPS, x_out);
+    GSR_LAUNCH_CHECK();
+    return GSR_OK;
+}
+
+struct SdI2tLayout {
+    size_t total;
+    dn_half* ctx;
+    float* att;
+    SdI2tLayout(int P, int T, void* ws) {
+        GsrWsCursor cur(ws);
+        ctx = cur.take<dn_half>((size_t)P * T * SD_CI * 2);
+        att = cur.take<float>((size_t)P * T * SD_C * 4);
+        total = cur.off;
+    }
+};
+
+extern "C" size_t gsr_sam_dec_i2t_workspace_bytes(int32_t P, int32_t T) {
+    if (P < 1 || P > SD_MAX_POINTS || T < 1 || T > SD_MAX_GRID * SD_MAX_GRID) return 0;
+    return SdI2tLayout(P, T, nullptr).total;
+}
+
+extern "C" int32_t gsr_sam_dec_i2t(const void* qx, const float* qpe, const float* k, const float* v, const void* x, int32_t P, int32_t T,
+                                   int32_t shared, const void* out_w, const void* out_b, const void* ln_w, const void* ln_b, void* ws,
+                                   size_t ws_bytes, void* x_out, gsr_stream_t stream_) {
+    int rc;
+    if ((rc = sd_check_points(P)) != GSR_OK) return rc;
+    if (T < 1 || T > SD_MAX_GRID * SD_MAX_GRID) { gsr_set_error("sam dec i2t: T %d is outside 1 .. %d", T, SD_MAX_GRID * SD_MAX_GRID); return GSR_E_INVALID; }
+    if (!qx || !qpe || !k || !v || !x || !out_w || !out_b || !ln_w || !ln_b || !x_out) {
+        gsr_set_error("sam dec i2t: an input, a weight or x_out is null");
+        return GSR_E_INVALID;
+    }
+    SdI2tLayout lay(P, T, ws);
+    if (!ws || ws_bytes < lay.total) {
+        gsr_set_error("ws_bytes: sam dec i2t workspace too small (%zu < %zu bytes)", ws_bytes, lay.total);
+        return GSR_E_INVALID;
+    }
+    auto hp = [](const void* p) { return static_cast<const dn_half*>(p); };
+    return sd_i2t(hp(qx), qpe, k, v, hp(x), P, T, shared != 0, hp(out_w), hp(out_b), hp(ln_w), hp(ln_b), lay.ctx, lay.att,
+                  static_cast<dn_half*>(x_out), static_cast<hipStream_t>(stream_));
+}
+
+// ---------------------------------------------------------------- SD_UP
+// rows of 64 channels (one output pixel of the first transposed convolution each): fp16(gelu(LayerNorm(row))); one wave per
+// row, a lane per channel
+__global__ void __launch_bounds__(256) sd_up_norm_kernel(const float* __restrict__ u, int64_t rows, const dn_half* __restrict__ g,
+                                                         const dn_half* __restrict__ beta, dn_half* __restrict__ y) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float x = u[row * 64 + lane];
+    const float mean = sd_wave_sum(x) / 64.0f;
+    const float d = x - mean;
+    const float rstd = 1.0f / sqrtf(sd_wave_sum(d * d) / 64.0f + SD_EPS);
+    y[row * 64 + lane] = (dn_half)sd_gelu(d * rstd * (float)g[lane] + (float)beta[lane]);
+}
+
+// low_res[p][m][Y][X] = sum_c hyper[m][p][c] fp32(c2[((p T + t) 4 + tap1) 128 + tap2 32 + c]), c ascending, fmaf; t = (Y >> 2) g +
+// (X >> 2), tap1 = ((Y >> 1) & 1) 2 + ((X >> 1) & 1), tap2 = (Y & 1) 2 + (X & 1).  A thread per output pixel, X fastest.
+__global__ void __launch_bounds__(256) sd_mask_kernel(const dn_half* __restrict__ c2, const float* __restrict__ hyper, int g, int P,
+                                                      float* __restrict__ low_res) {
+    __shared__ float hs[3 * 32];
+    const int64_t p = blockIdx.y;
+    const int L = 4 * g;
+    if (threadIdx.x < 96) hs[threadIdx.x] = hyper[((int64_t)(threadIdx.x >> 5) * P + p) * 32 + (threadIdx.x & 31)];
+    __syncthreads();
+    const int i = (int)blockIdx.x * 256 + threadIdx.x;
+    if (i >= L * L) return;
+    const int Y = i / L, X = i - Y * L;
+    const int64_t t = (int64_t)(Y >> 2) * g + (X >> 2);
+    const int tap1 = ((Y >> 1) & 1) * 2 + ((X >> 1) & 1), tap2 = (Y & 1) * 2 + (X & 1);
+    const dn_half* src = c2 + (((p * g * g + t) * 4 + tap1) * 128 + tap2 * 32);
+    float acc[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const sd_h8 a = *reinterpret_cast<const sd_h8*>(src + 8 * q);
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+#pragma unroll
+            for (int m = 0; m < 3; ++m) acc[m] = fmaf(hs[m * 32 + 8 * q + e], (float)a[e], acc[m]);
+    }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) low_res[((p * 3 + m) * L + Y) * L + X] = acc[m];
+}
+
+// u32 f32 [P T,256] (later fp16 [P T 4,128] in the same bytes) and u16 fp16 [P T 4,64] are the caller's
+static int sd_upscale(const dn_half* x, int g, int P, const dn_half* c1w, const dn_half* c1b, const dn_half* lw, const dn_half* lb,
+                      const dn_half* c2w, const dn_half* c2b, const float* hyper, float* u32, dn_half* u16, float* low_res,
+                      hipStream_t s) {
+    int rc;
+    const int64_t rows = (int64_t)P * g * g;
+    if ((rc = dn_linear(x, c1w, c1b, nullptr, u32, rows, SD_C, SD_C, DN_EPI_F32, 1, 0, 0, s)) != GSR_OK) return rc;
+    hipLaunchKernelGGL(sd_up_norm_kernel, dim3((unsigned)(rows)), dim3(256), 0, s, u32, rows * 4, lw, lb, u16);
+    GSR_LAUNCH_CHECK();
+    dn_half* c2 = reinterpret_cast<dn_half*>(u32);
+    if ((rc = dn_linear(u16, c2w, c2b, nullptr, c2, rows * 4, 64, 128, DN_EPI_GELU, 1, 0, 0, s)) != GSR_OK) return rc;
+    const int L = 4 * g;
+    hipLaunchKernelGGL(sd_mask_kernel, dim3((unsigned)((L * L + 255) / 256), (unsigned)P), dim3(256), 0, s, c2, hyper, g, P, low_res);
+    GSR_LAUNCH_CHECK();
+    return GSR_OK;
+}
+
+struct SdUpLayout {
+    size_t total;
+    float* u32;
+    dn_half* u16;
+    SdUpLayout(int g, int P, void* ws) {
+        GsrWsCursor cur(ws);
+        u32 = cur.take<float>((size_t)P * g * g * SD_C * 4);
+        u16 = cur.take<dn_half>((size_t)P * g * g * 4 * 64 * 2);
+        total = cur.off;
+    }
+};
+
+extern "C" size_t gsr_sam_dec_upscale_workspace_bytes(int32_t g, int32_t P) {
+    if (g < 1 || g > SD_MAX_GRID || P < 1 || P > SD_MAX_POINTS) return 0;
+    return SdUpLayout(g, P, nullptr).total;
+}
+
+extern "C" int32_t gsr_sam_dec_upscale(const void* x, int32_t g, int32_t P, const void* conv1_w, const void* conv1_b, const void* ln_w,
+                                       const void* ln_b, const void* conv2_w, const void* conv2_b, const float* hyper, void* ws,
+                                       size_t ws_bytes, float* low_res, gsr_stream_t stream_) {
+    int rc;
+    if ((rc = sd_check_grid(g)) != GSR_OK || (rc = sd_check_points(P)) != GSR_OK) return rc;
+    if (!x || !conv1_w || !conv1_b || !ln_w || !ln_b || !conv2_w || !conv2_b || !hyper || !low_res) {
+        gsr_set_error("sam dec upscale: x / a weight / hyper / low_res is null");
+        return GSR_E_INVALID;
+    }
+    SdUpLayout lay(g, P, ws);
+    if (!ws || ws_bytes < lay.total) {
+        gsr_set_error("ws_bytes: sam dec upscale workspace too small (%zu < %zu bytes)", ws_bytes, lay.total);
+        return GSR_E_INVALID;
+    }
+    auto hp = [](const void* p) { return static_cast<const dn_half*>(p); };
+    return sd_upscale(hp(x), g, P, hp(conv1_w), hp(conv1_b), hp(ln_w), hp(ln_b), hp(conv2_w), hp(conv2_b), hyper, lay.u32, lay.u16,
+                      low_res, static_cast<hipStream_t>(stream_));
+}
+
+// ---------------------------------------------------------------- SD_HEADS (gather)
+// rows[k][p] = fp16(tokens[p][k == 0 ? 0 : k + 1]): the iou token and mask tokens 1..3
+__global__ void __launch_bounds__(256) sd_heads_gather_kernel(const float* __restrict__ q, int P, dn_half* __restrict__ rows) {
+    const int64_t p = blockIdx.x;
+    const int c = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) rows[((int64_t)k * P + p) * SD_C + c] = (dn_half)q[(p * SD_TOK + (k == 0 ? 0 : k + 1)) * SD_C + c];
+}
+
+// ---------------------------------------------------------------- the whole decoder
+struct SdLayout {
+    size_t total;
+    // per image
+    dn_half *E16, *PE16, *kx0, *v0, *qx0;
+    float* pe_proj[5];      // t2i layer 0, i2t layer 0, t2i layer 1, i2t layer 1, final: proj(pe) + bias, f32 [T,128]
+    // tokens
+    float *sparse, *tok0, *qa, *qb, *qf, *kf, *vf, *hyper;
+    dn_half *h16, *h16b, *c16, *m16, *heads16, *t16a, *t16b;
+    // per point and image token
+    dn_half *x16, *b1, *b2;
+    float* a32;
+    SdLayout(int g, int P, void* ws) {
+        const size_t T = (size_t)g * g, R = (size_t)P * SD_TOK, PT = (size_t)P * T;
+        GsrWsCursor cur(ws);
+        E16 = cur.take<dn_half>(T * SD_C * 2);
+        PE16 = cur.take<dn_half>(T * SD_C * 2);
+        kx0 = cur.take<dn_half>(T * SD_CI * 2);
+        v0 = cur.take<dn_half>(T * SD_CI * 2);
+        qx0 = cur.take<dn_half>(T * SD_CI * 2);
+        for (int i = 0; i < 5; ++i) pe_proj[i] = cur.take<float>(T * SD_CI * 4);
+        sparse = cur.take<float>((size_t)P * 2 * SD_C * 4);
+        tok0 = cur.take<float>(R * SD_C * 4);
+        qa = cur.take<float>(R * SD_C * 4);
+        qb = cur.take<float>(R * SD_C * 4);
+        qf = cur.take<float>(R * SD_C * 4);
+        kf = cur.take<float>(R * SD_C * 4);
+        vf = cur.take<float>(R * SD_C * 4);
+        hyper = cur.take<float>((size_t)3 * P * 32 * 4);
+        h16 = cur.take<dn_half>(R * SD_C * 2);
+        h16b = cur.take<dn_half>(R * SD_C * 2);
+        c16 = cur.take<dn_half>(R * SD_C * 2);
+        m16 = cur.take<dn_half>(R * SD_MLP * 2);
+        heads16 = cur.take<dn_half>((size_t)4 * P * SD_C * 2);
+        t16a = cur.take<dn_half>((size_t)P * SD_C * 2);
+        t16b = cur.take<dn_half>((size_t)P * SD_C * 2);
+        x16 = cur.take<dn_half>(PT * SD_C * 2);
+        // b1 and b2 are contiguous: together they hold the up-scaling's fp16 [P T 4,64]
+        const size_t half_bytes = gsr_align(PT * SD_CI * 2);
+        b1 = cur.take<dn_half>(2 * half_bytes);
+        b2 = b1 ? reinterpret_cast<dn_half*>(reinterpret_cast<char*>(b1) + half_bytes) : nullptr;
+        a32 = cur.take<float>(PT * SD_C * 4);
+        total = cur.off;
+    }
+};
+
+extern "C" int32_t gsr_sam_dec_num_weights(void) { return GSR_SAMD_W_COUNT; }
+
+extern "C" size_t gsr_sam_decode_workspace_bytes(int32_t g, int32_t P) {
+    if (g < 1 || g > SD_MAX_GRID || P < 1 || P > SD_MAX_POINTS) return 0;
+    return SdLayout(g, P, nullptr).total;
+}
+
+extern "C" int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, int32_t n_weights, const float* emb, const float* pe,
+                                  const float* points, int32_t P, int32_t image_size, void* ws, size_t ws_bytes, float* low_res,
+                                  float* iou, gsr_stream_t stream_) {
+    int rc;
+    if ((rc = sd_check_grid(g)) != GSR_OK || (rc = sd_check_points(P)) != GSR_OK) return rc;
+    if (image_size != 16 * g) { gsr_set_error("sam decoder: image_size %d is not 16 x grid %d", image_size, g); return GSR_E_INVALID; }
+    if (!weights_host || n_weights != GSR_SAMD_W_COUNT) {
+        gsr_set_error("sam decoder: the weight table is null or has %d entries (%d are needed)", n_weights, (int)GSR_SAMD_W_COUNT);
+        return GSR_E_INVALID;
+    }
+    for (int i = 0; i < n_weights; ++i)
+        if (!weights_host[i]) { gsr_set_error("sam decoder: weight %d of the table is null", i); return GSR_E_INVALID; }
+    if (!emb || !pe || !points || !low_res || !iou) { gsr_set_error("sam decoder: emb / pe / points / low_res / iou is null"); return GSR_E_INVALID; }
+    SdLayout lay(g, P, ws);
+    if (!ws || ws_bytes < lay.total) {
+        gsr_set_error("ws_bytes: sam decoder workspace too small (%zu < %zu bytes)", ws_bytes, lay.total);
+        return GSR_E_INVALID;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    const int T = g * g;
+    const int64_t R = (int64_t)P * SD_TOK, PT = (int64_t)P * T;
+    auto W = [&](int i) { return static_cast<const dn_half*>(weights_host[i]); };
+#define SD_RC(call) do { if ((rc = (call)) != GSR_OK) return rc; } while (0)
+    auto lin = [&](const dn_half* x, int wi, int bi, void* out, int64_t M, int K, int N, int epi) -> int {
+        return dn_linear(x, W(wi), bi < 0 ? nullptr : W(bi), nullptr, out, M, K, N, epi, 1, 0, 0, s);
+    };
+    auto addcast = [&](const float* a, const float* b, dn_half* y) -> int {
+        const int64_t n = R * SD_C;
+        hipLaunchKernelGGL(sd_addcast_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, b, n, y);
+        GSR_LAUNCH_CHECK();
+        return GSR_OK;
+    };
+    auto relu = [&](dn_half* x, int64_t n) -> int {
+        hipLaunchKernelGGL(sd_relu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n);
+        GSR_LAUNCH_CHECK();
+        return GSR_OK;
+    };
+    float *q = lay.qa, *q_alt = lay.qb;
+    auto norm = [&](int wi, float eps) -> int {
+        const int r = dn_norm(q, R, SD_C, SD_C, W(wi), W(wi + 1), eps, q_alt, 1, s);
+        float* tmp = q; q = q_alt; q_alt = tmp;
+        return r;
+    };
+
+    // SD_PROMPT and the tokens
+    SD_RC(sd_prompt(points, P, image_size, static_cast<const float*>(weights_host[GSR_SAMD_W_GAUSS]), W(GSR_SAMD_W_POINT1),
+                    W(GSR_SAMD_W_NOT_A_POINT), lay.sparse, s));
+    hipLaunchKernelGGL(sd_tokens_kernel, dim3((unsigned)P), dim3(256), 0, s, W(GSR_SAMD_W_IOU_TOKEN), W(GSR_SAMD_W_MASK_TOKENS), lay.sparse,
+                       lay.tok0, q);
+    GSR_LAUNCH_CHECK();
+
+    // SD_IMAGE
+    hipLaunchKernelGGL(sd_image_kernel, dim3((unsigned)((T * SD_C + 255) / 256)), dim3(256), 0, s, emb, pe, W(GSR_SAMD_W_NO_MASK), T, lay.E16,
+                       lay.PE16);
+    GSR_LAUNCH_CHECK();
+    const int l0 = GSR_SAMD_W_LAYER0, l1 = GSR_SAMD_W_LAYER0 + GSR_SAMD_W_PER_LAYER, fin = GSR_SAMD_W_FINAL;
+    SD_RC(lin(lay.PE16, l0 + GSR_SAMD_L_T2I + 2, l0 + GSR_SAMD_L_T2I + 3, lay.pe_proj[0], T, SD_C, SD_CI, DN_EPI_F32));
+    SD_RC(lin(lay.PE16, l0 + GSR_SAMD_L_I2T + 0, l0 + GSR_SAMD_L_I2T + 1, lay.pe_proj[1], T, SD_C, SD_CI, DN_EPI_F32));
+    SD_RC(lin(lay.PE16, l1 + GSR_SAMD_L_T2I + 2, l1 + GSR_SAMD_L_T2I + 3, lay.pe_proj[2], T, SD_C, SD_CI, DN_EPI_F32));
+    SD_RC(lin(lay.PE16, l1 + GSR_SAMD_L_I2T + 0, l1 + GSR_SAMD_L_I2T + 1, lay.pe_proj[3], T, SD_C, SD_CI, DN_EPI_F32));
+    SD_RC(lin(lay.PE16, fin + 2, fin + 3, lay.pe_proj[4], T, SD_C, SD_CI, DN_EPI_F32));
+    SD_RC(lin(lay.E16, l0 + GSR_SAMD_L_T2I + 2, -1, lay.kx0, T, SD_C, SD_CI, DN_EPI_BIAS));
+    SD_RC(lin(lay.E16, l0 + GSR_SAMD_L_T2I + 4, l0 + GSR_SAMD_L_T2I + 5, lay.v0, T, SD_C, SD_CI, DN_EPI_BIAS));
+    SD_RC(lin(lay.E16, l0 + GSR_SAMD_L_I2T + 0, -1, lay.qx0, T, SD_C, SD_CI, DN_EPI_BIAS));
+
+    // token -> image attention with the weights at `a`: queries += out_proj(attention)
+    auto t2i = [&](int a, int first, const float* kpe) -> int {
+        int r;
+        if ((r = addcast(q, lay.tok0, lay.h16)) != GSR_OK) return r;
+        if ((r = lin(lay.h16, a + 0, a + 1, lay.qf, R, SD_C, SD_CI, DN_EPI_F32)) != GSR_OK) return r;
+        if (!first) {
+            if ((r = lin(lay.x16, a + 2, -1, lay.b1, PT, SD_C, SD_CI, DN_EPI_BIAS)) != GSR_OK) return r;
+            if ((r = lin(lay.x16, a + 4, a + 5, lay.b2, PT, SD_C, SD_CI, DN_EPI_BIAS)) != GSR_OK) return r;
+        }
+        if ((r = sd_t2i(lay.qf, first ? lay.kx0 : lay.b1, kpe, first ? lay.v0 : lay.b2, P, T, first, 0.25f, lay.c16, s)) != GSR_OK) return r;
+        return lin(lay.c16, a + 6, a + 7, q, R, SD_CI, SD_C, DN_EPI_RESID1);
+    };
+
+    for (int l = 0; l < 2; ++l) {
+        const int b = GSR_SAMD_W_LAYER0 + GSR_SAMD_W_PER_LAYER * l;
+        // SD_TOKENS: self-attention
+        const int sa = b + GSR_SAMD_L_SELF;
+        if (l == 0) {
+            SD_RC(addcast(q, nullptr, lay.h16));
+            SD_RC(lin(lay.h16, sa + 4, sa + 5, lay.vf, R, SD_C, SD_C, DN_EPI_F32));
+        } else {
+            SD_RC(addcast(q, lay.tok0, lay.h16));
+            SD_RC(addcast(q, nullptr, lay.h16b));
+            SD_RC(lin(lay.h16b, sa + 4, sa + 5, lay.vf, R, SD_C, SD_C, DN_EPI_F32));
+        }
+        SD_RC(lin(lay.h16, sa + 0, sa + 1, lay.qf, R, SD_C, SD_C, DN_EPI_F32));
+        SD_RC(lin(lay.h16, sa + 2, sa + 3, lay.kf, R, SD_C, SD_C, DN_EPI_F32));
+        hipLaunchKernelGGL(sd_self_attn_kernel, dim3((unsigned)P), dim3(64), 0, s, lay.qf, lay.kf, lay.vf, lay.c16);
+        GSR_LAUNCH_CHECK();
+        SD_RC(lin(lay.c16, sa + 6, sa + 7, q, R, SD_C, SD_C, l == 0 ? DN_EPI_F32 : DN_EPI_RESID1));
+        SD_RC(norm(b + GSR_SAMD_L_NORM1, SD_EPS));
+        // SD_T2I
+        SD_RC(t2i(b + GSR_SAMD_L_T2I, l == 0, lay.pe_proj[2 * l]));
+        SD_RC(norm(b + GSR_SAMD_L_NORM2, SD_EPS));
+        // SD_TOKENS: MLP
+        SD_RC(addcast(q, nullptr, lay.h16));
+        SD_RC(lin(lay.h16, b + GSR_SAMD_L_MLP + 0, b + GSR_SAMD_L_MLP + 1, lay.m16, R, SD_C, SD_MLP, DN_EPI_BIAS));
+        SD_RC(relu(lay.m16, R * SD_MLP));
+        SD_RC(lin(lay.m16, b + GSR_SAMD_L_MLP + 2, b + GSR_SAMD_L_MLP + 3, q, R, SD_MLP, SD_C, DN_EPI_RESID1));
+        SD_RC(norm(b + GSR_SAMD_L_NORM3, SD_EPS));
+        // SD_I2T
+        const int it = b + GSR_SAMD_L_I2T;
+        SD_RC(addcast(q, lay.tok0, lay.h16));
+        SD_RC(addcast(q, nullptr, lay.h16b));
+        SD_RC(lin(lay.h16, it + 2, it + 3, lay.kf, R, SD_C, SD_CI, DN_EPI_F32));
+        SD_RC(lin(lay.h16b, it + 4, it + 5, lay.vf, R, SD_C, SD_CI, DN_EPI_F32));
+        if (l > 0) SD_RC(lin(lay.x16, it + 0, -1, lay.b1, PT, SD_C, SD_CI, DN_EPI_BIAS));
+        SD_RC(sd_i2t(l == 0 ? lay.qx0 : lay.b1, lay.pe_proj[2 * l + 1], lay.kf, lay.vf, l == 0 ? lay.E16 : lay.x16, P, T, l == 0, W(it + 6),
+                     W(it + 7), W(b + GSR_SAMD_L_NORM4), W(b + GSR_SAMD_L_NORM4 + 1), lay.b2, lay.a32, lay.x16, s));
+    }
+    SD_RC(t2i(fin, 0, lay.pe_proj[4]));
+    SD_RC(norm(fin + 8, SD_EPS_FINAL));
+
+    // SD_HEADS
+    hipLaunchKernelGGL(sd_heads_gather_kernel, dim3((unsigned)P), dim3(256), 0, s, q, P, lay.heads16);
+    GSR_LAUNCH_CHECK();
+    for (int k = 0; k < 4; ++k) {
+        const int a = k == 0 ? GSR_SAMD_W_IOU : GSR_SAMD_W_HYPER + 6 * (k - 1);
+        SD_RC(lin(lay.heads16 + (int64_t)k * P * SD_C, a + 0, a + 1, lay.t16a, P, SD_C, SD_C, DN_EPI_BIAS));
+        SD_RC(relu(lay.t16a, (int64_t)P * SD_C));
+        SD_RC(lin(lay.t16a, a + 2, a + 3, lay.t16b, P, SD_C, SD_C, DN_EPI_BIAS));
+        SD_RC(relu(lay.t16b, (int64_t)P * SD_C));
+        if (k == 0)     // rows 1..3 of the IoU head's last layer [4,256]: columns 1..3 of its output
+            SD_RC(dn_linear(lay.t16b, W(a + 4) + SD_C, W(a + 5) + 1, nullptr, iou, P, SD_C, 3, DN_EPI_F32, 1, 0, 0, s));
+        else
+            SD_RC(lin(lay.t16b, a + 4, a + 5, lay.hyper + (int64_t)(k - 1) * P * 32, P, SD_C, 32, DN_EPI_F32));
+    }
+    // SD_UP
+    const int up = GSR_SAMD_W_UP;
+    return sd_upscale(lay.x16, g, P, W(up), W(up + 1), W(up + 2), W(up + 3), W(up + 4), W(up + 5), lay.hyper, lay.a32, lay.b1, low_res, s);
+#undef SD_RC
+}

@@ -2,7 +2,8 @@
 65-92: SamAutomaticMaskGenerator(vit_h, points_per_side=32, pred_iou_thresh=0.86, stability_score_thresh=0.92)) with the
 image encoder and the mask selection computed by the kernels of csrc/sam.hip (include/gsr.h: SV_EMBED, SV_ATTN, SV_NECK,
 SM_SCORE, SM_NMS, SM_EMIT).  The prompt encoder and the mask decoder are transformers' own torch modules, run on the device
-in fp32 as they are.
+in fp32 as they are (decoder="torch", the default), or the kernels of csrc/sam_decoder.hip (decoder="hip"; include/gsr.h:
+SD_PROMPT, SD_IMAGE, SD_TOKENS, SD_T2I, SD_I2T, SD_UP, SD_HEADS: fp16 operands, fp32 accumulation and token stream).
 
     from gaussmart_amd.sam import SamMaskGenerator, load_sam_weights, save_segments_boxes
     gen = SamMaskGenerator(load_sam_weights("/models/sam_vit_h_4b8939.pth"))     # or a directory, see load_sam_weights
@@ -17,7 +18,7 @@ What differs from the reference, on purpose:
   * DEVIATION: the first resize (long side <= 1024) is cv2.INTER_LINEAR in the reference and PIL's bilinear here.
   * one full-image crop only: no crop layers, no min_mask_region_area, no SAM2.  The crop-edge filter of the reference never
     fires for the single full-image crop and is left out.
-`sam_host`, `select_host` and `nms_host` are the torch twins (any device): they back `host=True` and the tests.
+`sam_host`, `decode_host`, `select_host` and `nms_host` are the torch twins (any device): they back `host=True` and the tests.
 """
 import ctypes as C
 import json
@@ -50,6 +51,29 @@ ENC_NECK = ("neck.conv1.weight", "neck.layer_norm1.weight", "neck.layer_norm1.bi
             "neck.layer_norm2.weight", "neck.layer_norm2.bias")
 assert (len(ENC_HEAD), len(ENC_LAYER), len(ENC_NECK)) == (_lib.GSR_SAM_W_LAYER0, _lib.GSR_SAM_W_PER_LAYER, _lib.GSR_SAM_W_NECK)
 VISION = "vision_encoder."
+
+# the weight table of gsr_sam_decode, in the order of include/gsr.h (names of SamModel.state_dict())
+_ATTN = tuple(f"{p}_proj.{x}" for p in ("q", "k", "v", "out") for x in ("weight", "bias"))
+_NORM = ("weight", "bias")
+DEC_HEAD = ("prompt_encoder.shared_embedding.positional_embedding", "prompt_encoder.point_embed.1.weight",
+            "prompt_encoder.not_a_point_embed.weight", "prompt_encoder.no_mask_embed.weight", "mask_decoder.iou_token.weight",
+            "mask_decoder.mask_tokens.weight")
+DEC_LAYER = (tuple(f"self_attn.{k}" for k in _ATTN) + tuple(f"layer_norm1.{k}" for k in _NORM)
+             + tuple(f"cross_attn_token_to_image.{k}" for k in _ATTN) + tuple(f"layer_norm2.{k}" for k in _NORM)
+             + ("mlp.lin1.weight", "mlp.lin1.bias", "mlp.lin2.weight", "mlp.lin2.bias") + tuple(f"layer_norm3.{k}" for k in _NORM)
+             + tuple(f"layer_norm4.{k}" for k in _NORM) + tuple(f"cross_attn_image_to_token.{k}" for k in _ATTN))
+DEC_FINAL = tuple(f"final_attn_token_to_image.{k}" for k in _ATTN) + tuple(f"layer_norm_final_attn.{k}" for k in _NORM)
+DEC_UP = ("upscale_conv1.weight", "upscale_conv1.bias", "upscale_layer_norm.weight", "upscale_layer_norm.bias", "upscale_conv2.weight",
+          "upscale_conv2.bias")
+_MLP3 = tuple(f"{p}.{x}" for p in ("proj_in", "layers.0", "proj_out") for x in ("weight", "bias"))
+DEC_HYPER = tuple(f"output_hypernetworks_mlps.{m}.{k}" for m in (1, 2, 3) for k in _MLP3)
+DEC_IOU = tuple(f"iou_prediction_head.{k}" for k in _MLP3)
+DEC_LAYERS = 2
+assert (len(DEC_HEAD), len(DEC_LAYER)) == (_lib.GSR_SAMD_W_LAYER0, _lib.GSR_SAMD_W_PER_LAYER)
+assert _lib.GSR_SAMD_W_FINAL == len(DEC_HEAD) + DEC_LAYERS * len(DEC_LAYER) and _lib.GSR_SAMD_W_UP == _lib.GSR_SAMD_W_FINAL + len(DEC_FINAL)
+assert _lib.GSR_SAMD_W_HYPER == _lib.GSR_SAMD_W_UP + len(DEC_UP) and _lib.GSR_SAMD_W_IOU == _lib.GSR_SAMD_W_HYPER + len(DEC_HYPER)
+assert _lib.GSR_SAMD_W_COUNT == _lib.GSR_SAMD_W_IOU + len(DEC_IOU)
+DECODER_WORKSPACE_BUDGET = 2 << 30       # bytes of gsr_sam_decode workspace per call of decoder="hip": the points are chunked to fit
 TIED = ("prompt_encoder.shared_embedding.positional_embedding", "shared_image_embedding.positional_embedding")
 
 
@@ -166,6 +190,30 @@ class SamWeights:
         for l in range(self.config.num_hidden_layers):
             names += [f"{VISION}layers.{l}.{k}" for k in ENC_LAYER]
         return [self.tensors[k] for k in names + [VISION + k for k in ENC_NECK]]
+
+    def decoder_table(self):
+        """The tensors of gsr_sam_decode's weight table, in its order, on the tensors' device: fp16 copies, except the
+        positional matrix (fp32, as it is).  The two transposed convolutions [ci,co,2,2] are re-laid as [(dy 2 + dx) co_n + co]
+        [ci] and their biases repeated per tap, which is what one DN_LINEAR over the input channels takes."""
+        if not self.decoder:
+            raise ValueError("sam: these weights hold no prompt encoder and mask decoder")
+        t, md = self.tensors, "mask_decoder."
+        names = list(DEC_HEAD)
+        for l in range(DEC_LAYERS):
+            names += [f"{md}transformer.layers.{l}.{k}" for k in DEC_LAYER]
+        names += [f"{md}transformer.{k}" for k in DEC_FINAL] + [md + k for k in DEC_UP + DEC_HYPER + DEC_IOU]
+        out = []
+        for k in names:
+            v = t[k]
+            if k == DEC_HEAD[0]:
+                out.append(v.to(torch.float32).contiguous())
+                continue
+            if k.startswith(md + "upscale_conv") and k.endswith(".weight"):
+                v = v.permute(2, 3, 1, 0).reshape(4 * v.shape[1], v.shape[0])
+            elif k.startswith(md + "upscale_conv"):
+                v = v.repeat(4)
+            out.append(v.to(torch.float16).contiguous())
+        return out
 
     def sub(self, prefix):
         """The tensors under `prefix`, with it removed (a sub-module's state dict), in fp32."""
@@ -353,6 +401,44 @@ def sam_host(weights, pixel_values, dtype=torch.float64, device=None, model=None
     return model(x).last_hidden_state[0]
 
 
+def host_decoder(weights, dtype=torch.float32, device="cpu"):
+    """(SamPromptEncoder, SamMaskDecoder, wide [1,256,g,g]) holding these tensors, in `dtype` on `device`, in eval mode; wide
+    is SamModel.get_image_wide_positional_embeddings()."""
+    from transformers.models.sam.modeling_sam import SamPromptEncoder, SamMaskDecoder, SamPositionalEmbedding
+    hf = weights.config.to_hf()
+    prompt, decoder, shared = SamPromptEncoder(hf), SamMaskDecoder(hf.mask_decoder_config), SamPositionalEmbedding(hf.vision_config)
+    prompt.load_state_dict(weights.sub("prompt_encoder."), strict=True)
+    decoder.load_state_dict(weights.sub("mask_decoder."), strict=True)
+    shared.load_state_dict(weights.sub("shared_image_embedding."), strict=True)
+    prompt, decoder, shared = (m.to(device=device, dtype=dtype).eval() for m in (prompt, decoder, shared))
+    g = weights.config.grid
+    c = (torch.arange(g, device=device, dtype=dtype) + 0.5) / g      # get_image_wide_positional_embeddings
+    with torch.no_grad():
+        wide = shared(torch.stack([c[None, :].expand(g, g), c[:, None].expand(g, g)], -1)).permute(2, 0, 1)[None]
+    return prompt, decoder, wide
+
+
+@torch.no_grad()
+def decode_host(weights, emb, wide, points, dtype=torch.float32, device=None, modules=None, points_per_batch=64):
+    """transformers' prompt encoder and mask decoder as they are: emb [1,256,g,g], points [P,2] (x, y) in the input frame, one
+    foreground point per prompt, multimask output -> (low_res [P,3,4g,4g], iou [P,3]) in `dtype`.  wide=None: computed here;
+    modules: what host_decoder returned (built here otherwise)."""
+    device = emb.device if device is None else torch.device(device)
+    prompt, decoder, own = host_decoder(weights, dtype, device) if modules is None else modules
+    wide = own if wide is None else wide.to(device=device, dtype=dtype)
+    emb = emb.to(device=device, dtype=dtype)
+    low, iou = [], []
+    for part in points.to(device=device, dtype=torch.float64 if dtype == torch.float64 else torch.float32).split(points_per_batch):
+        pts = part[None, :, None, :]
+        labels = torch.ones(1, part.shape[0], 1, dtype=torch.int64, device=device)
+        sparse, dense = prompt(pts, labels, None, None)
+        m, q = decoder(image_embeddings=emb, image_positional_embeddings=wide, sparse_prompt_embeddings=sparse.to(dtype),
+                       dense_prompt_embeddings=dense, multimask_output=True)
+        low.append(m[0])
+        iou.append(q[0])
+    return torch.cat(low).contiguous(), torch.cat(iou).contiguous()
+
+
 # ---------------------------------------------------------------- the encoder
 class SamImageEncoder:
     """encode(pixel_values f32 [3,S,S] on the device) -> f32 [C,g,g], on the kernels."""
@@ -505,32 +591,46 @@ class SamMaskGenerator:
     SamVisionEncoder in fp32 and the selection through select_host, on the same device."""
 
     def __init__(self, weights, points_per_side=32, points_per_batch=64, pred_iou_thresh=0.86, stability_score_thresh=0.92,
-                 stability_score_offset=1.0, box_nms_thresh=0.7, host=False, device="cuda"):
+                 stability_score_offset=1.0, box_nms_thresh=0.7, host=False, device="cuda", decoder="torch"):
         if not weights.decoder:
             raise ValueError("sam: the mask generator needs weights with the prompt encoder and the mask decoder")
+        if decoder not in ("torch", "hip"):
+            raise ValueError(f"sam: decoder {decoder!r} is not 'torch' or 'hip'")
+        if host and decoder == "hip":
+            raise ValueError("sam: host=True runs the torch modules only; decoder='hip' cannot be combined with it")
         self.weights, self.config, self.device, self.host = weights, weights.config, torch.device(device), bool(host)
+        self.decoder = decoder
         self.points_per_side, self.points_per_batch = int(points_per_side), int(points_per_batch)
         self.pred_iou_thresh, self.stability_score_thresh = float(pred_iou_thresh), float(stability_score_thresh)
         self.stability_score_offset, self.box_nms_thresh = float(stability_score_offset), float(box_nms_thresh)
         self.encoder = None if host else SamImageEncoder(weights)
-        self._host_encoder = self._modules = None
+        self._host_encoder = self._modules = self._hip = None
         self.last_ms = {}
 
     # -- the torch modules of the decoder
     def _decoder(self):
         if self._modules is None:
-            from transformers.models.sam.modeling_sam import SamPromptEncoder, SamMaskDecoder, SamPositionalEmbedding
-            hf = self.config.to_hf()
-            prompt, decoder, shared = SamPromptEncoder(hf), SamMaskDecoder(hf.mask_decoder_config), SamPositionalEmbedding(hf.vision_config)
-            prompt.load_state_dict(self.weights.sub("prompt_encoder."), strict=True)
-            decoder.load_state_dict(self.weights.sub("mask_decoder."), strict=True)
-            shared.load_state_dict(self.weights.sub("shared_image_embedding."), strict=True)
-            prompt, decoder, shared = (m.to(self.device).eval() for m in (prompt, decoder, shared))
-            g = self.config.grid
-            c = (torch.arange(g, device=self.device, dtype=torch.float32) + 0.5) / g      # get_image_wide_positional_embeddings
-            wide = shared(torch.stack([c[None, :].expand(g, g), c[:, None].expand(g, g)], -1)).permute(2, 0, 1)[None]
-            self._modules = (prompt, decoder, wide)
+            self._modules = host_decoder(self.weights, torch.float32, self.device)
         return self._modules
+
+    # -- the weight table of gsr_sam_decode and the positional embedding of the grid
+    def _decoder_hip(self):
+        if self._hip is None:
+            if self.config.grid > 64:
+                raise NotImplementedError(f"sam: decoder='hip' is built for grids up to 64 (image_size <= 1024), not {self.config.grid}")
+            w = SamWeights.__new__(SamWeights)
+            w.config, w.decoder = self.config, True
+            w.tensors = {k: t.to(self.device) for k, t in self.weights.tensors.items() if not k.startswith(VISION)}
+            tensors = w.decoder_table()
+            table = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+            g = self.config.grid
+            G = tensors[0].to(torch.float32)
+            c = (torch.arange(g, device=self.device, dtype=torch.float32) + 0.5) / g
+            xy = 2 * torch.stack([c[None, :].expand(g, g), c[:, None].expand(g, g)], -1) - 1
+            arg = 2 * np.pi * (xy @ G)
+            wide = torch.cat([torch.sin(arg), torch.cos(arg)], -1).permute(2, 0, 1).contiguous()
+            self._hip = dict(tensors=tensors, table=table, n=len(tensors), wide=wide)
+        return self._hip
 
     @torch.no_grad()
     def embed(self, image):
@@ -547,18 +647,39 @@ class SamMaskGenerator:
 
     @torch.no_grad()
     def decode(self, emb, points):
-        """emb [1,C,g,g], points f32 [P,2] (x, y) in the input frame -> (low_res f32 [P,3,L,L], iou f32 [P,3])."""
-        prompt, decoder, wide = self._decoder()
-        low, iou = [], []
-        for part in points.to(self.device).split(self.points_per_batch):
-            pts = part[None, :, None, :]
-            labels = torch.ones(1, part.shape[0], 1, dtype=torch.int64, device=self.device)
-            sparse, dense = prompt(pts, labels, None, None)
-            m, q = decoder(image_embeddings=emb, image_positional_embeddings=wide, sparse_prompt_embeddings=sparse,
-                           dense_prompt_embeddings=dense, multimask_output=True)
-            low.append(m[0])
-            iou.append(q[0])
-        return torch.cat(low).to(torch.float32).contiguous(), torch.cat(iou).to(torch.float32).contiguous()
+        """emb [1,C,g,g], points f32 [P,2] (x, y) in the input frame -> (low_res f32 [P,3,L,L], iou f32 [P,3]).  decoder="torch":
+        transformers' modules in fp32, points_per_batch at a time; "hip": gsr_sam_decode, as many points per call as
+        DECODER_WORKSPACE_BUDGET bytes of workspace hold."""
+        if self.decoder == "hip":
+            return self._decode_hip(emb, points)
+        low, iou = decode_host(self.weights, emb, self._decoder()[2], points, torch.float32, self.device, self._decoder(),
+                               self.points_per_batch)
+        return low.to(torch.float32).contiguous(), iou.to(torch.float32).contiguous()
+
+    def _decode_hip(self, emb, points):
+        if not emb.is_cuda:
+            raise _lib.GsrError("sam: decoder='hip' needs the embedding on the device (no CPU path; see decode_host)")
+        d, L, g, S = self._decoder_hip(), _lib.lib(), self.config.grid, self.config.image_size
+        dev = emb.device
+        emb = emb.reshape(DECODER_CHANNELS, g, g).to(torch.float32).contiguous()
+        pts = points.to(device=dev, dtype=torch.float32).reshape(-1, 2).contiguous()
+        P = pts.shape[0]
+        low = torch.empty(P, 3, 4 * g, 4 * g, dtype=torch.float32, device=dev)
+        iou = torch.empty(P, 3, dtype=torch.float32, device=dev)
+        if P == 0:
+            return low, iou
+        one = L.gsr_sam_decode_workspace_bytes(g, 1)
+        per = max(1, L.gsr_sam_decode_workspace_bytes(g, 2) - one)
+        chunk = int(min(P, 65535, max(1, 1 + (DECODER_WORKSPACE_BUDGET - one) // per)))
+        while chunk > 1 and L.gsr_sam_decode_workspace_bytes(g, chunk) > DECODER_WORKSPACE_BUDGET:
+            chunk -= 1
+        nbytes = L.gsr_sam_decode_workspace_bytes(g, chunk)
+        ws = workspace(nbytes, dev)
+        for k in range(0, P, chunk):
+            n = min(chunk, P - k)
+            _lib.check(L.gsr_sam_decode(g, d["table"], d["n"], ptr(emb), ptr(d["wide"]), ptr(pts[k:k + n]), n, S, ptr(ws), nbytes,
+                                        ptr(low[k:k + n]), ptr(iou[k:k + n]), stream(dev)))
+        return low, iou
 
     @torch.no_grad()
     def select(self, low_res, iou, input_size, mask_size):

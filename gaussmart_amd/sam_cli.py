@@ -1,13 +1,16 @@
 """Step 2 of the reference's identification/main.py, the SAM masks of the chosen views, on the device.
 
     python -m gaussmart_amd.sam_cli -s SCAN -o OUT --views i j k ... --sam_checkpoint FILE_OR_DIR [--model_type vit_h|vit_l|vit_b] [--host]
+        [--decoder torch|hip]
         [--points_per_side 32] [--pred_iou_thresh 0.86] [--stability_score_thresh 0.92]      (the reference's values)
 
 View i is the i-th file of sorted(listdir(SCAN/images)).  Writes OUT/segments/masks/segments_NNN.npz (keys masks, boxes,
 areas; the k-th file belongs to the k-th --views entry) and copies the images to OUT/segments/images/; prints one JSON line
 per view.  `python -m gaussmart_amd.segment_cli --masks OUT/segments/masks --views ...` reads them.  --sam_checkpoint is a
 LOCAL .pth under segment_anything's names or a LOCAL directory under transformers' (gaussmart_amd.sam.load_sam_weights);
-nothing is downloaded.  --host runs transformers' encoder in fp32 and the torch selection on the same device.
+nothing is downloaded.  --host runs transformers' encoder in fp32 and the torch selection on the same device.  --decoder hip
+runs the prompt encoder and the mask decoder on the kernels of csrc/sam_decoder.hip (fp16 operands); torch, the default, runs
+transformers' modules in fp32.
 Not built: SAM2 (--sam2), crop layers, min_mask_region_area, and the camera clustering that picks the views (step 1).
 """
 import argparse
@@ -30,6 +33,7 @@ def main(argv=None):
     ap.add_argument("--model_type", choices=("vit_h", "vit_l", "vit_b"), default=None,
                     help="checked against the checkpoint's own shape when given")
     ap.add_argument("--host", action="store_true", help="transformers' encoder in fp32 and the torch selection")
+    ap.add_argument("--decoder", choices=("torch", "hip"), default="torch", help="the prompt encoder and mask decoder: transformers' or the kernels")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--points_per_side", type=int, default=32)
     ap.add_argument("--pred_iou_thresh", type=float, default=0.86)
@@ -54,7 +58,7 @@ def main(argv=None):
                   file=sys.stderr)
             raise SystemExit(2)
     gen = S.SamMaskGenerator(weights, points_per_side=args.points_per_side, pred_iou_thresh=args.pred_iou_thresh,
-                             stability_score_thresh=args.stability_score_thresh, host=args.host, device=args.device)
+                             stability_score_thresh=args.stability_score_thresh, host=args.host, device=args.device, decoder=args.decoder)
     mask_dir = os.path.join(args.output_path, "segments", "masks")
     copy_dir = os.path.join(args.output_path, "segments", "images")
     os.makedirs(mask_dir, exist_ok=True)
@@ -70,7 +74,7 @@ def main(argv=None):
             e = S.preprocess(image, weights.config.image_size)[2]
             np.savez(out, masks=np.zeros((0, *e), bool), boxes=np.zeros((0, 4), np.int64), areas=np.zeros((0,), np.int64))
         shutil.copy(path, os.path.join(copy_dir, files[i]))
-        print(json.dumps({"view": i, "image": files[i], "masks": len(masks), "host": bool(args.host),
+        print(json.dumps({"view": i, "image": files[i], "masks": len(masks), "host": bool(args.host), "decoder": args.decoder,
                           **{f"{name}_ms": round(ms, 3) for name, ms in gen.last_ms.items()}}))
     return 0
 

@@ -48,7 +48,9 @@ extern "C" {
                                 15: LPIPS (gsr_lpips_*);
                                 16: frame kernels of the trajectory and viewer pictures (gsr_frame_*);
                                 17: DINOv3 ViT encoder and its cosine term (GsrDinoConfig, gsr_dino_*);
-                                18: SAM image encoder and mask selection (GsrSamConfig, gsr_sam_*) */
+                                18: SAM image encoder and mask selection (GsrSamConfig, gsr_sam_*); still 18 with SAM's
+                                    prompt encoder and mask decoder (gsr_sam_dec_*, gsr_sam_decode): additions only, no
+                                    existing struct or signature changed */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -1194,7 +1196,7 @@ int32_t gsr_dino_cosine(const float* a, const float* b, int32_t n, float lambda1
  * transformers' SamVisionEncoder (models/sam/modeling_sam.py; segment_anything's ImageEncoderViT), which the reference's
  * SAMSegmentation runs in fp32 inside SamAutomaticMaskGenerator (identification/sam.py:41-46,65-92), and the selection of that
  * generator's candidate masks, as inference kernels (sam.hip; Python: gaussmart_amd/sam.py).  The prompt encoder and the mask
- * decoder are not here.  Patch 16 x 16, g = image_size / 16 tokens per side (g <= 256), T = g g; head_dim 64 or 80, hidden =
+ * decoder have a part of their own below (SD_*).  Patch 16 x 16, g = image_size / 16 tokens per side (g <= 256), T = g g; head_dim 64 or 80, hidden =
  * heads head_dim; hidden, mlp_dim and output_channels multiples of 64; layers >= 1; per layer a window size w (0: global
  * attention, else w >= 1); ln_eps 1e-6; one image per call.  A layer's two relative-position tables have EXACTLY 2 s - 1
  * rows, s = g for a global layer and s = w otherwise (then the twin's F.interpolate of the table is the identity); any
@@ -1298,6 +1300,96 @@ int32_t gsr_sam_mask_emit(const float* logits, int32_t n, int32_t L, int32_t ih,
 size_t gsr_sam_nms_workspace_bytes(int32_t n);
 int32_t gsr_sam_nms(const float* boxes, const float* scores, const uint8_t* keep_in, int32_t n, float theta, void* ws,
                     size_t ws_bytes, int32_t* kept, int32_t* count, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- SAM: the prompt encoder and the mask decoder
+ * transformers' SamPromptEncoder and SamMaskDecoder in the stock configuration (SamPromptEncoderConfig(), SamMaskDecoderConfig()):
+ * hidden 256, two two-way layers, 8 heads, self-attention width 256 (head_dim 32), cross-attention width 128 (head_dim 16),
+ * MLP 2048 with ReLU, 4 mask tokens and 1 IoU token, IoU head 256-256-4, up-scaling 256 -> 64 -> 32 by two 2x2 stride-2
+ * transposed convolutions (sam_decoder.hip; Python: gaussmart_amd/sam.py).  g = image_size / 16 with 1 <= g <= 64, T = g g (any
+ * value); P points, 1 <= P <= 65535.  One prompt is ONE foreground point (label 1) plus the padding token: 7 tokens per point
+ * (iou, mask 0..3, point, not-a-point).  multimask output: masks 1..3 and IoU columns 1..3; mask 0's hypernetwork is not
+ * computed.  Boxes, mask prompts, several points per prompt and SAM2 are not built.
+ * Precision: every weight is fp16 except the positional matrix; every product with a weight is DN_LINEAR (fp16 operands, one
+ * k-ascending fp32 chain per element, rows independent); LayerNorm statistics (DN_NORM's formula), softmax and the token stream
+ * are fp32; the per-point image stream is STORED AS fp16 between stages.  No split-K, no float atomics: a point's bits do not
+ * depend on the other points of the call.  LayerNorm eps is 1e-6 except layer_norm_final_attn's 1e-5.  Rules:
+ *   SD_PROMPT  point (x, y) f32 in the input frame, S = image_size, G = shared_embedding.positional_embedding f32 [2,128] (NOT
+ *              rounded to fp16): a = 2 ((c + 0.5) / S) - 1 per coordinate, arg_j = (ax G[0][j] + ay G[1][j]) * fp32(2 pi), every
+ *              operation one fp32 rounding, no contraction; token 0 = [sinf(arg), cosf(arg)] + fp32(point_embed.1) (precise
+ *              sinf / cosf, not the hardware approximations), token 1 = fp32(not_a_point_embed).  Output f32 [P,2,256].
+ *   SD_IMAGE   once per call: src0[t][c] = fp16(emb[c][t] + fp32(no_mask_embed[c])), pe16[t][c] = fp16(pe[c][t]); for layer 0
+ *              kx0 = fp16(k_proj(src0) WITHOUT bias), v0 = fp16(v_proj(src0) + bias) of the token->image attention and qx0 =
+ *              fp16(q_proj(src0) without bias) of the image->token attention; for each of the five cross attentions (t2i 0,
+ *              i2t 0, t2i 1, i2t 1, final) the positional term proj(pe16) + bias as f32 [T,128] (k_proj for t2i / final,
+ *              q_proj for i2t): proj(keys + pe) = proj(keys) + proj(pe).
+ *   SD_TOKENS  tokens f32 [P,7,256], qpe = their initial value.  An operand of a product is fp16(tokens) or fp16(tokens + qpe)
+ *              (one fp32 addition); q, k, v of the token side are STORED AS fp32.  Self-attention: 8 heads of 32, score
+ *              (sum_d q_d k_d, d ascending, fmaf) * fp32(32^-1/2), p = expf(s - max), out = (sum_j p_j v_j, j ascending, fmaf)
+ *              / (sum_j p_j), ROUNDED TO fp16; layer 0: q = k = v = tokens and tokens = out_proj(out) (no residual); layer 1:
+ *              q = k = tokens + qpe, v = tokens, tokens += out_proj(out) (one fp32 addition after the bias's).  MLP: lin1
+ *              ROUNDED TO fp16 then ReLU, tokens += lin2.  layer_norm1..3 and layer_norm_final_attn: DN_NORM in fp32.
+ *   SD_T2I     q = q_proj(fp16(tokens + qpe)) f32 [P,7,128]; key of image token t: fp32(kx[t]) + kpe[t] (kx fp16 [T,128] is
+ *              kx0 for layer 0, else fp16(k_proj(stream) without bias) per point; kpe of SD_IMAGE); v fp16 [T,128] = v0 or
+ *              fp16(v_proj(stream) + bias).  Per (point, head): score = (sum_d q_d k_d, d ascending, fmaf) * 1/4.  A thread
+ *              takes keys t, t + 256, ... in order; maximum per query over all keys; p = expf(s - max); l and p v are added
+ *              per thread in key order (fmaf), the 64 lanes by a xor butterfly (32, 16, .., 1), the four waves in order;
+ *              out = acc / l ROUNDED TO fp16 [P,7,128]; tokens += out_proj(out).  No [T,7] score array is stored.
+ *   SD_I2T     per image token and head: q = fp32(qx[t]) + qpe[t] (qx fp16 = qx0 for layer 0, else fp16(q_proj(stream) without
+ *              bias)); k = k_proj(fp16(tokens + qpe)), v = v_proj(fp16(tokens)), f32 [P,7,128]; score = (sum_d q_d k_jd) * 1/4,
+ *              p_j = expf(s_j - max), ctx = (sum_j p_j v_j) / (sum_j p_j), j ascending, ROUNDED TO fp16 [P,T,128]; a =
+ *              out_proj(ctx) + bias as fp32; stream = fp16(layer_norm4(fp32(stream) + a)), the stream of layer 0 being src0.
+ *   SD_UP      u = conv1(stream) + bias as fp32 [P T,4,64] (one DN_LINEAR over K = 256 with the weight laid out [(dy 2 + dx) 64
+ *              + co][ci]); per (token, tap) the channel LayerNorm over 64 (eps 1e-6), exact GELU, ROUNDED TO fp16; conv2
+ *              likewise over K = 64 to [.,(dy 2 + dx) 32 + co] with exact GELU in the epilogue, ROUNDED TO fp16; low_res[p][m]
+ *              [4 y + 2 dy1 + dy2][4 x + 2 dx1 + dx2] = sum_c hyper[m][p][c] fp32(c2[c]), c ascending, fmaf, for m = masks
+ *              1..3.  The [P,32,4g,4g] up-scaled embedding is stored as fp16 once; low_res is f32 [P,3,4g,4g].
+ *   SD_HEADS   after layer_norm_final_attn: hyper[m] = MLP_m(fp16(mask token m)) for m = 1..3 and iou = columns 1..3 of the
+ *              IoU head on fp16(iou token); hidden layers ROUNDED TO fp16 then ReLU, the last layer stored as fp32.
+ * Weight table of gsr_sam_decode: a HOST array of gsr_sam_dec_num_weights() (= GSR_SAMD_W_COUNT) DEVICE pointers, none NULL,
+ * fp16 unless stated (names: SamModel.state_dict()):
+ *   GSR_SAMD_W_GAUSS prompt_encoder.shared_embedding.positional_embedding F32 [2,128]; _POINT1 prompt_encoder.point_embed.1.weight;
+ *   _NOT_A_POINT prompt_encoder.not_a_point_embed.weight; _NO_MASK prompt_encoder.no_mask_embed.weight; _IOU_TOKEN
+ *   mask_decoder.iou_token.weight; _MASK_TOKENS mask_decoder.mask_tokens.weight [4,256];
+ *   per layer l at GSR_SAMD_W_LAYER0 + GSR_SAMD_W_PER_LAYER l (mask_decoder.transformer.layers.l.): GSR_SAMD_L_SELF self_attn.
+ *   {q,k,v,out}_proj.{weight,bias} (8 entries in that order), _NORM1 layer_norm1.{weight,bias}, _T2I cross_attn_token_to_image
+ *   (8), _NORM2, _MLP mlp.lin1.{weight,bias}, mlp.lin2.{weight,bias}, _NORM3, _NORM4, _I2T cross_attn_image_to_token (8);
+ *   GSR_SAMD_W_FINAL mask_decoder.transformer.final_attn_token_to_image (8) and layer_norm_final_attn.{weight,bias};
+ *   GSR_SAMD_W_UP upscale_conv1.weight re-laid as [(dy 2 + dx) 64 + co][256], its bias repeated 4 times [256],
+ *   upscale_layer_norm.{weight,bias}, upscale_conv2.weight as [(dy 2 + dx) 32 + co][64], its bias repeated 4 times [128];
+ *   GSR_SAMD_W_HYPER output_hypernetworks_mlps.m.{proj_in,layers.0,proj_out}.{weight,bias} for m = 1, 2, 3 (18);
+ *   GSR_SAMD_W_IOU iou_prediction_head.{proj_in,layers.0,proj_out}.{weight,bias} (6; proj_out whole, [4,256] and [4]).
+ * Entry points (caller's stream, caller's buffers, nothing synchronises; anything refused is GSR_E_INVALID before a launch):
+ *   gsr_sam_dec_prompt  SD_PROMPT.
+ *   gsr_sam_dec_t2i     SD_T2I's attention: q f32 [P,7,128]; kx, v fp16 [T,128] (shared != 0) or [P,T,128]; kpe f32 [T,128] or
+ *                       NULL (no positional term); out fp16 [P,7,128].
+ *   gsr_sam_dec_i2t     SD_I2T whole: qx fp16 [T,128] / [P,T,128] and x fp16 [T,256] / [P,T,256] by `shared`; out_w [256,128],
+ *                       out_b, ln_w, ln_b fp16; x_out fp16 [P,T,256] (may be x when shared == 0).
+ *   gsr_sam_dec_upscale SD_UP: x fp16 [P,T,256], the six GSR_SAMD_W_UP arrays, hyper f32 [3,P,32]; low_res f32 [P,3,4g,4g].
+ *   gsr_sam_decode      everything: emb, pe f32 [256,g,g]; points f32 [P,2]; image_size = 16 g; low_res f32 [P,3,4g,4g]; iou f32
+ *                       [P,3].  ws: gsr_sam_decode_workspace_bytes(g, P), about 2 KiB per point and image token. */
+enum { GSR_SAMD_W_GAUSS = 0, GSR_SAMD_W_POINT1, GSR_SAMD_W_NOT_A_POINT, GSR_SAMD_W_NO_MASK, GSR_SAMD_W_IOU_TOKEN,
+       GSR_SAMD_W_MASK_TOKENS, GSR_SAMD_W_LAYER0 };
+enum { GSR_SAMD_L_SELF = 0, GSR_SAMD_L_NORM1 = 8, GSR_SAMD_L_T2I = 10, GSR_SAMD_L_NORM2 = 18, GSR_SAMD_L_MLP = 20, GSR_SAMD_L_NORM3 = 24,
+       GSR_SAMD_L_NORM4 = 26, GSR_SAMD_L_I2T = 28, GSR_SAMD_W_PER_LAYER = 36 };
+enum { GSR_SAMD_W_FINAL = GSR_SAMD_W_LAYER0 + 2 * GSR_SAMD_W_PER_LAYER, GSR_SAMD_W_UP = GSR_SAMD_W_FINAL + 10,
+       GSR_SAMD_W_HYPER = GSR_SAMD_W_UP + 6, GSR_SAMD_W_IOU = GSR_SAMD_W_HYPER + 18, GSR_SAMD_W_COUNT = GSR_SAMD_W_IOU + 6 };
+int32_t gsr_sam_dec_prompt(const float* points, int32_t P, int32_t image_size, const float* gauss, const void* point1,
+                           const void* not_a_point, float* out, gsr_stream_t stream);
+int32_t gsr_sam_dec_t2i(const float* q, const void* kx, const float* kpe, const void* v, int32_t P, int32_t T, int32_t shared,
+                        void* out, gsr_stream_t stream);
+size_t gsr_sam_dec_i2t_workspace_bytes(int32_t P, int32_t T);
+int32_t gsr_sam_dec_i2t(const void* qx, const float* qpe, const float* k, const float* v, const void* x, int32_t P, int32_t T,
+                        int32_t shared, const void* out_w, const void* out_b, const void* ln_w, const void* ln_b, void* ws,
+                        size_t ws_bytes, void* x_out, gsr_stream_t stream);
+size_t gsr_sam_dec_upscale_workspace_bytes(int32_t g, int32_t P);
+int32_t gsr_sam_dec_upscale(const void* x, int32_t g, int32_t P, const void* conv1_w, const void* conv1_b, const void* ln_w,
+                            const void* ln_b, const void* conv2_w, const void* conv2_b, const float* hyper, void* ws, size_t ws_bytes,
+                            float* low_res, gsr_stream_t stream);
+int32_t gsr_sam_dec_num_weights(void);
+size_t gsr_sam_decode_workspace_bytes(int32_t g, int32_t P);
+int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, int32_t n_weights, const float* emb, const float* pe,
+                       const float* points, int32_t P, int32_t image_size, void* ws, size_t ws_bytes, float* low_res, float* iou,
+                       gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only

@@ -1,6 +1,7 @@
 """Time SAM mask generation on one GPU: the encoder kernels of csrc/sam.hip stage by stage and as a whole at 1024x1024 next to
 transformers' SamVisionEncoder in fp32 (the reference's precision) and in fp16 on the same GPU, the mask selection next to
-its torch twin, and the share of an image's time that the (torch) prompt encoder and mask decoder take.
+its torch twin, the decoder kernels of csrc/sam_decoder.hip stage by stage and as a whole for 1024 points next to decode_host
+in fp32 and in fp16, and an image's time split into embed / decode / select with either decoder.
 
     python scripts/sam_bench.py [--out profiles/sam_bench.txt] [--model_type vit_h] [--points_per_side 32]
 
@@ -180,20 +181,105 @@ def selection(dev, args, out, points=1024):
         torch.cuda.empty_cache()
 
 
-def image(cfg, w, dev, args, out):
+def decoder_stages(cfg, w, dev, args, out, P=256):
+    """The stage entry points of csrc/sam_decoder.hip at the grid of `cfg` with P points (random inputs of the right shapes)."""
+    L, s, chk = _lib.lib(), stream(dev), _lib.check
+    g = cfg.grid
+    T = g * g
+    gen = torch.Generator().manual_seed(4)
+    h16 = lambda *shape: torch.randn(*shape, generator=gen).to(torch.float16).to(dev)
+    f32 = lambda *shape: torch.randn(*shape, generator=gen).to(dev)
+    table = [t.to(dev) for t in w.decoder_table()]
+    out(f" decoder stages, g = {g} (T = {T} image tokens), {P} points, 7 tokens per point:")
+    pts, sparse = (1024 * torch.rand(P, 2, generator=gen)).to(dev), torch.empty(P, 2, 256, device=dev)
+    attempt(out, "prompt (2 sparse tokens per point)", lambda: chk(L.gsr_sam_dec_prompt(
+        ptr(pts), P, cfg.image_size, ptr(table[0]), ptr(table[1]), ptr(table[2]), ptr(sparse), s)), dev, args)
+    q, kpe, o16 = f32(P, 7, 128), f32(T, 128), torch.empty(P, 7, 128, dtype=torch.float16, device=dev)
+    kx, v = h16(P, T, 128), h16(P, T, 128)
+    flop = 4.0 * P * 7 * T * 128
+    attempt(out, "t2i attention, per-image keys (layer 0)", lambda: chk(L.gsr_sam_dec_t2i(
+        ptr(q), ptr(kx), ptr(kpe), ptr(v), P, T, 1, ptr(o16), s)), dev, args, flop)
+    attempt(out, "t2i attention, per-point keys (layer 1, final)", lambda: chk(L.gsr_sam_dec_t2i(
+        ptr(q), ptr(kx), ptr(kpe), ptr(v), P, T, 0, ptr(o16), s)), dev, args, flop)
+    x = h16(P, T, 256)
+    attempt(out, "linear 256->128 on the image stream (k, v, q)", lambda: chk(L.gsr_dino_linear(
+        ptr(x), ptr(table[_lib.GSR_SAMD_W_LAYER0 + 12]), None, None, P * T, 256, 128, 0, ptr(kx), s)), dev, args, 2.0 * P * T * 256 * 128)
+    k7, v7 = f32(P, 7, 128), f32(P, 7, 128)
+    it = _lib.GSR_SAMD_W_LAYER0 + 28
+    n4 = _lib.GSR_SAMD_W_LAYER0 + 26
+    nb = L.gsr_sam_dec_i2t_workspace_bytes(P, T)
+    ws = workspace(nb, dev)
+    attempt(out, "i2t (attention, out_proj, residual, layer_norm4)", lambda: chk(L.gsr_sam_dec_i2t(
+        ptr(kx), ptr(kpe), ptr(k7), ptr(v7), ptr(x), P, T, 0, ptr(table[it + 6]), ptr(table[it + 7]), ptr(table[n4]), ptr(table[n4 + 1]),
+        ptr(ws), nb, ptr(x), s)), dev, args, 4.0 * P * T * 7 * 128 + 2.0 * P * T * 128 * 256)
+    del ws
+    up = _lib.GSR_SAMD_W_UP
+    hyper, low = f32(3, P, 32), torch.empty(P, 3, 4 * g, 4 * g, device=dev)
+    nb = L.gsr_sam_dec_upscale_workspace_bytes(g, P)
+    ws = workspace(nb, dev)
+    attempt(out, "upscale (conv1, norm, GELU, conv2, GELU, masks)", lambda: chk(L.gsr_sam_dec_upscale(
+        ptr(x), g, P, *[ptr(t) for t in table[up:up + 6]], ptr(hyper), ptr(ws), nb, ptr(low), s)), dev, args,
+        2.0 * P * T * (256 * 256 + 4 * 64 * 128 + 16 * 32 * 3))
+
+
+def decoder_whole(cfg, w, dev, args, out, points=1024):
+    """The whole prompt encoder and mask decoder for `points` points: the kernels next to decode_host in fp32 (what the
+    generator runs by default) and in fp16 (the strongest stock alternative), on the same GPU in the same run."""
+    g = cfg.grid
+    emb = torch.randn(1, 256, g, g, generator=torch.Generator().manual_seed(5)).to(torch.float16).float().to(dev)
+    pts = S.point_grid(int(round(points ** 0.5)), (cfg.image_size - 8, cfg.image_size))
+    out(f" whole decoder, g = {g}, {len(pts)} points (decoder='hip' chunks them by {S.DECODER_WORKSPACE_BUDGET >> 20} MiB of workspace; "
+        f"decode_host takes 64 at a time):")
+    gen = S.SamMaskGenerator(w, device=dev, decoder="hip")
+    t = {}
+    try:
+        with torch.no_grad():
+            t["hip"] = timed(lambda: gen.decode(emb, pts), dev, args.warmup, args.repeats)
+        out(fmt("kernels (gsr_sam_decode)", t["hip"]))
+        ours = gen.decode(emb, pts)
+    except Exception as e:
+        out(f"  kernels (gsr_sam_decode) failed: {type(e).__name__}: {e}")
+        ours = None
+    for dtype, label in ((torch.float32, "fp32 (the generator's default)"), (torch.float16, "fp16")):
+        try:
+            modules = S.host_decoder(w, dtype, dev)
+            with torch.no_grad():
+                t[label[:4]] = timed(lambda: S.decode_host(w, emb, None, pts, dtype, dev, modules), dev, args.warmup, args.repeats)
+            out(fmt(f"decode_host {label}", t[label[:4]]))
+            if ours is not None:
+                lo, io = S.decode_host(w, emb, None, pts, dtype, dev, modules)
+                out(f"  max |kernels - decode_host {label[:4]}|: masks {float((lo.float() - ours[0]).abs().max()):.3e}, "
+                    f"iou {float((io.float() - ours[1]).abs().max()):.3e}")
+            del modules
+        except Exception as e:
+            out(f"  decode_host {label} failed: {type(e).__name__}: {e}")
+        torch.cuda.empty_cache()
+    if "hip" in t and "fp16" in t:
+        margin = t["fp16"][0] - t["hip"][0]
+        spread = max(t["hip"][2] - t["hip"][1], t["fp16"][2] - t["fp16"][1])
+        verdict = "below" if margin > spread else "NOT below"
+        out(f"  kernels {verdict} decode_host fp16: margin {margin:.3f} ms against a spread of {spread:.3f} ms (the larger min..max)")
+    if "hip" in t and "fp32" in t:
+        out(f"  kernels {'below' if t['hip'][0] < t['fp32'][0] else 'NOT below'} decode_host fp32: {t['fp32'][0] / t['hip'][0]:.2f} x")
+
+
+def image(cfg, w, dev, args, out, decoder="torch"):
     rng = np.random.default_rng(3)
     img = rng.integers(0, 255, (768, 1024, 3), dtype=np.uint8)
-    gen = S.SamMaskGenerator(w, points_per_side=args.points_per_side, device=dev)
+    gen = S.SamMaskGenerator(w, points_per_side=args.points_per_side, device=dev, decoder=decoder)
     rows = []
     for _ in range(args.warmup + 3):
         gen.generate_device(img)
         rows.append(dict(gen.last_ms))
     last = rows[-1]
     total = sum(last.values())
-    out(f" one 1024x768 image, {args.points_per_side ** 2} points (host preprocessing inside embed; the last of {len(rows)} runs):")
+    out(f" one 1024x768 image, {args.points_per_side ** 2} points, decoder={decoder!r} (host preprocessing inside embed; the last of {len(rows)} runs):")
     for k in ("embed", "decode", "select"):
         out(f"  {k:<52s} {last[k]:9.3f} ms  ({100 * last[k] / total:.1f} % of the image)")
-    out("  decode is transformers' prompt encoder and mask decoder in fp32 torch, as they are")
+    if decoder == "torch":
+        out("  decode is transformers' prompt encoder and mask decoder in fp32 torch, as they are")
+    else:
+        out("  decode is gsr_sam_decode: the kernels of csrc/sam_decoder.hip")
 
 
 def main(argv=None):
@@ -231,10 +317,17 @@ def main(argv=None):
         selection(dev, args, out)
     except Exception as e:
         out(f" selection failed: {type(e).__name__}: {e}")
-    try:
-        image(cfg, w, dev, args, out)
-    except Exception as e:
-        out(f" image failed: {type(e).__name__}: {e}")
+    for section in (decoder_stages, decoder_whole):
+        try:
+            section(cfg, w, dev, args, out)
+        except Exception as e:
+            out(f" {section.__name__} failed: {type(e).__name__}: {e}")
+        torch.cuda.empty_cache()
+    for decoder in ("torch", "hip"):
+        try:
+            image(cfg, w, dev, args, out, decoder)
+        except Exception as e:
+            out(f" image ({decoder}) failed: {type(e).__name__}: {e}")
 
 
 if __name__ == "__main__":
