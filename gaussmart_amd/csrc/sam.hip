@@ -1,66 +1,51 @@
 // SAM automatic mask generation (transformers' SamVisionEncoder; the reference's identification/sam.py): the ViT image encoder
 // with windowed attention and the decomposed relative-position bias, and the selection of the candidate masks, as kernels.
 // The rules are in include/gsr.h (SV_EMBED, SV_ATTN, SV_NECK, SM_SCORE, SM_NMS, SM_EMIT); each has one named place below.
-// The matrix products outside attention are DN_LINEAR's and the LayerNorms DN_NORM's (dino.hip, through dino_internal.h).
+// The matrix products outside attention are DN_LINEAR's and the LayerNorms DN_NORM's (vit.hip, through vit_common.h).
 // No split-K, no float atomics: the bits are the same on every run.
 #include <climits>
 #include "cloud_common.h"
-#include "dino_internal.h"
+#include "vit_attn.h"
 
-typedef _Float16 sv_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 sv_h4 __attribute__((ext_vector_type(4)));
-typedef float sv_f32x16 __attribute__((ext_vector_type(16)));
-
-#define SV_PATCH 16
-#define SV_PATCH_K (3 * SV_PATCH * SV_PATCH)
 #define SV_MAX_GRID 256             // tokens per side: g g windows of size 1 must fit the launch grid's z
-
-// row of a 32x32 accumulator held in register `reg` of a lane of half `h` (the column is lane & 31)
-__device__ __forceinline__ int sv_acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
 // ---------------------------------------------------------------- SV_EMBED (gather)
 // patches[p][c 256 + ky 16 + kx] = fp16(x[c,16 py + ky,16 px + kx]): DN_EMBED's k order, the input already normalised.
 __global__ void __launch_bounds__(256) sv_im2col_kernel(const float* __restrict__ x, int S, int g, dn_half* __restrict__ patches) {
-    const int64_t n = (int64_t)g * g * (SV_PATCH_K / 8);
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int64_t row = i / (SV_PATCH_K / 8);
-    const int part = (int)(i - row * (SV_PATCH_K / 8));
-    const int c = part >> 5, ky = (part >> 1) & 15, kx0 = (part & 1) * 8;
-    const int py = (int)(row / g), px = (int)(row - (int64_t)py * g);
-    const float* src = x + ((int64_t)c * S + (py * SV_PATCH + ky)) * S + px * SV_PATCH + kx0;
-    sv_h8 v;
+    VitPatchPart a;
+    if (!vit_patch_part((int64_t)g * g, a)) return;
+    const int py = (int)(a.row / g), px = (int)(a.row - (int64_t)py * g);
+    const float* src = x + ((int64_t)a.c * S + (py * VIT_PATCH + a.ky)) * S + px * VIT_PATCH + a.kx0;
+    vit_h8 v;
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (dn_half)src[e];
-    *reinterpret_cast<sv_h8*>(patches + row * SV_PATCH_K + part * 8) = v;
+    vit_patch_store(patches, a, v);
 }
 
 static int sv_embed(const float* x, int S, int hidden, const dn_half* pw, const dn_half* pb, const dn_half* pos, dn_half* patches,
                     float* out, hipStream_t s) {
-    const int g = S / SV_PATCH;
-    const int64_t n = (int64_t)g * g * (SV_PATCH_K / 8);
-    hipLaunchKernelGGL(sv_im2col_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, S, g, patches);
+    const int g = S / VIT_PATCH;
+    hipLaunchKernelGGL(sv_im2col_kernel, dim3(vit_patch_blocks((int64_t)g * g)), dim3(256), 0, s, x, S, g, patches);
     GSR_LAUNCH_CHECK();
-    return dn_linear(patches, pw, pb, pos, out, (int64_t)g * g, SV_PATCH_K, hidden, DN_EPI_POS, 1, 0, 0, s);
+    return dn_linear(patches, pw, pb, pos, out, (int64_t)g * g, VIT_PATCH_K, hidden, DN_EPI_POS, s);
 }
 
 static int sv_check_image(int S) {
-    if (S < SV_PATCH || S % SV_PATCH != 0 || S / SV_PATCH > SV_MAX_GRID) {
-        gsr_set_error("sam: image_size %d must be a multiple of 16 in 16 .. %d", S, SV_PATCH * SV_MAX_GRID);
+    if (S < VIT_PATCH || S % VIT_PATCH != 0 || S / VIT_PATCH > SV_MAX_GRID) {
+        gsr_set_error("sam: image_size %d must be a multiple of 16 in 16 .. %d", S, VIT_PATCH * SV_MAX_GRID);
         return GSR_E_INVALID;
     }
     return GSR_OK;
 }
 
 extern "C" size_t gsr_sam_embed_workspace_bytes(int32_t S) {
-    if (S < SV_PATCH) return 0;
-    return gsr_align((size_t)(S / SV_PATCH) * (size_t)(S / SV_PATCH) * SV_PATCH_K * 2);
+    if (S < VIT_PATCH) return 0;
+    return gsr_align((size_t)(S / VIT_PATCH) * (size_t)(S / VIT_PATCH) * VIT_PATCH_K * 2);
 }
 
 extern "C" int32_t gsr_sam_embed(const float* pixel_values, int32_t S, int32_t hidden, const void* patch_w, const void* patch_b,
                                  const void* pos_embed, void* ws, size_t ws_bytes, float* out, gsr_stream_t stream_) {
-    int rc;
-    if ((rc = sv_check_image(S)) != GSR_OK) return rc;
+    GSR_TRY(sv_check_image(S));
     if (hidden < 1) { gsr_set_error("sam embed: hidden %d must be >= 1", hidden); return GSR_E_INVALID; }
     if (!pixel_values || !patch_w || !patch_b || !pos_embed || !out) {
         gsr_set_error("sam embed: pixel_values / patch_w / patch_b / pos_embed / out is null");
@@ -100,55 +85,48 @@ __global__ void __launch_bounds__(256) sv_rel_kernel(const dn_half* __restrict__
 }
 
 // ---------------------------------------------------------------- SV_ATTN
-// DN_ATTN's scheme (one pass, S^T = K Q^T so that a lane owns a query, P^T the B operand of O^T = V^T P^T as it lies) over the
-// s s positions of one window.  A workgroup of 4 waves owns 128 window positions of one head of one window; positions outside
-// the grid are padded: as queries they are computed on zeros and never written, as keys they are real and their k and v are
-// the k and v thirds of the qkv bias (what DN_LINEAR gives on a zero row), read from the bias itself: the padded layout is
-// synthesised, not stored.  K and V tiles of 64 go through LDS (V transposed); positions past s s are zeros there and
-// their scores -inf before the maximum.  HD = 80: five k-steps of 16, and the O^T tiles cover 96 rows of which rows 80..95
-// of V^T are zeros and never stored.  The bits of a window depend on its own data only.
-#define SA_BQ 128
-#define SA_BKV 64
-#define SA_LDV 68
+// The tile of vit_attn.h (DN_ATTN's scheme) over the s s positions of one window.  A workgroup of 4 waves owns 128 window
+// positions of one head of one window; positions outside the grid are padded: as queries they are computed on zeros and never
+// written, as keys they are real and their k and v are the k and v thirds of the qkv bias (what DN_LINEAR gives on a zero row),
+// read from the bias itself: the padded layout is synthesised, not stored.  K and V tiles of 64 go through LDS (V transposed);
+// positions past s s are zeros there and their scores -inf before the maximum.  The base-2 score is ((raw scale + bh) + bw)
+// log2(e), the two bias terms from the pre-pass.  The bits of a window depend on its own data only.
 #define SA_LOG2E 1.44269504088896340736f
 
 template <int HD>
 __global__ void __launch_bounds__(256) sv_attn_kernel(const dn_half* __restrict__ qkv, const dn_half* __restrict__ qkv_bias,
                                                       const float* __restrict__ rel, dn_half* __restrict__ o, int g, int s, int nwx,
                                                       int heads, float scale) {
-    constexpr int KS = HD / 16, DT = (HD + 31) / 32, LDK = HD + 8, CH = HD / 8;
-    __shared__ __attribute__((aligned(16))) dn_half Ks[SA_BKV * LDK];       // [kv][d]
-    __shared__ __attribute__((aligned(16))) dn_half Vt[DT * 32 * SA_LDV];   // [d][kv]
-    __shared__ int s_kh[SA_BKV], s_kw[SA_BKV];
+    typedef VitAttnTile<HD> Tile;
+    constexpr int KS = Tile::KS, DT = Tile::DT, LDK = Tile::LDK, CH = HD / 8;
+    __shared__ __attribute__((aligned(16))) dn_half Ks[VA_BKV * LDK];       // [kv][d]
+    __shared__ __attribute__((aligned(16))) dn_half Vt[DT * 32 * VA_LDV];   // [d][kv]
+    __shared__ int s_kh[VA_BKV], s_kw[VA_BKV];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
     const int hidden = heads * HD;
     const int64_t ld = 3 * (int64_t)hidden;
     const int head = (int)blockIdx.y, win = (int)blockIdx.z, wy = win / nwx, wx = win - wy * nwx;
     const int S2 = s * s;
-    const int ql = (int)blockIdx.x * SA_BQ + wave * 32 + r;
+    const int ql = (int)blockIdx.x * VA_BQ + wave * 32 + r;
     const int qh = ql / s, qw = ql - qh * s, qy = wy * s + qh, qx = wx * s + qw;
     const bool qok = ql < S2 && qy < g && qx < g;
     const int64_t qtok = qok ? (int64_t)qy * g + qx : 0;
-    sv_h8 qf[KS];
+    vit_h8 qf[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-        if (qok) qf[ks] = *reinterpret_cast<const sv_h8*>(qkv + qtok * ld + head * HD + ks * 16 + 8 * h);
+        if (qok) qf[ks] = *reinterpret_cast<const vit_h8*>(qkv + qtok * ld + head * HD + ks * 16 + 8 * h);
         else
 #pragma unroll
             for (int e = 0; e < 8; ++e) qf[ks][e] = (dn_half)0.f;
     }
     const float* relq = rel + (qtok * heads + head) * 2 * s;        // rh at [0, s), rw at [s, 2 s)
-    for (int i = HD * SA_LDV + t; i < DT * 32 * SA_LDV; i += 256) Vt[i] = (dn_half)0.f;   // rows HD .. 32 DT - 1: never stored below
-    sv_f32x16 acc[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[dt][e] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
+    for (int i = HD * VA_LDV + t; i < DT * 32 * VA_LDV; i += 256) Vt[i] = (dn_half)0.f;   // rows HD .. 32 DT - 1: never stored below
+    Tile tile;
+    tile.init();
 
-    for (int kv0 = 0; kv0 < S2; kv0 += SA_BKV) {
+    for (int kv0 = 0; kv0 < S2; kv0 += VA_BKV) {
         __syncthreads();            // the previous tile's reads are done
-        for (int c = t; c < SA_BKV * CH; c += 256) {
+        for (int c = t; c < VA_BKV * CH; c += 256) {
             const int row = c / CH, col = c - row * CH, j = kv0 + row;
             uint4 kk = make_uint4(0, 0, 0, 0), vv = make_uint4(0, 0, 0, 0);
             if (j < S2) {
@@ -159,11 +137,11 @@ __global__ void __launch_bounds__(256) sv_attn_kernel(const dn_half* __restrict_
                 vv = *reinterpret_cast<const uint4*>(src + hidden);
             }
             *reinterpret_cast<uint4*>(&Ks[row * LDK + 8 * col]) = kk;
-            const sv_h8 v8 = *reinterpret_cast<const sv_h8*>(&vv);
+            const vit_h8 v8 = *reinterpret_cast<const vit_h8*>(&vv);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) Vt[(8 * col + e) * SA_LDV + row] = v8[e];
+            for (int e = 0; e < 8; ++e) Vt[(8 * col + e) * VA_LDV + row] = v8[e];
         }
-        if (t < SA_BKV) {
+        if (t < VA_BKV) {
             const int j = kv0 + t;
             const int kh = j < S2 ? j / s : -1;
             s_kh[t] = kh;
@@ -171,84 +149,21 @@ __global__ void __launch_bounds__(256) sv_attn_kernel(const dn_half* __restrict_
         }
         __syncthreads();
 
-        sv_f32x16 sc[2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) sc[kb][e] = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const sv_h8 a = *reinterpret_cast<const sv_h8*>(&Ks[(kb * 32 + r) * LDK + ks * 16 + 8 * h]);
-                sc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, qf[ks], sc[kb], 0, 0, 0);
+        // position kv0 of the tile is inside the window, so the tile's maximum is finite
+        tile.step(Ks, Vt, qf, r, h, [&](float raw, int jj) {
+            const int kh = s_kh[jj];
+            float tv = -INFINITY;
+            if (kh >= 0) {
+                const float bh = qok ? relq[kh] : 0.f, bw = qok ? relq[s + s_kw[jj]] : 0.f;
+                tv = ((raw * scale + bh) + bw) * SA_LOG2E;
             }
-        }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int jj = kb * 32 + sv_acc_row(e, h);
-                const int kh = s_kh[jj];
-                float tv = -INFINITY;
-                if (kh >= 0) {
-                    const float bh = qok ? relq[kh] : 0.f, bw = qok ? relq[s + s_kw[jj]] : 0.f;
-                    tv = ((sc[kb][e] * scale + bh) + bw) * SA_LOG2E;
-                }
-                sc[kb][e] = tv;
-                mx = fmaxf(mx, tv);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);           // finite: position kv0 of this tile is inside the window
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const float p = __builtin_amdgcn_exp2f(sc[kb][e] - m_new);
-                sc[kb][e] = p;
-                psum += p;
-            }
-        psum += __shfl_xor(psum, 32, 64);
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[dt][e] *= alpha;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int ss = 0; ss < 2; ++ss) {
-                sv_h8 pf;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) pf[e] = (dn_half)sc[kb][8 * ss + e];
-#pragma unroll
-                for (int dt = 0; dt < DT; ++dt) {
-                    // element j of half h is kv 16 ss + 8 (j >> 2) + 4 h + (j & 3) of the block: two runs of 4 consecutive kv
-                    const dn_half* vp = &Vt[(dt * 32 + r) * SA_LDV + kb * 32 + ss * 16 + 4 * h];
-                    const sv_h4 lo = *reinterpret_cast<const sv_h4*>(vp), hi = *reinterpret_cast<const sv_h4*>(vp + 8);
-                    sv_h8 a;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { a[e] = lo[e]; a[4 + e] = hi[e]; }
-                    acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, pf, acc[dt], 0, 0, 0);
-                }
-            }
+            return tv;
+        });
     }
     if (!qok) return;
-    dn_half* orow = o + qtok * hidden + head * HD;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const int d0 = dt * 32 + 8 * gq + 4 * h;
-            if (d0 >= HD) continue;
-            sv_h4 out;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) out[e] = (dn_half)(acc[dt][4 * gq + e] / l_run);
-            *reinterpret_cast<sv_h4*>(orow + d0) = out;
-        }
+    tile.store(o + qtok * hidden + head * HD, h);
 }
+
 
 static int sv_check_attn(int g, int w, int heads, int hd, int rel_rows) {
     if (g < 1 || g > SV_MAX_GRID) { gsr_set_error("sam attn: grid %d is outside 1 .. %d", g, SV_MAX_GRID); return GSR_E_INVALID; }
@@ -274,7 +189,7 @@ static int sv_attn(const dn_half* qkv, const dn_half* qkv_bias, const dn_half* R
     hipLaunchKernelGGL(sv_rel_kernel, dim3((unsigned)((n_rel + 255) / 256)), dim3(256), 0, st, qkv, Rh, Rw, g, s, heads, hd, rel);
     GSR_LAUNCH_CHECK();
     const float scale = (float)(1.0 / sqrt((double)hd));
-    const dim3 grid((unsigned)((s * s + SA_BQ - 1) / SA_BQ), (unsigned)heads, (unsigned)(nw * nw));
+    const dim3 grid((unsigned)((s * s + VA_BQ - 1) / VA_BQ), (unsigned)heads, (unsigned)(nw * nw));
     if (hd == 64) hipLaunchKernelGGL(sv_attn_kernel<64>, grid, dim3(256), 0, st, qkv, qkv_bias, rel, out, g, s, nw, heads, scale);
     else hipLaunchKernelGGL(sv_attn_kernel<80>, grid, dim3(256), 0, st, qkv, qkv_bias, rel, out, g, s, nw, heads, scale);
     GSR_LAUNCH_CHECK();
@@ -289,8 +204,7 @@ extern "C" size_t gsr_sam_attn_workspace_bytes(int32_t g, int32_t window, int32_
 extern "C" int32_t gsr_sam_attn(const void* qkv, const void* qkv_bias, const void* rel_pos_h, const void* rel_pos_w, int32_t rel_rows,
                                 int32_t g, int32_t window, int32_t heads, int32_t head_dim, void* ws, size_t ws_bytes, void* out,
                                 gsr_stream_t stream_) {
-    int rc;
-    if ((rc = sv_check_attn(g, window, heads, head_dim, rel_rows)) != GSR_OK) return rc;
+    GSR_TRY(sv_check_attn(g, window, heads, head_dim, rel_rows));
     if (!qkv || !qkv_bias || !rel_pos_h || !rel_pos_w || !out) {
         gsr_set_error("sam attn: qkv / qkv_bias / rel_pos_h / rel_pos_w / out is null");
         return GSR_E_INVALID;
@@ -350,15 +264,14 @@ static int sv_neck(const float* x, int g, int hidden, int Cn, const dn_half* con
                    const dn_half* conv2, const dn_half* ln2w, const dn_half* ln2b, float eps, const SvNeckLayout& lay, float* out,
                    hipStream_t s) {
     const int64_t T = (int64_t)g * g;
-    int rc;
     hipLaunchKernelGGL(sv_cast_kernel, dim3((unsigned)((T * hidden + 255) / 256)), dim3(256), 0, s, x, T * hidden, lay.xh);
     GSR_LAUNCH_CHECK();
-    if ((rc = dn_linear(lay.xh, conv1, nullptr, nullptr, lay.c1, T, hidden, Cn, DN_EPI_F32, 1, 0, 0, s)) != GSR_OK) return rc;
-    if ((rc = dn_norm(lay.c1, T, Cn, Cn, ln1w, ln1b, eps, lay.ln, 0, s)) != GSR_OK) return rc;
+    GSR_TRY(dn_linear(lay.xh, conv1, nullptr, nullptr, lay.c1, T, hidden, Cn, DN_EPI_F32, s));
+    GSR_TRY(dn_norm(lay.c1, T, Cn, Cn, ln1w, ln1b, eps, lay.ln, 0, s));
     hipLaunchKernelGGL(sv_im2col3_kernel, dim3((unsigned)((T * 9 * Cn + 255) / 256)), dim3(256), 0, s, lay.ln, g, Cn, lay.col);
     GSR_LAUNCH_CHECK();
-    if ((rc = dn_linear(lay.col, conv2, nullptr, nullptr, lay.c2, T, 9 * Cn, Cn, DN_EPI_F32, 1, 0, 0, s)) != GSR_OK) return rc;
-    if ((rc = dn_norm(lay.c2, T, Cn, Cn, ln2w, ln2b, eps, lay.c1, 1, s)) != GSR_OK) return rc;
+    GSR_TRY(dn_linear(lay.col, conv2, nullptr, nullptr, lay.c2, T, 9 * Cn, Cn, DN_EPI_F32, s));
+    GSR_TRY(dn_norm(lay.c2, T, Cn, Cn, ln2w, ln2b, eps, lay.c1, 1, s));
     hipLaunchKernelGGL(sv_transpose_kernel, dim3((unsigned)((T * Cn + 255) / 256)), dim3(256), 0, s, lay.c1, T, Cn, out);
     GSR_LAUNCH_CHECK();
     return GSR_OK;
@@ -381,8 +294,7 @@ extern "C" size_t gsr_sam_neck_workspace_bytes(int32_t g, int32_t hidden, int32_
 extern "C" int32_t gsr_sam_neck(const float* x, int32_t g, int32_t hidden, int32_t channels, const void* conv1_w, const void* ln1_w,
                                 const void* ln1_b, const void* conv2_w, const void* ln2_w, const void* ln2_b, void* ws,
                                 size_t ws_bytes, float* out, gsr_stream_t stream_) {
-    int rc;
-    if ((rc = sv_check_neck(g, hidden, channels)) != GSR_OK) return rc;
+    GSR_TRY(sv_check_neck(g, hidden, channels));
     if (!x || !conv1_w || !ln1_w || !ln1_b || !conv2_w || !ln2_w || !ln2_b || !out) {
         gsr_set_error("sam neck: x / a weight / out is null");
         return GSR_E_INVALID;
@@ -400,8 +312,7 @@ extern "C" int32_t gsr_sam_neck(const float* x, int32_t g, int32_t hidden, int32
 // ---------------------------------------------------------------- the whole encoder
 static int sv_check_cfg(const GsrSamConfig* c) {
     if (!c) { gsr_set_error("sam: cfg is null"); return GSR_E_INVALID; }
-    int rc;
-    if ((rc = sv_check_image(c->image_size)) != GSR_OK) return rc;
+    GSR_TRY(sv_check_image(c->image_size));
     if (c->head_dim != 64 && c->head_dim != 80) { gsr_set_error("sam: head_dim %d is not built (64 and 80 are)", c->head_dim); return GSR_E_INVALID; }
     if (c->heads < 1 || c->heads > 1024 || c->hidden != c->heads * c->head_dim) {
         gsr_set_error("sam: hidden %d is not heads (%d) x head_dim (%d)", c->hidden, c->heads, c->head_dim);
@@ -415,9 +326,9 @@ static int sv_check_cfg(const GsrSamConfig* c) {
     if (c->layers < 1 || c->layers > 4096) { gsr_set_error("sam: layers %d is outside 1 .. 4096", c->layers); return GSR_E_INVALID; }
     if (c->ln_eps != 1e-6f) { gsr_set_error("sam: ln_eps %g is not 1e-6", (double)c->ln_eps); return GSR_E_INVALID; }
     if (!c->window_host || !c->rel_rows_host) { gsr_set_error("sam: window_host / rel_rows_host is null"); return GSR_E_INVALID; }
-    const int g = c->image_size / SV_PATCH;
+    const int g = c->image_size / VIT_PATCH;
     for (int l = 0; l < c->layers; ++l)
-        if ((rc = sv_check_attn(g, c->window_host[l], c->heads, c->head_dim, c->rel_rows_host[l])) != GSR_OK) return rc;
+        GSR_TRY(sv_check_attn(g, c->window_host[l], c->heads, c->head_dim, c->rel_rows_host[l]));
     return GSR_OK;
 }
 
@@ -427,7 +338,7 @@ struct SvLayout {
     dn_half *xn, *qkv, *att, *mlp, *patches;
     void* neck;
     SvLayout(const GsrSamConfig* c, void* ws) {
-        const int g = c->image_size / SV_PATCH;
+        const int g = c->image_size / VIT_PATCH;
         const size_t T = (size_t)g * g, row = T * c->hidden;
         int smax = 1;
         for (int l = 0; l < c->layers; ++l) {
@@ -440,7 +351,7 @@ struct SvLayout {
         qkv = cur.take<dn_half>(row * 3 * 2);
         att = cur.take<dn_half>(row * 2);
         mlp = cur.take<dn_half>(T * c->mlp_dim * 2);
-        patches = cur.take<dn_half>(T * SV_PATCH_K * 2);
+        patches = cur.take<dn_half>(T * VIT_PATCH_K * 2);
         rel = cur.take<float>(sv_rel_bytes(g, smax, c->heads));
         neck = cur.take<void>(SvNeckLayout(g, c->hidden, c->output_channels, nullptr).total);
         total = cur.off;
@@ -456,8 +367,7 @@ extern "C" int32_t gsr_sam_num_weights(int32_t layers) { return layers < 1 ? 0 :
 
 extern "C" int32_t gsr_sam_encode(const GsrSamConfig* cfg, const void* const* weights_host, int32_t n_weights,
                                   const float* pixel_values, void* ws, size_t ws_bytes, float* out, gsr_stream_t stream_) {
-    int rc;
-    if ((rc = sv_check_cfg(cfg)) != GSR_OK) return rc;
+    GSR_TRY(sv_check_cfg(cfg));
     if (!weights_host || n_weights != gsr_sam_num_weights(cfg->layers)) {
         gsr_set_error("sam: the weight table is null or has %d entries (%d layers need %d)", n_weights, cfg->layers,
                       gsr_sam_num_weights(cfg->layers));
@@ -473,21 +383,20 @@ extern "C" int32_t gsr_sam_encode(const GsrSamConfig* cfg, const void* const* we
     }
     auto wp = [&](int i) { return static_cast<const dn_half*>(weights_host[i]); };
     hipStream_t s = static_cast<hipStream_t>(stream_);
-    const int hid = cfg->hidden, g = cfg->image_size / SV_PATCH;
+    const int hid = cfg->hidden, g = cfg->image_size / VIT_PATCH;
     const int64_t T = (int64_t)g * g;
-    if ((rc = sv_embed(pixel_values, cfg->image_size, hid, wp(GSR_SAM_W_PATCH_W), wp(GSR_SAM_W_PATCH_B), wp(GSR_SAM_W_POS), lay.patches,
-                       lay.resid, s)) != GSR_OK)
-        return rc;
+    GSR_TRY(sv_embed(pixel_values, cfg->image_size, hid, wp(GSR_SAM_W_PATCH_W), wp(GSR_SAM_W_PATCH_B), wp(GSR_SAM_W_POS), lay.patches,
+                     lay.resid, s));
     for (int l = 0; l < cfg->layers; ++l) {
         const int w0 = GSR_SAM_W_LAYER0 + GSR_SAM_W_PER_LAYER * l;
-        if ((rc = dn_norm(lay.resid, T, hid, hid, wp(w0 + GSR_SAM_L_NORM1_W), wp(w0 + GSR_SAM_L_NORM1_B), cfg->ln_eps, lay.xn, 0, s)) != GSR_OK) return rc;
-        if ((rc = dn_linear(lay.xn, wp(w0 + GSR_SAM_L_QKV_W), wp(w0 + GSR_SAM_L_QKV_B), nullptr, lay.qkv, T, hid, 3 * hid, DN_EPI_BIAS, 1, 0, 0, s)) != GSR_OK) return rc;
-        if ((rc = sv_attn(lay.qkv, wp(w0 + GSR_SAM_L_QKV_B), wp(w0 + GSR_SAM_L_REL_H), wp(w0 + GSR_SAM_L_REL_W), g, cfg->window_host[l],
-                          cfg->heads, cfg->head_dim, lay.rel, lay.att, s)) != GSR_OK) return rc;
-        if ((rc = dn_linear(lay.att, wp(w0 + GSR_SAM_L_PROJ_W), wp(w0 + GSR_SAM_L_PROJ_B), nullptr, lay.resid, T, hid, hid, DN_EPI_RESID1, 1, 0, 0, s)) != GSR_OK) return rc;
-        if ((rc = dn_norm(lay.resid, T, hid, hid, wp(w0 + GSR_SAM_L_NORM2_W), wp(w0 + GSR_SAM_L_NORM2_B), cfg->ln_eps, lay.xn, 0, s)) != GSR_OK) return rc;
-        if ((rc = dn_linear(lay.xn, wp(w0 + GSR_SAM_L_LIN1_W), wp(w0 + GSR_SAM_L_LIN1_B), nullptr, lay.mlp, T, hid, cfg->mlp_dim, DN_EPI_GELU, 1, 0, 0, s)) != GSR_OK) return rc;
-        if ((rc = dn_linear(lay.mlp, wp(w0 + GSR_SAM_L_LIN2_W), wp(w0 + GSR_SAM_L_LIN2_B), nullptr, lay.resid, T, cfg->mlp_dim, hid, DN_EPI_RESID1, 1, 0, 0, s)) != GSR_OK) return rc;
+        GSR_TRY(dn_norm(lay.resid, T, hid, hid, wp(w0 + GSR_SAM_L_NORM1_W), wp(w0 + GSR_SAM_L_NORM1_B), cfg->ln_eps, lay.xn, 0, s));
+        GSR_TRY(dn_linear(lay.xn, wp(w0 + GSR_SAM_L_QKV_W), wp(w0 + GSR_SAM_L_QKV_B), nullptr, lay.qkv, T, hid, 3 * hid, DN_EPI_BIAS, s));
+        GSR_TRY(sv_attn(lay.qkv, wp(w0 + GSR_SAM_L_QKV_B), wp(w0 + GSR_SAM_L_REL_H), wp(w0 + GSR_SAM_L_REL_W), g, cfg->window_host[l],
+                        cfg->heads, cfg->head_dim, lay.rel, lay.att, s));
+        GSR_TRY(dn_linear(lay.att, wp(w0 + GSR_SAM_L_PROJ_W), wp(w0 + GSR_SAM_L_PROJ_B), nullptr, lay.resid, T, hid, hid, DN_EPI_RESID1, s));
+        GSR_TRY(dn_norm(lay.resid, T, hid, hid, wp(w0 + GSR_SAM_L_NORM2_W), wp(w0 + GSR_SAM_L_NORM2_B), cfg->ln_eps, lay.xn, 0, s));
+        GSR_TRY(dn_linear(lay.xn, wp(w0 + GSR_SAM_L_LIN1_W), wp(w0 + GSR_SAM_L_LIN1_B), nullptr, lay.mlp, T, hid, cfg->mlp_dim, DN_EPI_GELU, s));
+        GSR_TRY(dn_linear(lay.mlp, wp(w0 + GSR_SAM_L_LIN2_W), wp(w0 + GSR_SAM_L_LIN2_B), nullptr, lay.resid, T, cfg->mlp_dim, hid, DN_EPI_RESID1, s));
     }
     const int n0 = n_weights - GSR_SAM_W_NECK;
     SvNeckLayout nl(g, hid, cfg->output_channels, lay.neck);
@@ -608,8 +517,7 @@ extern "C" int32_t gsr_sam_mask_score(const float* logits, int32_t n, int32_t L,
                                       float tau, float delta, const uint8_t* skip, int32_t* counts, float* boxes,
                                       gsr_stream_t stream_) {
     SmGeom G;
-    int rc;
-    if ((rc = sm_geom(L, ih, iw, oh, ow, &G)) != GSR_OK) return rc;
+    GSR_TRY(sm_geom(L, ih, iw, oh, ow, &G));
     if (n < 0) { gsr_set_error("sam mask score: n %d must be >= 0", n); return GSR_E_INVALID; }
     if (!(delta >= 0.f) || !(tau == tau)) { gsr_set_error("sam mask score: tau must be a number and delta >= 0"); return GSR_E_INVALID; }
     if (n == 0) return GSR_OK;
@@ -623,8 +531,7 @@ extern "C" int32_t gsr_sam_mask_score(const float* logits, int32_t n, int32_t L,
 extern "C" int32_t gsr_sam_mask_emit(const float* logits, int32_t n, int32_t L, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
                                      float tau, const int32_t* index, int32_t m, uint8_t* out, gsr_stream_t stream_) {
     SmGeom G;
-    int rc;
-    if ((rc = sm_geom(L, ih, iw, oh, ow, &G)) != GSR_OK) return rc;
+    GSR_TRY(sm_geom(L, ih, iw, oh, ow, &G));
     if (n < 0 || m < 0 || m > 65535) { gsr_set_error("sam mask emit: n %d must be >= 0 and m %d in 0 .. 65535", n, m); return GSR_E_INVALID; }
     if (m == 0) return GSR_OK;
     if (!logits || !index || !out) { gsr_set_error("sam mask emit: logits / index / out is null"); return GSR_E_INVALID; }

@@ -1,10 +1,10 @@
 // SAM's prompt encoder and mask decoder (transformers' SamPromptEncoder / SamMaskDecoder with the stock configuration: hidden
 // 256, two two-way layers, 8 heads, 4 mask tokens, one foreground point per prompt, multimask output) as kernels.  The rules
 // are in include/gsr.h (SD_PROMPT, SD_IMAGE, SD_TOKENS, SD_T2I, SD_I2T, SD_UP, SD_HEADS); each has one named place below.
-// Every matrix product with a weight is DN_LINEAR (dino.hip, through dino_internal.h): fp16 operands, one k-ascending fp32
+// Every matrix product with a weight is DN_LINEAR (vit.hip, through vit_common.h): fp16 operands, one k-ascending fp32
 // chain per output element, rows independent of each other.  The attention cores, the LayerNorms of the image stream and the
 // mask product are the kernels of this file.  No split-K, no float atomics: a point's bits depend on its own data only.
-#include "dino_internal.h"
+#include "vit_common.h"
 
 #define SD_C 256           // hidden
 #define SD_CI 128           // internal width of the cross attentions: 8 heads of 16
@@ -15,21 +15,6 @@
 #define SD_MAX_POINTS 65535
 #define SD_EPS 1e-6f        // SamMaskDecoderConfig.layer_norm_eps and SamLayerNorm's default
 #define SD_EPS_FINAL 1e-5f  // layer_norm_final_attn is a plain nn.LayerNorm
-
-typedef _Float16 sd_h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 sd_h8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float sd_wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ float sd_wave_max(float v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ float sd_gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
 // ---------------------------------------------------------------- SD_PROMPT
 // out[p][0][c] = sinf(arg_c) + fp32(point1[c]), out[p][0][128 + c] = cosf(arg_c) + fp32(point1[128 + c]), out[p][1][:] = fp32(nap);
@@ -66,8 +51,7 @@ static int sd_check_grid(int g) {
 
 extern "C" int32_t gsr_sam_dec_prompt(const float* points, int32_t P, int32_t image_size, const float* gauss, const void* point1,
                                       const void* not_a_point, float* out, gsr_stream_t stream_) {
-    int rc;
-    if ((rc = sd_check_points(P)) != GSR_OK) return rc;
+    GSR_TRY(sd_check_points(P));
     if (image_size < 16 || image_size > 16 * SD_MAX_GRID) {
         gsr_set_error("sam decoder: image_size %d is outside 16 .. %d", image_size, 16 * SD_MAX_GRID);
         return GSR_E_INVALID;
@@ -173,7 +157,7 @@ __global__ void __launch_bounds__(256) sd_t2i_kernel(const float* __restrict__ q
     const float* pp = kpe ? kpe + h * 16 : nullptr;
     auto scores = [&](int key, float* s) {
         float kk[16];
-        const sd_h8 a = *reinterpret_cast<const sd_h8*>(kp + (int64_t)key * SD_CI), b = *reinterpret_cast<const sd_h8*>(kp + (int64_t)key * SD_CI + 8);
+        const vit_h8 a = *reinterpret_cast<const vit_h8*>(kp + (int64_t)key * SD_CI), b = *reinterpret_cast<const vit_h8*>(kp + (int64_t)key * SD_CI + 8);
 #pragma unroll
         for (int d = 0; d < 8; ++d) { kk[d] = (float)a[d]; kk[8 + d] = (float)b[d]; }
         if (pp) {
@@ -198,7 +182,7 @@ __global__ void __launch_bounds__(256) sd_t2i_kernel(const float* __restrict__ q
         for (int j = 0; j < SD_TOK; ++j) m[j] = fmaxf(m[j], s[j]);
     }
 #pragma unroll
-    for (int j = 0; j < SD_TOK; ++j) m[j] = sd_wave_max(m[j]);
+    for (int j = 0; j < SD_TOK; ++j) m[j] = wave_max_f32(m[j]);
     if (lane == 0)
 #pragma unroll
         for (int j = 0; j < SD_TOK; ++j) red[wave][j] = m[j];
@@ -217,7 +201,7 @@ __global__ void __launch_bounds__(256) sd_t2i_kernel(const float* __restrict__ q
     for (int key = t; key < T; key += 256) {
         float s[SD_TOK], vv[16];
         scores(key, s);
-        const sd_h8 a = *reinterpret_cast<const sd_h8*>(vp + (int64_t)key * SD_CI), b = *reinterpret_cast<const sd_h8*>(vp + (int64_t)key * SD_CI + 8);
+        const vit_h8 a = *reinterpret_cast<const vit_h8*>(vp + (int64_t)key * SD_CI), b = *reinterpret_cast<const vit_h8*>(vp + (int64_t)key * SD_CI + 8);
 #pragma unroll
         for (int d = 0; d < 8; ++d) { vv[d] = (float)a[d]; vv[8 + d] = (float)b[d]; }
 #pragma unroll
@@ -230,9 +214,9 @@ __global__ void __launch_bounds__(256) sd_t2i_kernel(const float* __restrict__ q
     }
 #pragma unroll
     for (int j = 0; j < SD_TOK; ++j) {
-        l[j] = sd_wave_sum(l[j]);
+        l[j] = wave_sum_f32(l[j]);
 #pragma unroll
-        for (int d = 0; d < 16; ++d) acc[j][d] = sd_wave_sum(acc[j][d]);
+        for (int d = 0; d < 16; ++d) acc[j][d] = wave_sum_f32(acc[j][d]);
     }
     if (lane == 0)
 #pragma unroll
@@ -260,8 +244,7 @@ static int sd_t2i(const float* q, const dn_half* kx, const float* kpe, const dn_
 
 extern "C" int32_t gsr_sam_dec_t2i(const float* q, const void* kx, const float* kpe, const void* v, int32_t P, int32_t T,
                                    int32_t shared, void* out, gsr_stream_t stream_) {
-    int rc;
-    if ((rc = sd_check_points(P)) != GSR_OK) return rc;
+    GSR_TRY(sd_check_points(P));
     if (T < 1 || T > SD_MAX_GRID * SD_MAX_GRID) { gsr_set_error("sam dec t2i: T %d is outside 1 .. %d", T, SD_MAX_GRID * SD_MAX_GRID); return GSR_E_INVALID; }
     if (!q || !kx || !v || !out) { gsr_set_error("sam dec t2i: q / kx / v / out is null"); return GSR_E_INVALID; }
     return sd_t2i(q, static_cast<const dn_half*>(kx), kpe, static_cast<const dn_half*>(v), P, T, shared != 0, 0.25f,
@@ -286,7 +269,7 @@ __global__ void __launch_bounds__(256) sd_i2t_kernel(const dn_half* __restrict__
     if (tok >= T) return;
     const dn_half* qr = qx + p * q_stride + (int64_t)tok * SD_CI + h * 16;
     const float* pr = qpe + (int64_t)tok * SD_CI + h * 16;
-    const sd_h8 a = *reinterpret_cast<const sd_h8*>(qr), b = *reinterpret_cast<const sd_h8*>(qr + 8);
+    const vit_h8 a = *reinterpret_cast<const vit_h8*>(qr), b = *reinterpret_cast<const vit_h8*>(qr + 8);
     float qq[16];
 #pragma unroll
     for (int d = 0; d < 8; ++d) { qq[d] = (float)a[d] + pr[d]; qq[8 + d] = (float)b[d] + pr[8 + d]; }
@@ -305,7 +288,7 @@ __global__ void __launch_bounds__(256) sd_i2t_kernel(const dn_half* __restrict__
         s[j] = expf(s[j] - m);
         l += s[j];
     }
-    sd_h8 o[2];
+    vit_h8 o[2];
 #pragma unroll
     for (int d = 0; d < 16; ++d) {
         float acc = 0.f;
@@ -314,8 +297,8 @@ __global__ void __launch_bounds__(256) sd_i2t_kernel(const dn_half* __restrict__
         o[d >> 3][d & 7] = (dn_half)(acc / l);
     }
     dn_half* dst = ctx + (p * T + tok) * SD_CI + h * 16;
-    *reinterpret_cast<sd_h8*>(dst) = o[0];
-    *reinterpret_cast<sd_h8*>(dst + 8) = o[1];
+    *reinterpret_cast<vit_h8*>(dst) = o[0];
+    *reinterpret_cast<vit_h8*>(dst + 8) = o[1];
 }
 
 // x_out[row] = fp16(LayerNorm(fp32(x[row]) + a[row])): one wave per row of 256, a lane owns channels 4 lane .. 4 lane + 3;
@@ -328,33 +311,32 @@ __global__ void __launch_bounds__(256) sd_addnorm_kernel(const dn_half* x, const
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int64_t p = row / T, tok = row - p * T;
-    const sd_h4 xv = *reinterpret_cast<const sd_h4*>(x + p * x_stride + tok * SD_C + 4 * lane);
+    const vit_h4 xv = *reinterpret_cast<const vit_h4*>(x + p * x_stride + tok * SD_C + 4 * lane);
     const float4 av = *reinterpret_cast<const float4*>(a + row * SD_C + 4 * lane);
     float y[4] = {(float)xv[0] + av.x, (float)xv[1] + av.y, (float)xv[2] + av.z, (float)xv[3] + av.w};
-    const float mean = sd_wave_sum(((y[0] + y[1]) + y[2]) + y[3]) / (float)SD_C;
+    const float mean = wave_sum_f32(((y[0] + y[1]) + y[2]) + y[3]) / (float)SD_C;
     float var = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         y[e] = y[e] - mean;
         var += y[e] * y[e];
     }
-    const float rstd = 1.0f / sqrtf(sd_wave_sum(var) / (float)SD_C + eps);
-    sd_h4 o;
+    const float rstd = 1.0f / sqrtf(wave_sum_f32(var) / (float)SD_C + eps);
+    vit_h4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = (dn_half)(y[e] * rstd * (float)g[4 * lane + e] + (float)beta[4 * lane + e]);
-    *reinterpret_cast<sd_h4*>(x_out + row * SD_C + 4 * lane) = o;
+    *reinterpret_cast<vit_h4*>(x_out + row * SD_C + 4 * lane) = o;
 }
 
 // ctx fp16 [P T,128] and att f32 [P T,256] are the caller's
 static int sd_i2t(const dn_half* qx, const float* qpe, const float* k, const float* v, const dn_half* x, int P, int T, int shared,
                   const dn_half* ow, const dn_half* ob, const dn_half* lw, const dn_half* lb, dn_half* ctx, float* att, dn_half* x_out,
                   hipStream_t s) {
-    int rc;
     const int64_t rows = (int64_t)P * T;
     hipLaunchKernelGGL(sd_i2t_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)P), dim3(256), 0, s, qx, qpe, k, v, T,
                        shared ? (int64_t)0 : (int64_t)T * SD_CI, ctx);
     GSR_LAUNCH_CHECK();
-    if ((rc = dn_linear(ctx, ow, ob, nullptr, att, rows, SD_CI, SD_C, DN_EPI_F32, 1, 0, 0, s)) != GSR_OK) return rc;
+    GSR_TRY(dn_linear(ctx, ow, ob, nullptr, att, rows, SD_CI, SD_C, DN_EPI_F32, s));
     hipLaunchKernelGGL(sd_addnorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, att, rows, T,
                        shared ? (int64_t)0 : (int64_t)T * SD_C, lw, lb, SD_EPS, x_out);
     GSR_LAUNCH_CHECK();
@@ -381,8 +363,7 @@ extern "C" size_t gsr_sam_dec_i2t_workspace_bytes(int32_t P, int32_t T) {
 extern "C" int32_t gsr_sam_dec_i2t(const void* qx, const float* qpe, const float* k, const float* v, const void* x, int32_t P, int32_t T,
                                    int32_t shared, const void* out_w, const void* out_b, const void* ln_w, const void* ln_b, void* ws,
                                    size_t ws_bytes, void* x_out, gsr_stream_t stream_) {
-    int rc;
-    if ((rc = sd_check_points(P)) != GSR_OK) return rc;
+    GSR_TRY(sd_check_points(P));
     if (T < 1 || T > SD_MAX_GRID * SD_MAX_GRID) { gsr_set_error("sam dec i2t: T %d is outside 1 .. %d", T, SD_MAX_GRID * SD_MAX_GRID); return GSR_E_INVALID; }
     if (!qx || !qpe || !k || !v || !x || !out_w || !out_b || !ln_w || !ln_b || !x_out) {
         gsr_set_error("sam dec i2t: an input, a weight or x_out is null");
@@ -407,10 +388,10 @@ __global__ void __launch_bounds__(256) sd_up_norm_kernel(const float* __restrict
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float x = u[row * 64 + lane];
-    const float mean = sd_wave_sum(x) / 64.0f;
+    const float mean = wave_sum_f32(x) / 64.0f;
     const float d = x - mean;
-    const float rstd = 1.0f / sqrtf(sd_wave_sum(d * d) / 64.0f + SD_EPS);
-    y[row * 64 + lane] = (dn_half)sd_gelu(d * rstd * (float)g[lane] + (float)beta[lane]);
+    const float rstd = 1.0f / sqrtf(wave_sum_f32(d * d) / 64.0f + SD_EPS);
+    y[row * 64 + lane] = (dn_half)vit_gelu(d * rstd * (float)g[lane] + (float)beta[lane]);
 }
 
 // low_res[p][m][Y][X] = sum_c hyper[m][p][c] fp32(c2[((p T + t) 4 + tap1) 128 + tap2 32 + c]), c ascending, fmaf; t = (Y >> 2) g +
@@ -431,7 +412,7 @@ __global__ void __launch_bounds__(256) sd_mask_kernel(const dn_half* __restrict_
     float acc[3] = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const sd_h8 a = *reinterpret_cast<const sd_h8*>(src + 8 * q);
+        const vit_h8 a = *reinterpret_cast<const vit_h8*>(src + 8 * q);
 #pragma unroll
         for (int e = 0; e < 8; ++e)
 #pragma unroll
@@ -445,13 +426,12 @@ __global__ void __launch_bounds__(256) sd_mask_kernel(const dn_half* __restrict_
 static int sd_upscale(const dn_half* x, int g, int P, const dn_half* c1w, const dn_half* c1b, const dn_half* lw, const dn_half* lb,
                       const dn_half* c2w, const dn_half* c2b, const float* hyper, float* u32, dn_half* u16, float* low_res,
                       hipStream_t s) {
-    int rc;
     const int64_t rows = (int64_t)P * g * g;
-    if ((rc = dn_linear(x, c1w, c1b, nullptr, u32, rows, SD_C, SD_C, DN_EPI_F32, 1, 0, 0, s)) != GSR_OK) return rc;
+    GSR_TRY(dn_linear(x, c1w, c1b, nullptr, u32, rows, SD_C, SD_C, DN_EPI_F32, s));
     hipLaunchKernelGGL(sd_up_norm_kernel, dim3((unsigned)(rows)), dim3(256), 0, s, u32, rows * 4, lw, lb, u16);
     GSR_LAUNCH_CHECK();
     dn_half* c2 = reinterpret_cast<dn_half*>(u32);
-    if ((rc = dn_linear(u16, c2w, c2b, nullptr, c2, rows * 4, 64, 128, DN_EPI_GELU, 1, 0, 0, s)) != GSR_OK) return rc;
+    GSR_TRY(dn_linear(u16, c2w, c2b, nullptr, c2, rows * 4, 64, 128, DN_EPI_GELU, s));
     const int L = 4 * g;
     hipLaunchKernelGGL(sd_mask_kernel, dim3((unsigned)((L * L + 255) / 256), (unsigned)P), dim3(256), 0, s, c2, hyper, g, P, low_res);
     GSR_LAUNCH_CHECK();
@@ -478,8 +458,8 @@ extern "C" size_t gsr_sam_dec_upscale_workspace_bytes(int32_t g, int32_t P) {
 extern "C" int32_t gsr_sam_dec_upscale(const void* x, int32_t g, int32_t P, const void* conv1_w, const void* conv1_b, const void* ln_w,
                                        const void* ln_b, const void* conv2_w, const void* conv2_b, const float* hyper, void* ws,
                                        size_t ws_bytes, float* low_res, gsr_stream_t stream_) {
-    int rc;
-    if ((rc = sd_check_grid(g)) != GSR_OK || (rc = sd_check_points(P)) != GSR_OK) return rc;
+    GSR_TRY(sd_check_grid(g));
+    GSR_TRY(sd_check_points(P));
     if (!x || !conv1_w || !conv1_b || !ln_w || !ln_b || !conv2_w || !conv2_b || !hyper || !low_res) {
         gsr_set_error("sam dec upscale: x / a weight / hyper / low_res is null");
         return GSR_E_INVALID;
@@ -559,8 +539,8 @@ extern "C" size_t gsr_sam_decode_workspace_bytes(int32_t g, int32_t P) {
 extern "C" int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, int32_t n_weights, const float* emb, const float* pe,
                                   const float* points, int32_t P, int32_t image_size, void* ws, size_t ws_bytes, float* low_res,
                                   float* iou, gsr_stream_t stream_) {
-    int rc;
-    if ((rc = sd_check_grid(g)) != GSR_OK || (rc = sd_check_points(P)) != GSR_OK) return rc;
+    GSR_TRY(sd_check_grid(g));
+    GSR_TRY(sd_check_points(P));
     if (image_size != 16 * g) { gsr_set_error("sam decoder: image_size %d is not 16 x grid %d", image_size, g); return GSR_E_INVALID; }
     if (!weights_host || n_weights != GSR_SAMD_W_COUNT) {
         gsr_set_error("sam decoder: the weight table is null or has %d entries (%d are needed)", n_weights, (int)GSR_SAMD_W_COUNT);
@@ -578,9 +558,8 @@ extern "C" int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, in
     const int T = g * g;
     const int64_t R = (int64_t)P * SD_TOK, PT = (int64_t)P * T;
     auto W = [&](int i) { return static_cast<const dn_half*>(weights_host[i]); };
-#define SD_RC(call) do { if ((rc = (call)) != GSR_OK) return rc; } while (0)
     auto lin = [&](const dn_half* x, int wi, int bi, void* out, int64_t M, int K, int N, int epi) -> int {
-        return dn_linear(x, W(wi), bi < 0 ? nullptr : W(bi), nullptr, out, M, K, N, epi, 1, 0, 0, s);
+        return dn_linear(x, W(wi), bi < 0 ? nullptr : W(bi), nullptr, out, M, K, N, epi, s);
     };
     auto addcast = [&](const float* a, const float* b, dn_half* y) -> int {
         const int64_t n = R * SD_C;
@@ -601,7 +580,7 @@ extern "C" int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, in
     };
 
     // SD_PROMPT and the tokens
-    SD_RC(sd_prompt(points, P, image_size, static_cast<const float*>(weights_host[GSR_SAMD_W_GAUSS]), W(GSR_SAMD_W_POINT1),
+    GSR_TRY(sd_prompt(points, P, image_size, static_cast<const float*>(weights_host[GSR_SAMD_W_GAUSS]), W(GSR_SAMD_W_POINT1),
                     W(GSR_SAMD_W_NOT_A_POINT), lay.sparse, s));
     hipLaunchKernelGGL(sd_tokens_kernel, dim3((unsigned)P), dim3(256), 0, s, W(GSR_SAMD_W_IOU_TOKEN), W(GSR_SAMD_W_MASK_TOKENS), lay.sparse,
                        lay.tok0, q);
@@ -612,25 +591,24 @@ extern "C" int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, in
                        lay.PE16);
     GSR_LAUNCH_CHECK();
     const int l0 = GSR_SAMD_W_LAYER0, l1 = GSR_SAMD_W_LAYER0 + GSR_SAMD_W_PER_LAYER, fin = GSR_SAMD_W_FINAL;
-    SD_RC(lin(lay.PE16, l0 + GSR_SAMD_L_T2I + 2, l0 + GSR_SAMD_L_T2I + 3, lay.pe_proj[0], T, SD_C, SD_CI, DN_EPI_F32));
-    SD_RC(lin(lay.PE16, l0 + GSR_SAMD_L_I2T + 0, l0 + GSR_SAMD_L_I2T + 1, lay.pe_proj[1], T, SD_C, SD_CI, DN_EPI_F32));
-    SD_RC(lin(lay.PE16, l1 + GSR_SAMD_L_T2I + 2, l1 + GSR_SAMD_L_T2I + 3, lay.pe_proj[2], T, SD_C, SD_CI, DN_EPI_F32));
-    SD_RC(lin(lay.PE16, l1 + GSR_SAMD_L_I2T + 0, l1 + GSR_SAMD_L_I2T + 1, lay.pe_proj[3], T, SD_C, SD_CI, DN_EPI_F32));
-    SD_RC(lin(lay.PE16, fin + 2, fin + 3, lay.pe_proj[4], T, SD_C, SD_CI, DN_EPI_F32));
-    SD_RC(lin(lay.E16, l0 + GSR_SAMD_L_T2I + 2, -1, lay.kx0, T, SD_C, SD_CI, DN_EPI_BIAS));
-    SD_RC(lin(lay.E16, l0 + GSR_SAMD_L_T2I + 4, l0 + GSR_SAMD_L_T2I + 5, lay.v0, T, SD_C, SD_CI, DN_EPI_BIAS));
-    SD_RC(lin(lay.E16, l0 + GSR_SAMD_L_I2T + 0, -1, lay.qx0, T, SD_C, SD_CI, DN_EPI_BIAS));
+    GSR_TRY(lin(lay.PE16, l0 + GSR_SAMD_L_T2I + 2, l0 + GSR_SAMD_L_T2I + 3, lay.pe_proj[0], T, SD_C, SD_CI, DN_EPI_F32));
+    GSR_TRY(lin(lay.PE16, l0 + GSR_SAMD_L_I2T + 0, l0 + GSR_SAMD_L_I2T + 1, lay.pe_proj[1], T, SD_C, SD_CI, DN_EPI_F32));
+    GSR_TRY(lin(lay.PE16, l1 + GSR_SAMD_L_T2I + 2, l1 + GSR_SAMD_L_T2I + 3, lay.pe_proj[2], T, SD_C, SD_CI, DN_EPI_F32));
+    GSR_TRY(lin(lay.PE16, l1 + GSR_SAMD_L_I2T + 0, l1 + GSR_SAMD_L_I2T + 1, lay.pe_proj[3], T, SD_C, SD_CI, DN_EPI_F32));
+    GSR_TRY(lin(lay.PE16, fin + 2, fin + 3, lay.pe_proj[4], T, SD_C, SD_CI, DN_EPI_F32));
+    GSR_TRY(lin(lay.E16, l0 + GSR_SAMD_L_T2I + 2, -1, lay.kx0, T, SD_C, SD_CI, DN_EPI_BIAS));
+    GSR_TRY(lin(lay.E16, l0 + GSR_SAMD_L_T2I + 4, l0 + GSR_SAMD_L_T2I + 5, lay.v0, T, SD_C, SD_CI, DN_EPI_BIAS));
+    GSR_TRY(lin(lay.E16, l0 + GSR_SAMD_L_I2T + 0, -1, lay.qx0, T, SD_C, SD_CI, DN_EPI_BIAS));
 
     // token -> image attention with the weights at `a`: queries += out_proj(attention)
     auto t2i = [&](int a, int first, const float* kpe) -> int {
-        int r;
-        if ((r = addcast(q, lay.tok0, lay.h16)) != GSR_OK) return r;
-        if ((r = lin(lay.h16, a + 0, a + 1, lay.qf, R, SD_C, SD_CI, DN_EPI_F32)) != GSR_OK) return r;
+        GSR_TRY(addcast(q, lay.tok0, lay.h16));
+        GSR_TRY(lin(lay.h16, a + 0, a + 1, lay.qf, R, SD_C, SD_CI, DN_EPI_F32));
         if (!first) {
-            if ((r = lin(lay.x16, a + 2, -1, lay.b1, PT, SD_C, SD_CI, DN_EPI_BIAS)) != GSR_OK) return r;
-            if ((r = lin(lay.x16, a + 4, a + 5, lay.b2, PT, SD_C, SD_CI, DN_EPI_BIAS)) != GSR_OK) return r;
+            GSR_TRY(lin(lay.x16, a + 2, -1, lay.b1, PT, SD_C, SD_CI, DN_EPI_BIAS));
+            GSR_TRY(lin(lay.x16, a + 4, a + 5, lay.b2, PT, SD_C, SD_CI, DN_EPI_BIAS));
         }
-        if ((r = sd_t2i(lay.qf, first ? lay.kx0 : lay.b1, kpe, first ? lay.v0 : lay.b2, P, T, first, 0.25f, lay.c16, s)) != GSR_OK) return r;
+        GSR_TRY(sd_t2i(lay.qf, first ? lay.kx0 : lay.b1, kpe, first ? lay.v0 : lay.b2, P, T, first, 0.25f, lay.c16, s));
         return lin(lay.c16, a + 6, a + 7, q, R, SD_CI, SD_C, DN_EPI_RESID1);
     };
 
@@ -639,57 +617,56 @@ extern "C" int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, in
         // SD_TOKENS: self-attention
         const int sa = b + GSR_SAMD_L_SELF;
         if (l == 0) {
-            SD_RC(addcast(q, nullptr, lay.h16));
-            SD_RC(lin(lay.h16, sa + 4, sa + 5, lay.vf, R, SD_C, SD_C, DN_EPI_F32));
+            GSR_TRY(addcast(q, nullptr, lay.h16));
+            GSR_TRY(lin(lay.h16, sa + 4, sa + 5, lay.vf, R, SD_C, SD_C, DN_EPI_F32));
         } else {
-            SD_RC(addcast(q, lay.tok0, lay.h16));
-            SD_RC(addcast(q, nullptr, lay.h16b));
-            SD_RC(lin(lay.h16b, sa + 4, sa + 5, lay.vf, R, SD_C, SD_C, DN_EPI_F32));
+            GSR_TRY(addcast(q, lay.tok0, lay.h16));
+            GSR_TRY(addcast(q, nullptr, lay.h16b));
+            GSR_TRY(lin(lay.h16b, sa + 4, sa + 5, lay.vf, R, SD_C, SD_C, DN_EPI_F32));
         }
-        SD_RC(lin(lay.h16, sa + 0, sa + 1, lay.qf, R, SD_C, SD_C, DN_EPI_F32));
-        SD_RC(lin(lay.h16, sa + 2, sa + 3, lay.kf, R, SD_C, SD_C, DN_EPI_F32));
+        GSR_TRY(lin(lay.h16, sa + 0, sa + 1, lay.qf, R, SD_C, SD_C, DN_EPI_F32));
+        GSR_TRY(lin(lay.h16, sa + 2, sa + 3, lay.kf, R, SD_C, SD_C, DN_EPI_F32));
         hipLaunchKernelGGL(sd_self_attn_kernel, dim3((unsigned)P), dim3(64), 0, s, lay.qf, lay.kf, lay.vf, lay.c16);
         GSR_LAUNCH_CHECK();
-        SD_RC(lin(lay.c16, sa + 6, sa + 7, q, R, SD_C, SD_C, l == 0 ? DN_EPI_F32 : DN_EPI_RESID1));
-        SD_RC(norm(b + GSR_SAMD_L_NORM1, SD_EPS));
+        GSR_TRY(lin(lay.c16, sa + 6, sa + 7, q, R, SD_C, SD_C, l == 0 ? DN_EPI_F32 : DN_EPI_RESID1));
+        GSR_TRY(norm(b + GSR_SAMD_L_NORM1, SD_EPS));
         // SD_T2I
-        SD_RC(t2i(b + GSR_SAMD_L_T2I, l == 0, lay.pe_proj[2 * l]));
-        SD_RC(norm(b + GSR_SAMD_L_NORM2, SD_EPS));
+        GSR_TRY(t2i(b + GSR_SAMD_L_T2I, l == 0, lay.pe_proj[2 * l]));
+        GSR_TRY(norm(b + GSR_SAMD_L_NORM2, SD_EPS));
         // SD_TOKENS: MLP
-        SD_RC(addcast(q, nullptr, lay.h16));
-        SD_RC(lin(lay.h16, b + GSR_SAMD_L_MLP + 0, b + GSR_SAMD_L_MLP + 1, lay.m16, R, SD_C, SD_MLP, DN_EPI_BIAS));
-        SD_RC(relu(lay.m16, R * SD_MLP));
-        SD_RC(lin(lay.m16, b + GSR_SAMD_L_MLP + 2, b + GSR_SAMD_L_MLP + 3, q, R, SD_MLP, SD_C, DN_EPI_RESID1));
-        SD_RC(norm(b + GSR_SAMD_L_NORM3, SD_EPS));
+        GSR_TRY(addcast(q, nullptr, lay.h16));
+        GSR_TRY(lin(lay.h16, b + GSR_SAMD_L_MLP + 0, b + GSR_SAMD_L_MLP + 1, lay.m16, R, SD_C, SD_MLP, DN_EPI_BIAS));
+        GSR_TRY(relu(lay.m16, R * SD_MLP));
+        GSR_TRY(lin(lay.m16, b + GSR_SAMD_L_MLP + 2, b + GSR_SAMD_L_MLP + 3, q, R, SD_MLP, SD_C, DN_EPI_RESID1));
+        GSR_TRY(norm(b + GSR_SAMD_L_NORM3, SD_EPS));
         // SD_I2T
         const int it = b + GSR_SAMD_L_I2T;
-        SD_RC(addcast(q, lay.tok0, lay.h16));
-        SD_RC(addcast(q, nullptr, lay.h16b));
-        SD_RC(lin(lay.h16, it + 2, it + 3, lay.kf, R, SD_C, SD_CI, DN_EPI_F32));
-        SD_RC(lin(lay.h16b, it + 4, it + 5, lay.vf, R, SD_C, SD_CI, DN_EPI_F32));
-        if (l > 0) SD_RC(lin(lay.x16, it + 0, -1, lay.b1, PT, SD_C, SD_CI, DN_EPI_BIAS));
-        SD_RC(sd_i2t(l == 0 ? lay.qx0 : lay.b1, lay.pe_proj[2 * l + 1], lay.kf, lay.vf, l == 0 ? lay.E16 : lay.x16, P, T, l == 0, W(it + 6),
+        GSR_TRY(addcast(q, lay.tok0, lay.h16));
+        GSR_TRY(addcast(q, nullptr, lay.h16b));
+        GSR_TRY(lin(lay.h16, it + 2, it + 3, lay.kf, R, SD_C, SD_CI, DN_EPI_F32));
+        GSR_TRY(lin(lay.h16b, it + 4, it + 5, lay.vf, R, SD_C, SD_CI, DN_EPI_F32));
+        if (l > 0) GSR_TRY(lin(lay.x16, it + 0, -1, lay.b1, PT, SD_C, SD_CI, DN_EPI_BIAS));
+        GSR_TRY(sd_i2t(l == 0 ? lay.qx0 : lay.b1, lay.pe_proj[2 * l + 1], lay.kf, lay.vf, l == 0 ? lay.E16 : lay.x16, P, T, l == 0, W(it + 6),
                      W(it + 7), W(b + GSR_SAMD_L_NORM4), W(b + GSR_SAMD_L_NORM4 + 1), lay.b2, lay.a32, lay.x16, s));
     }
-    SD_RC(t2i(fin, 0, lay.pe_proj[4]));
-    SD_RC(norm(fin + 8, SD_EPS_FINAL));
+    GSR_TRY(t2i(fin, 0, lay.pe_proj[4]));
+    GSR_TRY(norm(fin + 8, SD_EPS_FINAL));
 
     // SD_HEADS
     hipLaunchKernelGGL(sd_heads_gather_kernel, dim3((unsigned)P), dim3(256), 0, s, q, P, lay.heads16);
     GSR_LAUNCH_CHECK();
     for (int k = 0; k < 4; ++k) {
         const int a = k == 0 ? GSR_SAMD_W_IOU : GSR_SAMD_W_HYPER + 6 * (k - 1);
-        SD_RC(lin(lay.heads16 + (int64_t)k * P * SD_C, a + 0, a + 1, lay.t16a, P, SD_C, SD_C, DN_EPI_BIAS));
-        SD_RC(relu(lay.t16a, (int64_t)P * SD_C));
-        SD_RC(lin(lay.t16a, a + 2, a + 3, lay.t16b, P, SD_C, SD_C, DN_EPI_BIAS));
-        SD_RC(relu(lay.t16b, (int64_t)P * SD_C));
+        GSR_TRY(lin(lay.heads16 + (int64_t)k * P * SD_C, a + 0, a + 1, lay.t16a, P, SD_C, SD_C, DN_EPI_BIAS));
+        GSR_TRY(relu(lay.t16a, (int64_t)P * SD_C));
+        GSR_TRY(lin(lay.t16a, a + 2, a + 3, lay.t16b, P, SD_C, SD_C, DN_EPI_BIAS));
+        GSR_TRY(relu(lay.t16b, (int64_t)P * SD_C));
         if (k == 0)     // rows 1..3 of the IoU head's last layer [4,256]: columns 1..3 of its output
-            SD_RC(dn_linear(lay.t16b, W(a + 4) + SD_C, W(a + 5) + 1, nullptr, iou, P, SD_C, 3, DN_EPI_F32, 1, 0, 0, s));
+            GSR_TRY(dn_linear(lay.t16b, W(a + 4) + SD_C, W(a + 5) + 1, nullptr, iou, P, SD_C, 3, DN_EPI_F32, s));
         else
-            SD_RC(lin(lay.t16b, a + 4, a + 5, lay.hyper + (int64_t)(k - 1) * P * 32, P, SD_C, 32, DN_EPI_F32));
+            GSR_TRY(lin(lay.t16b, a + 4, a + 5, lay.hyper + (int64_t)(k - 1) * P * 32, P, SD_C, 32, DN_EPI_F32));
     }
     // SD_UP
     const int up = GSR_SAMD_W_UP;
     return sd_upscale(lay.x16, g, P, W(up), W(up + 1), W(up + 2), W(up + 3), W(up + 4), W(up + 5), lay.hyper, lay.a32, lay.b1, low_res, s);
-#undef SD_RC
 }

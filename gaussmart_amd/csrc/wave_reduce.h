@@ -1,4 +1,5 @@
-// DPP-row (16-lane) reductions shared by the backward kernels, and whole-wave min / max (tsdf.hip, cloud_common.h) (gfx950 only).
+// DPP-row (16-lane) reductions shared by the backward kernels, and whole-wave min / max / sum (tsdf.hip, cloud_common.h, the ViT
+// kernels) (gfx950 only).
 #pragma once
 #include "gsr_common.h"
 
@@ -59,7 +60,7 @@ __device__ __forceinline__ float row_sum16_transposed(const float (&v)[16], int 
     const float keep = b0 ? p[1] : p[0], send = b0 ? p[0] : p[1];
     return keep + dpp_move<0xB1, 0xf>(send);   // bit 0: partner is lane ^ 1 (quad_perm [1,0,3,2])
 }
-// ---- whole-wave (64 lanes) min / max: every lane returns the wave's value ---------------------------------
+// ---- whole-wave (64 lanes) min / max / sum: every lane returns the wave's value; xor butterfly 32, 16, ..., 1 ----------
 __device__ __forceinline__ float wave_min_f32(float v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
@@ -68,6 +69,11 @@ __device__ __forceinline__ float wave_min_f32(float v) {
 __device__ __forceinline__ float wave_max_f32(float v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_sum_f32(float v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
     return v;
 }
 // Two values: on return lanes 0..7 of the row hold the row total of a, lanes 8..15 that of b.

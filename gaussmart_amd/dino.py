@@ -1,5 +1,5 @@
 """DINOv3 ViT image encoder on the device: the reference's DINOImageEncoder (identification/feature_extraction.py:18-43, a
-transformers DINOv3ViTModel in fp16) computed by the kernels of csrc/dino.hip (include/gsr.h: DN_EMBED, DN_NORM, DN_LINEAR,
+transformers DINOv3ViTModel in fp16) computed by the kernels of csrc/dino.hip and csrc/vit.hip (include/gsr.h: DN_EMBED, DN_NORM, DN_LINEAR,
 DN_ROPE, DN_ATTN, DN_POOL, DN_COS).
 
     from gaussmart_amd.dino import DINOImageEncoder, load_dino_weights

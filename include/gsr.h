@@ -1105,7 +1105,8 @@ int32_t gsr_frame_colormap(const float* x, int32_t H, int32_t W, const uint32_t*
 
 /* ---------------------------------------------------------------- DINOv3 ViT encoder
  * transformers' DINOv3ViTModel (models/dinov3_vit/modeling_dinov3_vit.py), which the reference's DINOImageEncoder runs in fp16
- * (identification/feature_extraction.py:18-43) for the cosine term of utils/loss_utils.py:77-97, as inference kernels (dino.hip;
+ * (identification/feature_extraction.py:18-43) for the cosine term of utils/loss_utils.py:77-97, as inference kernels (dino.hip,
+ * DN_LINEAR and DN_NORM in vit.hip;
  * Python: gaussmart_amd/dino.py).  head_dim is 64 and the patch 16 x 16; hidden = 64 heads, layers >= 1, intermediate a multiple
  * of 64, registers >= 0, B in 1..8, H, W >= 16 are run-time parameters.  EVERY weight is stored in fp16 (the reference's
  * .half()) and widened exactly where it is used in fp32.  Matrix products take fp16 operands on v_mfma_f32_32x32x16_f16 and

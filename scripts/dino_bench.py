@@ -1,4 +1,4 @@
-"""Time the DINOv3 ViT encoder on one GPU: the kernels of csrc/dino.hip stage by stage and as a whole, transformers' fp16
+"""Time the DINOv3 ViT encoder on one GPU: the kernels of csrc/dino.hip and csrc/vit.hip stage by stage and as a whole, transformers' fp16
 model with its default attention on the same GPU next to it, and the training step with the feature term off, on a side
 stream and on the training stream.
 

@@ -1,4 +1,4 @@
-"""The DINOv3 ViT kernels (csrc/dino.hip; include/gsr.h: DN_EMBED, DN_NORM, DN_LINEAR, DN_ROPE, DN_ATTN, DN_POOL, DN_COS) on
+"""The DINOv3 ViT kernels (csrc/dino.hip, csrc/vit.hip; include/gsr.h: DN_EMBED, DN_NORM, DN_LINEAR, DN_ROPE, DN_ATTN, DN_POOL, DN_COS) on
 the device, everything through the C ABI: each stage against fp64 from the same fp16 inputs with a bar that follows the
 roundings its rule states, the whole model against transformers' fp64 model with a bar measured on transformers' own fp16
 model, the bit-equalities the rules promise, the refusals, and train_cli with --dino_dir.  Weights, images, twins and the bar
