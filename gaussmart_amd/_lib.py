@@ -21,6 +21,8 @@ GSR_LPIPS_ALEX, GSR_LPIPS_VGG = 0, 1
 GSR_DINO_EPI_BIAS, GSR_DINO_EPI_GELU, GSR_DINO_EPI_RESID = 0, 1, 2
 GSR_DINO_W_LAYER0, GSR_DINO_W_PER_LAYER = 4, 18      # include/gsr.h: the weight table of gsr_dino_forward
 GSR_SAM_W_LAYER0, GSR_SAM_W_PER_LAYER, GSR_SAM_W_NECK = 3, 14, 6     # include/gsr.h: the weight table of gsr_sam_encode
+GSR_SAM2_EPI_RESID1, GSR_SAM2_EPI_F32 = 4, 5
+GSR_SAM2_W_BLOCK0, GSR_SAM2_W_PER_BLOCK, GSR_SAM2_W_NECK = 3, 14, 13     # include/gsr.h: the weight table of gsr_sam2_encode
 # include/gsr.h: the weight table of gsr_sam_decode (head, per two-way layer, final attention, up-scaling, hypernetworks, IoU head)
 GSR_SAMD_W_LAYER0, GSR_SAMD_W_PER_LAYER, GSR_SAMD_W_FINAL, GSR_SAMD_W_UP, GSR_SAMD_W_HYPER, GSR_SAMD_W_IOU, GSR_SAMD_W_COUNT = 6, 36, 78, 88, 94, 112, 118
 
@@ -107,6 +109,13 @@ class GsrSamConfig(C.Structure):
     _fields_ = [("hidden", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32), ("layers", C.c_int32),
                 ("mlp_dim", C.c_int32), ("output_channels", C.c_int32), ("image_size", C.c_int32), ("ln_eps", C.c_float),
                 ("window_host", C.POINTER(C.c_int32)), ("rel_rows_host", C.POINTER(C.c_int32))]
+
+
+class GsrSam2Config(C.Structure):
+    """include/gsr.h: the run-time shape of SAM2's Hiera encoder and FPN neck (gaussmart_amd/sam2.py); global_host is a host array."""
+    _fields_ = [("image_size", C.c_int32), ("fpn_hidden", C.c_int32), ("top_down_mask", C.c_int32), ("num_global", C.c_int32),
+                ("blocks", C.c_int32 * 4), ("dims", C.c_int32 * 4), ("heads", C.c_int32 * 4), ("windows", C.c_int32 * 4),
+                ("query_stride", C.c_int32 * 2), ("ln_eps", C.c_float), ("global_host", C.POINTER(C.c_int32))]
 
 
 class GsrDinoConfig(C.Structure):
@@ -383,7 +392,19 @@ def lib():
                 ("gsr_sam_dec_upscale", C.c_int32, [vp, C.c_int32, C.c_int32] + [vp] * 8 + [sz, vp, vp]),
                 ("gsr_sam_dec_num_weights", C.c_int32, []),
                 ("gsr_sam_decode_workspace_bytes", sz, [C.c_int32] * 2),
-                ("gsr_sam_decode", C.c_int32, [C.c_int32, C.POINTER(vp), C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, sz, vp, vp, vp])):
+                ("gsr_sam_decode", C.c_int32, [C.c_int32, C.POINTER(vp), C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, sz, vp, vp, vp]),
+                ("gsr_sam_mask_score_direct", C.c_int32, [vp] + [C.c_int32] * 4 + [C.c_float, C.c_float, vp, vp, vp, vp]),
+                ("gsr_sam_mask_emit_direct", C.c_int32, [vp] + [C.c_int32] * 4 + [C.c_float, vp, C.c_int32, vp, vp]),
+                ("gsr_sam2_embed_workspace_bytes", sz, [C.c_int32]),
+                ("gsr_sam2_embed", C.c_int32, [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, sz, vp, vp]),
+                ("gsr_sam2_linear", C.c_int32, [vp, vp, vp, vp, i64, C.c_int32, C.c_int32, C.c_int32, vp, vp]),
+                ("gsr_sam2_attn", C.c_int32, [vp] + [C.c_int32] * 5 + [vp, vp]),
+                ("gsr_sam2_pool", C.c_int32, [vp, C.c_int32, C.c_int32, vp, vp]),
+                ("gsr_sam2_neck_workspace_bytes", sz, [C.c_int32] * 3),
+                ("gsr_sam2_neck", C.c_int32, [C.POINTER(vp)] + [C.c_int32] * 4 + [C.POINTER(vp), vp, sz, vp, vp, vp, vp]),
+                ("gsr_sam2_workspace_bytes", sz, [C.POINTER(GsrSam2Config)]),
+                ("gsr_sam2_num_weights", C.c_int32, [C.c_int32]),
+                ("gsr_sam2_encode", C.c_int32, [C.POINTER(GsrSam2Config), C.POINTER(vp), C.c_int32, vp, vp, sz, vp, vp, vp, vp])):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]

@@ -408,6 +408,7 @@ extern "C" int32_t gsr_sam_encode(const GsrSamConfig* cfg, const void* const* we
 struct SmGeom {
     int L, ih, iw, oh, ow, identity;
     float sh, sw;       // fp32(ih) / fp32(oh), fp32(iw) / fp32(ow): F.interpolate's scale when a size is given
+    int direct;         // SAM2's one step: (L, L) -> (oh, ow) with ih = iw = L, the taps are the logits themselves
 };
 
 // F.interpolate(L -> 4 L, bilinear, align_corners=False) at pixel (Y, X): src = max(0.25 (Y + 0.5) - 0.5, 0), i0 = floor(src),
@@ -428,6 +429,7 @@ __device__ __forceinline__ float sm_value(const float* __restrict__ p, const SmG
     const int y0 = min((int)sy, G.ih - 1), x0 = min((int)sx, G.iw - 1);
     const int y1 = y0 + (y0 < G.ih - 1), x1 = x0 + (x0 < G.iw - 1);
     const float ly = sy - (float)y0, lx = sx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
+    if (G.direct) return hy * (hx * p[y0 * G.L + x0] + lx * p[y0 * G.L + x1]) + ly * (hx * p[y1 * G.L + x0] + lx * p[y1 * G.L + x1]);
     return hy * (hx * sm_up(p, G.L, y0, x0) + lx * sm_up(p, G.L, y0, x1)) + ly * (hx * sm_up(p, G.L, y1, x0) + lx * sm_up(p, G.L, y1, x1));
 }
 
@@ -510,14 +512,20 @@ static int sm_geom(int L, int ih, int iw, int oh, int ow, SmGeom* G) {
     G->identity = oh == ih && ow == iw;
     G->sh = (float)ih / (float)oh;
     G->sw = (float)iw / (float)ow;
+    G->direct = 0;
     return GSR_OK;
 }
 
-extern "C" int32_t gsr_sam_mask_score(const float* logits, int32_t n, int32_t L, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
-                                      float tau, float delta, const uint8_t* skip, int32_t* counts, float* boxes,
-                                      gsr_stream_t stream_) {
-    SmGeom G;
-    GSR_TRY(sm_geom(L, ih, iw, oh, ow, &G));
+// SAM2's postprocess_masks: one F.interpolate from the L x L logits to the mask size
+static int sm_geom_direct(int L, int oh, int ow, SmGeom* G) {
+    GSR_TRY(sm_geom(L, L, L, oh, ow, G));
+    G->identity = 0;
+    G->direct = 1;
+    return GSR_OK;
+}
+
+static int sm_score(const SmGeom& G, const float* logits, int32_t n, float tau, float delta, const uint8_t* skip, int32_t* counts,
+                    float* boxes, gsr_stream_t stream_) {
     if (n < 0) { gsr_set_error("sam mask score: n %d must be >= 0", n); return GSR_E_INVALID; }
     if (!(delta >= 0.f) || !(tau == tau)) { gsr_set_error("sam mask score: tau must be a number and delta >= 0"); return GSR_E_INVALID; }
     if (n == 0) return GSR_OK;
@@ -528,10 +536,24 @@ extern "C" int32_t gsr_sam_mask_score(const float* logits, int32_t n, int32_t L,
     return GSR_OK;
 }
 
-extern "C" int32_t gsr_sam_mask_emit(const float* logits, int32_t n, int32_t L, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
-                                     float tau, const int32_t* index, int32_t m, uint8_t* out, gsr_stream_t stream_) {
+extern "C" int32_t gsr_sam_mask_score(const float* logits, int32_t n, int32_t L, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
+                                      float tau, float delta, const uint8_t* skip, int32_t* counts, float* boxes,
+                                      gsr_stream_t stream_) {
     SmGeom G;
     GSR_TRY(sm_geom(L, ih, iw, oh, ow, &G));
+    return sm_score(G, logits, n, tau, delta, skip, counts, boxes, stream_);
+}
+
+extern "C" int32_t gsr_sam_mask_score_direct(const float* logits, int32_t n, int32_t L, int32_t oh, int32_t ow, float tau, float delta,
+                                             const uint8_t* skip, int32_t* counts, float* boxes, gsr_stream_t stream_) {
+    SmGeom G;
+    GSR_TRY(sm_geom_direct(L, oh, ow, &G));
+    return sm_score(G, logits, n, tau, delta, skip, counts, boxes, stream_);
+}
+
+static int sm_emit(const SmGeom& G, const float* logits, int32_t n, float tau, const int32_t* index, int32_t m, uint8_t* out,
+                   gsr_stream_t stream_) {
+    const int oh = G.oh, ow = G.ow;
     if (n < 0 || m < 0 || m > 65535) { gsr_set_error("sam mask emit: n %d must be >= 0 and m %d in 0 .. 65535", n, m); return GSR_E_INVALID; }
     if (m == 0) return GSR_OK;
     if (!logits || !index || !out) { gsr_set_error("sam mask emit: logits / index / out is null"); return GSR_E_INVALID; }
@@ -539,6 +561,20 @@ extern "C" int32_t gsr_sam_mask_emit(const float* logits, int32_t n, int32_t L, 
                        logits, index, n, G, tau, out);
     GSR_LAUNCH_CHECK();
     return GSR_OK;
+}
+
+extern "C" int32_t gsr_sam_mask_emit(const float* logits, int32_t n, int32_t L, int32_t ih, int32_t iw, int32_t oh, int32_t ow,
+                                     float tau, const int32_t* index, int32_t m, uint8_t* out, gsr_stream_t stream_) {
+    SmGeom G;
+    GSR_TRY(sm_geom(L, ih, iw, oh, ow, &G));
+    return sm_emit(G, logits, n, tau, index, m, out, stream_);
+}
+
+extern "C" int32_t gsr_sam_mask_emit_direct(const float* logits, int32_t n, int32_t L, int32_t oh, int32_t ow, float tau,
+                                            const int32_t* index, int32_t m, uint8_t* out, gsr_stream_t stream_) {
+    SmGeom G;
+    GSR_TRY(sm_geom_direct(L, oh, ow, &G));
+    return sm_emit(G, logits, n, tau, index, m, out, stream_);
 }
 
 // ---------------------------------------------------------------- SM_NMS

@@ -55,11 +55,13 @@ extern "C" int32_t gsr_dino_norm(const float* x, int64_t rows, int32_t hidden, i
 // (lane l: 8 consecutive k of row l & 31, k = 8 (l >> 5) + j).  A workgroup of 4 waves owns 128 rows x 128 columns, a wave
 // 2 x 2 tiles of 32 x 32; K (a multiple of 64) goes through LDS in chunks of 64 with the next chunk's global loads issued
 // before the chunk's 64 matrix instructions.  Rows past M and columns past N are loaded as zeros and not written.
+// TAIL (HV_LINEAR, K a multiple of 8 that is no multiple of 64): the 16-byte loads past K give zeros too, so the last chunk adds
+// exact zeros to the chain.  K a multiple of 64 never takes the TAIL kernels: its code and its bits are what they were.
 #define DN_BM 128
 #define DN_KC 64
 #define DN_LD 72        // halves per LDS row: 144 bytes, 16-byte aligned, consecutive rows 4 banks apart
 
-template <int EPI>
+template <int EPI, bool TAIL>
 __global__ void __launch_bounds__(256) dn_linear_kernel(const dn_half* __restrict__ x, const dn_half* __restrict__ w,
                                                         const dn_half* __restrict__ bias, const dn_half* __restrict__ lam,
                                                         void* __restrict__ out_, int64_t M, int K, int N, int64_t Np, int T,
@@ -77,8 +79,9 @@ __global__ void __launch_bounds__(256) dn_linear_kernel(const dn_half* __restric
         for (int i = 0; i < 4; ++i) {
             const int64_t m = m0 + lr + 32 * i;
             const int n = n0 + lr + 32 * i;
-            ra[i] = m < M ? *reinterpret_cast<const uint4*>(x + m * K + k0 + 8 * lc) : make_uint4(0, 0, 0, 0);
-            rb[i] = n < N ? *reinterpret_cast<const uint4*>(w + (int64_t)n * K + k0 + 8 * lc) : make_uint4(0, 0, 0, 0);
+            const bool kin = !TAIL || k0 + 8 * lc < K;
+            ra[i] = m < M && kin ? *reinterpret_cast<const uint4*>(x + m * K + k0 + 8 * lc) : make_uint4(0, 0, 0, 0);
+            rb[i] = n < N && kin ? *reinterpret_cast<const uint4*>(w + (int64_t)n * K + k0 + 8 * lc) : make_uint4(0, 0, 0, 0);
         }
     };
     auto store = [&]() {
@@ -153,12 +156,9 @@ __global__ void __launch_bounds__(256) dn_linear_kernel(const dn_half* __restric
     }
 }
 
-int dn_linear(const dn_half* x, const dn_half* w, const dn_half* bias, const dn_half* lam, void* out, int64_t M, int K, int N,
-              int epi, hipStream_t s, DnEmbedRows embed) {
-    if (M < 1 || K < 64 || N < 1 || K % 64 != 0) {
-        gsr_set_error("dino linear: M %lld and N %d must be >= 1 and K %d a positive multiple of 64", (long long)M, N, K);
-        return GSR_E_INVALID;
-    }
+// the checks that DN_LINEAR and HV_LINEAR share, and the launch; K is checked by the two callers
+static int dn_linear_launch(const dn_half* x, const dn_half* w, const dn_half* bias, const dn_half* lam, void* out, int64_t M, int K,
+                            int N, int epi, hipStream_t s, DnEmbedRows embed) {
     if (!x || !w || !out) { gsr_set_error("dino linear: x / w / out is null"); return GSR_E_INVALID; }
     if ((epi == DN_EPI_RESID || epi == DN_EPI_POS) && !lam) { gsr_set_error("dino linear: the residual epilogue needs lambda"); return GSR_E_INVALID; }
     if ((M + DN_BM - 1) / DN_BM > 0x7fffffffLL || (N + DN_BM - 1) / DN_BM > 65535) {
@@ -166,8 +166,12 @@ int dn_linear(const dn_half* x, const dn_half* w, const dn_half* bias, const dn_
         return GSR_E_UNSUPPORTED;
     }
     const dim3 grid((unsigned)((M + DN_BM - 1) / DN_BM), (unsigned)((N + DN_BM - 1) / DN_BM));
-#define DN_LINEAR_LAUNCH(E) \
-    hipLaunchKernelGGL((dn_linear_kernel<E>), grid, dim3(256), 0, s, x, w, bias, lam, out, M, K, N, embed.Np, embed.T, embed.prefix)
+    const bool tail = K % DN_KC != 0;
+#define DN_LINEAR_LAUNCH(E)                                                                                                              \
+    do {                                                                                                                                 \
+        if (tail) hipLaunchKernelGGL((dn_linear_kernel<E, true>), grid, dim3(256), 0, s, x, w, bias, lam, out, M, K, N, embed.Np, embed.T, embed.prefix); \
+        else hipLaunchKernelGGL((dn_linear_kernel<E, false>), grid, dim3(256), 0, s, x, w, bias, lam, out, M, K, N, embed.Np, embed.T, embed.prefix);     \
+    } while (0)
     switch (epi) {
     case DN_EPI_BIAS: DN_LINEAR_LAUNCH(DN_EPI_BIAS); break;
     case DN_EPI_GELU: DN_LINEAR_LAUNCH(DN_EPI_GELU); break;
@@ -181,6 +185,25 @@ int dn_linear(const dn_half* x, const dn_half* w, const dn_half* bias, const dn_
 #undef DN_LINEAR_LAUNCH
     GSR_LAUNCH_CHECK();
     return GSR_OK;
+}
+
+int dn_linear(const dn_half* x, const dn_half* w, const dn_half* bias, const dn_half* lam, void* out, int64_t M, int K, int N,
+              int epi, hipStream_t s, DnEmbedRows embed) {
+    if (M < 1 || K < 64 || N < 1 || K % 64 != 0) {
+        gsr_set_error("dino linear: M %lld and N %d must be >= 1 and K %d a positive multiple of 64", (long long)M, N, K);
+        return GSR_E_INVALID;
+    }
+    return dn_linear_launch(x, w, bias, lam, out, M, K, N, epi, s, embed);
+}
+
+// HV_LINEAR: DN_LINEAR for any K that is a multiple of 8 (a row of 8 halves is one 16-byte load)
+int dn_linear_k8(const dn_half* x, const dn_half* w, const dn_half* bias, const dn_half* lam, void* out, int64_t M, int K, int N,
+                 int epi, hipStream_t s) {
+    if (M < 1 || K < 8 || N < 1 || K % 8 != 0) {
+        gsr_set_error("sam2 linear: M %lld and N %d must be >= 1 and K %d a positive multiple of 8", (long long)M, N, K);
+        return GSR_E_INVALID;
+    }
+    return dn_linear_launch(x, w, bias, lam, out, M, K, N, epi, s, {1, 0, 0});
 }
 
 extern "C" int32_t gsr_dino_linear(const void* x, const void* w, const void* bias, const void* lambda, int64_t M, int32_t K,

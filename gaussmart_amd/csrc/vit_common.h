@@ -38,6 +38,9 @@ struct DnEmbedRows {
 
 int dn_linear(const dn_half* x, const dn_half* w, const dn_half* bias, const dn_half* lam, void* out, int64_t M, int K, int N,
               int epi, hipStream_t s, DnEmbedRows embed = {1, 0, 0});
+// HV_LINEAR (sam2.hip): the same product for any K that is a multiple of 8; K a multiple of 64 runs DN_LINEAR's own kernels
+int dn_linear_k8(const dn_half* x, const dn_half* w, const dn_half* bias, const dn_half* lam, void* out, int64_t M, int K, int N,
+                 int epi, hipStream_t s);
 int dn_norm(const float* x, int64_t rows, int hidden, int64_t in_stride, const dn_half* g, const dn_half* b, float eps, void* y,
             int out_f32, hipStream_t s);
 

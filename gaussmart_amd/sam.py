@@ -16,8 +16,8 @@ What differs from the reference, on purpose:
   * the encoder's weights are fp16 and its matrix products take fp16 operands with fp32 accumulation; the residual stream,
     the LayerNorm statistics and the softmax are fp32.  The reference runs the encoder in fp32.
   * DEVIATION: the first resize (long side <= 1024) is cv2.INTER_LINEAR in the reference and PIL's bilinear here.
-  * one full-image crop only: no crop layers, no min_mask_region_area, no SAM2.  The crop-edge filter of the reference never
-    fires for the single full-image crop and is left out.
+  * one full-image crop only: no crop layers, no min_mask_region_area.  The crop-edge filter of the reference never fires
+    for the single full-image crop and is left out.  SAM2 (the reference's sam2=True) is gaussmart_amd/sam2.py.
 `sam_host`, `decode_host`, `select_host` and `nms_host` are the torch twins (any device): they back `host=True` and the tests.
 """
 import ctypes as C
@@ -538,10 +538,13 @@ def nms_host(boxes, scores, keep_in, theta):
     return torch.tensor(kept, dtype=torch.int64, device=boxes.device)
 
 
-def upsample_host(logits, input_size, mask_size, dtype=None):
+def upsample_host(logits, input_size, mask_size, dtype=None, direct=False):
     """[n,L,L] -> [n,oh,ow]: F.interpolate(L -> 4 L), the crop to input_size, F.interpolate to mask_size (bilinear,
-    align_corners=False), in `dtype` (default: the logits' own)."""
+    align_corners=False), in `dtype` (default: the logits' own).  direct: SAM2's one F.interpolate from L x L to mask_size
+    (input_size is not read)."""
     x = logits.to(dtype or logits.dtype)[:, None]
+    if direct:
+        return F.interpolate(x, tuple(mask_size), mode="bilinear", align_corners=False)[:, 0]
     S = 4 * logits.shape[-1]
     x = F.interpolate(x, (S, S), mode="bilinear", align_corners=False)[..., :input_size[0], :input_size[1]]
     return F.interpolate(x, tuple(mask_size), mode="bilinear", align_corners=False)[:, 0]
@@ -563,8 +566,9 @@ def mask_stats_host(values, tau=MASK_THRESHOLD, delta=1.0):
 
 
 def select_host(low_res, iou, input_size, mask_size, pred_iou_thresh=0.86, stability_score_thresh=0.92, stability_score_offset=1.0,
-                box_nms_thresh=0.7, dtype=None, chunk=64):
-    """SamMaskGenerator.select in torch (any device): the same gates in the same order on up-sampled planes."""
+                box_nms_thresh=0.7, dtype=None, chunk=64, direct=False):
+    """SamMaskGenerator.select in torch (any device): the same gates in the same order on up-sampled planes.  direct: SAM2's
+    one-step resampling (Sam2MaskGenerator.select)."""
     L = low_res.shape[-1]
     logits, scores = low_res.reshape(-1, L, L), iou.reshape(-1).to(torch.float32)
     n = logits.shape[0]
@@ -573,14 +577,14 @@ def select_host(low_res, iou, input_size, mask_size, pred_iou_thresh=0.86, stabi
     boxes = torch.zeros(n, 4, dtype=torch.float32, device=logits.device)
     todo = torch.nonzero(first).reshape(-1)
     for part in todo.split(chunk):
-        a, i, u, b = mask_stats_host(upsample_host(logits[part], input_size, mask_size, dtype), MASK_THRESHOLD, stability_score_offset)
+        a, i, u, b = mask_stats_host(upsample_host(logits[part], input_size, mask_size, dtype, direct), MASK_THRESHOLD, stability_score_offset)
         area[part], inter[part], union[part], boxes[part] = a, i, u, b
     stab = inter.to(torch.float32) / union.to(torch.float32)
     keep_in = first & (stab >= stability_score_thresh)            # 0 / 0 is NaN and fails
     index = nms_host(boxes, scores, keep_in, box_nms_thresh)
     masks = torch.zeros(len(index), *mask_size, dtype=torch.uint8, device=logits.device)
     for part in torch.arange(len(index), device=logits.device).split(chunk):
-        masks[part] = (upsample_host(logits[index[part]], input_size, mask_size, dtype) > MASK_THRESHOLD).to(torch.uint8)
+        masks[part] = (upsample_host(logits[index[part]], input_size, mask_size, dtype, direct) > MASK_THRESHOLD).to(torch.uint8)
     return dict(masks=masks, index=index, area=area[index], boxes=boxes[index], predicted_iou=scores[index],
                 stability_score=stab[index], keep_in=keep_in, stability_all=stab)
 

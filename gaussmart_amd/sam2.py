@@ -1,0 +1,532 @@
+"""SAM2 automatic mask generation on the device: the reference's SAMSegmentation(sam2=True).process_image
+(identification/sam.py: SAM2AutomaticMaskGenerator(sam2-hiera-large, points_per_side=32, pred_iou_thresh=0.86,
+stability_score_thresh=0.92)) with the image encoder (the Hiera trunk, the FPN neck and the three maps the mask decoder reads)
+computed by the kernels of csrc/sam2.hip (include/gsr.h: HV_EMBED, HV_LINEAR, HV_ATTN, HV_POOL, HV_NECK) and the mask selection
+by SM_SCORE / SM_NMS / SM_EMIT with SAM2's one-step resampling.  The prompt encoder and the mask decoder are transformers' own
+torch modules, run on the device in fp32 as they are.
+
+    from gaussmart_amd.sam2 import Sam2MaskGenerator, load_sam2_weights
+    gen = Sam2MaskGenerator(load_sam2_weights("/models/sam2-hiera-large"))     # a LOCAL directory, see load_sam2_weights
+    masks = gen.generate(image_u8)                    # the reference's list of dicts, in NMS order
+
+What differs from the reference, on purpose:
+  * nothing is fetched: `load_sam2_weights` takes a LOCAL directory under Sam2Model's names.  The original .pt layout is not read.
+  * the encoder's weights are fp16 and its matrix products take fp16 operands with fp32 accumulation; the residual stream, the
+    LayerNorm statistics and the softmax are fp32.  The reference runs the encoder in fp32.
+  * DEVIATION: the first resize (long side <= 1024) is cv2.INTER_LINEAR in the reference and PIL's bilinear here.
+  * DEVIATION: SAM2's transform resizes to S x S with torchvision's antialiased bilinear resize; this uses PIL's bilinear.
+  * one full-image crop only, no crop layers, no min_mask_region_area, and the object-score head is ignored, as SAM2's
+    generator ignores it.
+  * a stage whose grid is not a multiple of its window is refused (Hiera pads such windows).  sam2-hiera-large's windows
+    (8, 4, 16, 8) divide its grids at 1024 x 1024; the (8, 4, 14, 7) of the tiny, small and base-plus checkpoints do not.
+  * decoder="hip" is not built: SAM2's decoder has a fourth mask token, an object-score token and the two high-resolution
+    skips, which csrc/sam_decoder.hip does not have.
+`sam2_host`, `decode_host2` and `sam.select_host(direct=True)` are the torch twins (any device): they back `host=True` and the
+tests."""
+import ctypes as C
+import json
+import math
+import os
+import re
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+from . import sam as S1
+from ._dev import ptr, stream, workspace
+
+IMAGE_MEAN = (0.485, 0.456, 0.406)
+IMAGE_STD = (0.229, 0.224, 0.225)
+HEAD_DIMS = (56, 64, 72, 80, 96)            # what HV_ATTN is built for
+PATCH_K, PATCH_K_PADDED = 147, 152          # 3 x 7 x 7, padded to a multiple of 8 for HV_LINEAR
+VISION, BACKBONE = "vision_encoder.", "vision_encoder.backbone."
+NO_MEMORY = "no_memory_embedding"
+CONV_S = ("mask_decoder.conv_s0.weight", "mask_decoder.conv_s0.bias", "mask_decoder.conv_s1.weight", "mask_decoder.conv_s1.bias")
+TIED = ("prompt_encoder.shared_embedding.positional_embedding", "shared_image_embedding.positional_embedding")
+# the keys of a video checkpoint that transformers' Sam2Model itself ignores (Sam2PreTrainedModel._keys_to_ignore_on_load_unexpected)
+IGNORED = (r"^memory_.*", r"^mask_downsample.*", r"^object_pointer_proj.*", r"^temporal_positional_encoding_projection_layer.*",
+           "no_memory_positional_encoding", "no_object_pointer", "occlusion_spatial_embedding_parameter")
+
+# the weight table of gsr_sam2_encode, in the order of include/gsr.h
+ENC_BLOCK = ("layer_norm1.weight", "layer_norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias",
+             "layer_norm2.weight", "layer_norm2.bias", "mlp.proj_in.weight", "mlp.proj_in.bias", "mlp.proj_out.weight", "mlp.proj_out.bias",
+             "proj.weight", "proj.bias")
+assert len(ENC_BLOCK) == _lib.GSR_SAM2_W_PER_BLOCK
+
+
+@dataclass
+class Sam2Config:
+    """Defaults: sam2-hiera-large, what the reference loads."""
+    embed_dim: int = 144
+    num_heads: int = 2
+    blocks_per_stage: tuple = (2, 6, 36, 4)
+    global_attention_blocks: tuple = (23, 33, 43)
+    window_size_per_stage: tuple = (8, 4, 16, 8)
+    background_size: tuple = (7, 7)
+    fpn_hidden_size: int = 256
+    fpn_top_down_levels: tuple = (2, 3)
+    image_size: int = 1024
+    query_stride: tuple = (2, 2)
+    layer_norm_eps: float = 1e-6
+
+    @classmethod
+    def preset(cls, model_type):
+        """large is read off transformers' defaults and the reference; tiny, small and base_plus are recalled (a checkpoint's own
+        config.json always decides).  Their windows (8, 4, 14, 7) do not divide the grids at 1024: the encoder refuses them."""
+        if model_type == "large":
+            return cls()
+        small = dict(embed_dim=96, num_heads=1, window_size_per_stage=(8, 4, 14, 7))
+        if model_type == "tiny":
+            return cls(blocks_per_stage=(1, 2, 7, 2), global_attention_blocks=(5, 7, 9), **small)
+        if model_type == "small":
+            return cls(blocks_per_stage=(1, 2, 11, 2), global_attention_blocks=(7, 10, 13), **small)
+        if model_type == "base_plus":
+            return cls(embed_dim=112, num_heads=2, blocks_per_stage=(2, 3, 16, 3), global_attention_blocks=(12, 16, 20),
+                       window_size_per_stage=(8, 4, 14, 7), background_size=(14, 14))
+        raise ValueError(f"sam2: model_type {model_type!r} is not large, base_plus, small or tiny")
+
+    def dims(self):
+        return [self.embed_dim << i for i in range(len(self.blocks_per_stage))]
+
+    def heads(self):
+        return [self.num_heads << i for i in range(len(self.blocks_per_stage))]
+
+    def grids(self):
+        return [(self.image_size // 4) >> i for i in range(len(self.blocks_per_stage))]
+
+    @property
+    def head_dim(self):
+        return self.embed_dim // max(1, self.num_heads)
+
+    @property
+    def total_blocks(self):
+        return sum(self.blocks_per_stage)
+
+    def block_plan(self):
+        """Per block: (stage, stage start, grid the attention runs on, window (0: global), query stride)."""
+        plan, grids, k = [], self.grids(), 0
+        for i, n in enumerate(self.blocks_per_stage):
+            for b in range(n):
+                start = i > 0 and b == 0
+                glob = k in tuple(self.global_attention_blocks)
+                win = 0 if glob else self.window_size_per_stage[i - 1 if start else i]
+                plan.append((i, start, grids[i - 1] if start else grids[i], win, 2 if start else 1))
+                k += 1
+        return plan
+
+    def check(self):
+        """What gsr_sam2_encode refuses, with the same reasons, before any weight is touched."""
+        if len(self.blocks_per_stage) != 4 or len(self.window_size_per_stage) != 4:
+            raise ValueError(f"sam2: {len(self.blocks_per_stage)} stages are not built (4 are)")
+        if tuple(self.query_stride) != (2, 2):
+            raise ValueError(f"sam2: query stride {tuple(self.query_stride)} is not built ((2, 2) is)")
+        if self.embed_dim % max(1, self.num_heads) != 0 or self.num_heads < 1:
+            raise ValueError(f"sam2: embed_dim {self.embed_dim} is not a multiple of its {self.num_heads} heads")
+        if self.head_dim not in HEAD_DIMS:
+            raise NotImplementedError(f"sam2: head_dim {self.head_dim} is not built ({HEAD_DIMS} are)")
+        S = self.image_size
+        if S < 32 or S % 32 != 0 or S > 1024:
+            raise ValueError(f"sam2: image_size {S} must be a multiple of 32 in 32 .. 1024")
+        if (S // 4) % self.window_size_per_stage[0] != 0:
+            raise ValueError(f"sam2: the first grid {S // 4} is not a multiple of the window {self.window_size_per_stage[0]} of the position table")
+        if self.fpn_hidden_size < 64 or self.fpn_hidden_size % 64 != 0:
+            raise ValueError(f"sam2: fpn_hidden_size {self.fpn_hidden_size} must be a positive multiple of 64")
+        if any(not 0 <= l <= 3 for l in self.fpn_top_down_levels):
+            raise ValueError(f"sam2: fpn_top_down_levels {tuple(self.fpn_top_down_levels)} must lie in 0 .. 3")
+        if any(n < 1 for n in self.blocks_per_stage):
+            raise ValueError(f"sam2: every stage needs a block, got {tuple(self.blocks_per_stage)}")
+        if self.layer_norm_eps != 1e-6:
+            raise ValueError(f"sam2: layer_norm_eps {self.layer_norm_eps} is not 1e-6")
+        for k, (i, start, g, win, stride) in enumerate(self.block_plan()):
+            if start and win == 0:
+                raise ValueError(f"sam2: block {k} is global and the first of stage {i}: a global block cannot pool its queries")
+            s = win or g
+            if s < 1 or s > g or g % s != 0:
+                raise ValueError(f"sam2: block {k}: the grid {g} is not a multiple of the window {s}")
+            if s % stride != 0:
+                raise ValueError(f"sam2: block {k}: the window {s} is not a multiple of the query stride {stride}")
+        return self
+
+    def to_hf(self):
+        from transformers import Sam2Config as HfSam2
+        from transformers.models.sam2.configuration_sam2 import (Sam2HieraDetConfig, Sam2VisionConfig, Sam2PromptEncoderConfig,
+                                                                  Sam2MaskDecoderConfig)
+        S, dims, grids = self.image_size, self.dims(), self.grids()
+        backbone = Sam2HieraDetConfig(hidden_size=self.embed_dim, num_attention_heads=self.num_heads, image_size=[S, S],
+                                      query_stride=list(self.query_stride), blocks_per_stage=list(self.blocks_per_stage),
+                                      window_positional_embedding_background_size=list(self.background_size),
+                                      embed_dim_per_stage=dims, num_attention_heads_per_stage=self.heads(),
+                                      window_size_per_stage=list(self.window_size_per_stage),
+                                      global_attention_blocks=list(self.global_attention_blocks), layer_norm_eps=self.layer_norm_eps)
+        vision = Sam2VisionConfig(backbone_config=backbone, backbone_channel_list=dims[::-1],
+                                  backbone_feature_sizes=[[g, g] for g in grids[:3]], fpn_hidden_size=self.fpn_hidden_size,
+                                  fpn_top_down_levels=list(self.fpn_top_down_levels), layer_norm_eps=self.layer_norm_eps)
+        hf = HfSam2(vision_config=vision, prompt_encoder_config=Sam2PromptEncoderConfig(hidden_size=self.fpn_hidden_size, image_size=S),
+                    mask_decoder_config=Sam2MaskDecoderConfig(hidden_size=self.fpn_hidden_size))
+        for c in (hf, hf.vision_config, hf.vision_config.backbone_config, hf.mask_decoder_config):
+            c._attn_implementation = "eager"
+        return hf
+
+    def to_json(self):
+        S = self.image_size
+        return {"model_type": "sam2", "vision_config": {
+            "model_type": "sam2_vision_model", "fpn_hidden_size": self.fpn_hidden_size, "fpn_top_down_levels": list(self.fpn_top_down_levels),
+            "backbone_channel_list": self.dims()[::-1], "backbone_feature_sizes": [[g, g] for g in self.grids()[:3]],
+            "backbone_config": {
+                "model_type": "sam2_hiera_det_model", "hidden_size": self.embed_dim, "num_attention_heads": self.num_heads,
+                "image_size": [S, S], "query_stride": list(self.query_stride), "blocks_per_stage": list(self.blocks_per_stage),
+                "window_positional_embedding_background_size": list(self.background_size), "embed_dim_per_stage": self.dims(),
+                "num_attention_heads_per_stage": self.heads(), "window_size_per_stage": list(self.window_size_per_stage),
+                "global_attention_blocks": list(self.global_attention_blocks), "layer_norm_eps": self.layer_norm_eps,
+                "patch_kernel_size": [7, 7], "patch_stride": [4, 4], "patch_padding": [3, 3], "mlp_ratio": 4.0}}}
+
+    @classmethod
+    def from_json(cls, d):
+        v = d.get("vision_config", d)
+        b = v.get("backbone_config", {})
+        for key, want in (("patch_kernel_size", [7, 7]), ("patch_stride", [4, 4]), ("patch_padding", [3, 3])):
+            if list(b.get(key, want)) != want:
+                raise NotImplementedError(f"sam2: {key} {b[key]} is not built ({want} is)")
+        if float(b.get("mlp_ratio", 4.0)) != 4.0:
+            raise NotImplementedError(f"sam2: mlp_ratio {b['mlp_ratio']} is not built (4 is)")
+        size = b.get("image_size", [1024, 1024])
+        size = [size, size] if isinstance(size, int) else list(size)
+        if size[0] != size[1]:
+            raise NotImplementedError(f"sam2: image_size {size} is not square")
+        embed, heads = int(b.get("hidden_size", 96)), int(b.get("num_attention_heads", 1))
+        blocks = tuple(b.get("blocks_per_stage", (1, 2, 7, 2)))
+        cfg = cls(embed_dim=embed, num_heads=heads, blocks_per_stage=blocks,
+                  global_attention_blocks=tuple(b.get("global_attention_blocks", (5, 7, 9))),
+                  window_size_per_stage=tuple(b.get("window_size_per_stage", (8, 4, 14, 7))),
+                  background_size=tuple(b.get("window_positional_embedding_background_size", (7, 7))),
+                  fpn_hidden_size=int(v.get("fpn_hidden_size", 256)), fpn_top_down_levels=tuple(v.get("fpn_top_down_levels", (2, 3))),
+                  image_size=int(size[0]), query_stride=tuple(b.get("query_stride", (2, 2))), layer_norm_eps=float(b.get("layer_norm_eps", 1e-6)))
+        if list(b.get("embed_dim_per_stage", cfg.dims())) != cfg.dims():
+            raise ValueError(f"sam2: embed_dim_per_stage {b['embed_dim_per_stage']}: a stage does not double its width")
+        if list(b.get("num_attention_heads_per_stage", cfg.heads())) != cfg.heads():
+            raise NotImplementedError(f"sam2: num_attention_heads_per_stage {b['num_attention_heads_per_stage']}: the heads do not double per stage")
+        if int(b.get("num_query_pool_stages", 3)) != 3:
+            raise NotImplementedError("sam2: only three query-pool stages are built")
+        return cfg
+
+
+def _shapes(config):
+    """name -> shape of transformers' Sam2Model.state_dict() for this configuration (built on the meta device)."""
+    from transformers import Sam2Model
+    with torch.device("meta"):
+        sd = Sam2Model(config.to_hf()).state_dict()
+    return {k: tuple(v.shape) for k, v in sd.items()}
+
+
+def position_table(pos_embed, pos_embed_window, g):
+    """HV_EMBED's table, fp16 [g,g,embed]: Sam2HieraDetModel._get_pos_embed in fp32, rounded once."""
+    pe = F.interpolate(pos_embed.to(torch.float32), size=(g, g), mode="bicubic")
+    win = pos_embed_window.to(torch.float32)
+    pe = pe + win.tile([x // y for x, y in zip(pe.shape, win.shape)])
+    return pe.permute(0, 2, 3, 1)[0].to(torch.float16).contiguous()
+
+
+class Sam2Weights:
+    """config + the tensors under Sam2Model.state_dict()'s names: what the kernels read (the vision encoder and the mask
+    decoder's conv_s0 / conv_s1) in fp16; the prompt encoder, the rest of the mask decoder, no_memory_embedding and the
+    shared positional matrix in fp32."""
+
+    def __init__(self, config, tensors):
+        self.config, self.tensors = config.check(), {}
+        tensors = {k: v for k, v in dict(tensors).items() if not any(re.search(p, k) for p in IGNORED)}
+        for a, b in (TIED, TIED[::-1]):
+            if a not in tensors and b in tensors:
+                tensors[a] = tensors[b]
+        want = _shapes(config)
+        unknown = sorted(set(tensors) - set(want))
+        if unknown:
+            raise KeyError(f"sam2 weights: {len(unknown)} tensors have no place, e.g. {unknown[:3]}")
+        missing = sorted(set(want) - set(tensors))
+        if missing:
+            raise KeyError(f"sam2 weights: {len(missing)} tensors are not filled, e.g. {missing[:3]}")
+        for k, shape in want.items():
+            t = tensors[k].detach()
+            if tuple(t.shape) != shape:
+                raise ValueError(f"sam2 weights: {k} must be {list(shape)}, got {list(t.shape)}")
+            self.tensors[k] = t.to(torch.float16 if k.startswith(VISION) or k in CONV_S else torch.float32).contiguous()
+
+    def to(self, device):
+        w = Sam2Weights.__new__(Sam2Weights)
+        w.config = self.config
+        w.tensors = {k: t.to(device) for k, t in self.tensors.items()}
+        return w
+
+    def table(self):
+        """The tensors of gsr_sam2_encode's weight table, in its order (None: the projection of a block that starts no
+        stage), on the tensors' device: the patch weight as [embed,152], HV_EMBED's position table, and the neck's
+        convolutions by stage."""
+        cfg, t = self.config, self.tensors
+        pw = t[BACKBONE + "patch_embed.projection.weight"].reshape(cfg.embed_dim, PATCH_K)
+        out = [F.pad(pw, (0, PATCH_K_PADDED - PATCH_K)).contiguous(), t[BACKBONE + "patch_embed.projection.bias"],
+               position_table(t[BACKBONE + "pos_embed"], t[BACKBONE + "pos_embed_window"], cfg.image_size // 4)]
+        for b in range(cfg.total_blocks):
+            out += [t.get(f"{BACKBONE}blocks.{b}.{k}") for k in ENC_BLOCK]
+        n = len(cfg.blocks_per_stage) - 1
+        for i in range(n + 1):                       # convs[n - i] takes stage i
+            w = t[f"{VISION}neck.convs.{n - i}.weight"]
+            out += [w.reshape(w.shape[0], w.shape[1]).contiguous(), t[f"{VISION}neck.convs.{n - i}.bias"]]
+        for k in CONV_S:
+            out.append(t[k].reshape(t[k].shape[0], -1).contiguous() if k.endswith("weight") else t[k])
+        out.append(t[NO_MEMORY].to(torch.float32).reshape(-1).contiguous())
+        assert len(out) == _lib.GSR_SAM2_W_BLOCK0 + _lib.GSR_SAM2_W_PER_BLOCK * cfg.total_blocks + _lib.GSR_SAM2_W_NECK
+        return out
+
+    def sub(self, prefix):
+        """The tensors under `prefix`, with it removed (a sub-module's state dict), in fp32."""
+        return {k[len(prefix):]: t.to(torch.float32) for k, t in self.tensors.items() if k.startswith(prefix)}
+
+
+def load_sam2_weights(path):
+    """A LOCAL directory with config.json and model.safetensors under Sam2Model's names.  Nothing here opens a URL.  The
+    video-memory keys that transformers itself ignores are dropped; any other key without a place, and any key left unfilled,
+    raises."""
+    path = os.fspath(path)
+    if not os.path.isdir(path):
+        raise FileNotFoundError(f"sam2: {path!r} is not a local directory with config.json and model.safetensors.  The weights are "
+                                "never downloaded, and the original .pt layout is not read")
+    with open(os.path.join(path, "config.json")) as f:
+        cfg = Sam2Config.from_json(json.load(f))
+    from safetensors.torch import load_file
+    return Sam2Weights(cfg, load_file(os.path.join(path, "model.safetensors"), device="cpu"))
+
+
+def save_sam2_weights(weights, directory):
+    """Writes what load_sam2_weights reads (config.json, model.safetensors)."""
+    from safetensors.torch import save_file
+    os.makedirs(directory, exist_ok=True)
+    with open(os.path.join(directory, "config.json"), "w") as f:
+        json.dump(weights.config.to_json(), f, indent=1)
+    save_file({k: t.cpu().clone().contiguous() for k, t in weights.tensors.items() if k != TIED[0]},
+              os.path.join(directory, "model.safetensors"))
+
+
+def random_sam2_weights(config=None, seed=0):
+    """Seeded stand-ins by random_sam_weights' recipe: linear, convolution and patch weights N(0, 1/fan_in), both position
+    tables, no_memory_embedding, the embeddings and the tokens N(0, 1), LayerNorm gains U(0.5, 1.5), biases N(0, 0.1^2),
+    everything rounded to fp16.  (Default initialisation zeroes the position tables and no_memory_embedding.)"""
+    cfg = config or Sam2Config()
+    g = torch.Generator().manual_seed(seed)
+    tensors = {}
+    for name, shape in _shapes(cfg).items():
+        if name == TIED[0]:
+            continue
+        if "pos_embed" in name or name.endswith("positional_embedding") or name == NO_MEMORY or len(shape) == 2 and shape[0] <= 8 and "embed" in name \
+                or name.endswith("_token.weight") or name.endswith("_tokens.weight"):
+            t = torch.randn(shape, generator=g)
+        elif "norm" in name and name.endswith(".weight"):
+            t = 0.5 + torch.rand(shape, generator=g)
+        elif name.endswith(".bias"):
+            t = 0.1 * torch.randn(shape, generator=g)
+        else:
+            t = torch.randn(shape, generator=g) / math.sqrt(math.prod(shape[1:]))
+        tensors[name] = t.to(torch.float16)
+    return Sam2Weights(cfg, tensors)
+
+
+# ---------------------------------------------------------------- the twins
+def host_model(weights, dtype=torch.float64, device="cpu"):
+    """transformers' Sam2Model holding these tensors, in `dtype` on `device`, in eval mode."""
+    from transformers import Sam2Model
+    model = Sam2Model(weights.config.to_hf())
+    model.load_state_dict(weights.sub(""), strict=True)
+    return model.to(device=device, dtype=dtype).eval()
+
+
+@torch.no_grad()
+def sam2_host(weights, pixel_values, dtype=torch.float64, device=None, model=None):
+    """pixel_values [3,S,S] through transformers' Sam2Model.get_image_embeddings (Sam2VisionModel, conv_s0 / conv_s1,
+    + no_memory_embedding): the three maps [D/8,g0,g0], [D/4,g1,g1], [D,g2,g2]."""
+    device = pixel_values.device if device is None else device
+    model = host_model(weights, dtype, device) if model is None else model
+    x = pixel_values.reshape(1, 3, *pixel_values.shape[-2:]).to(device=device, dtype=dtype)
+    return [m[0] for m in model.get_image_embeddings(x)]
+
+
+def host_decoder2(weights, dtype=torch.float32, device="cpu"):
+    """(Sam2PromptEncoder, Sam2MaskDecoder, wide [1,D,g,g]) holding these tensors, in `dtype` on `device`, in eval mode; wide is
+    Sam2Model.get_image_wide_positional_embeddings()."""
+    from transformers.models.sam2.modeling_sam2 import Sam2PromptEncoder, Sam2MaskDecoder, Sam2PositionalEmbedding
+    hf = weights.config.to_hf()
+    prompt, decoder, shared = (Sam2PromptEncoder(hf.prompt_encoder_config), Sam2MaskDecoder(hf.mask_decoder_config),
+                               Sam2PositionalEmbedding(hf.prompt_encoder_config))
+    prompt.load_state_dict(weights.sub("prompt_encoder."), strict=True)
+    decoder.load_state_dict(weights.sub("mask_decoder."), strict=True)
+    shared.load_state_dict(weights.sub("shared_image_embedding."), strict=True)
+    prompt, decoder, shared = (m.to(device=device, dtype=dtype).eval() for m in (prompt, decoder, shared))
+    g = weights.config.image_size // 16
+    c = (torch.arange(g, device=device, dtype=dtype) + 0.5) / g
+    with torch.no_grad():
+        wide = shared(torch.stack([c[None, :].expand(g, g), c[:, None].expand(g, g)], -1)).permute(2, 0, 1)[None]
+    return prompt, decoder, wide
+
+
+@torch.no_grad()
+def decode_host2(weights, maps, points, dtype=torch.float32, device=None, modules=None, points_per_batch=64):
+    """transformers' prompt encoder and mask decoder as they are: maps = the encoder's three maps, points [P,2] (x, y) in the
+    S x S frame, one foreground point per prompt, multimask output -> (low_res [P,3,4g,4g], iou [P,3]) in `dtype` (masks and
+    IoU columns 1..3; the object score is ignored)."""
+    device = maps[2].device if device is None else torch.device(device)
+    prompt, decoder, wide = host_decoder2(weights, dtype, device) if modules is None else modules
+    maps = [m.reshape(1, *m.shape[-3:]).to(device=device, dtype=dtype) for m in maps]
+    low, iou = [], []
+    for part in points.to(device=device, dtype=dtype).split(points_per_batch):
+        labels = torch.ones(1, part.shape[0], 1, dtype=torch.int64, device=device)
+        sparse, dense = prompt(part[None, :, None, :], labels, None, None)
+        m, q, _, _ = decoder(image_embeddings=maps[2], image_positional_embeddings=wide, sparse_prompt_embeddings=sparse.to(dtype),
+                             dense_prompt_embeddings=dense, multimask_output=True, high_resolution_features=maps[:2])
+        low.append(m[0])
+        iou.append(q[0])
+    return torch.cat(low).contiguous(), torch.cat(iou).contiguous()
+
+
+# ---------------------------------------------------------------- the encoder
+class Sam2ImageEncoder:
+    """encode(pixel_values f32 [3,S,S] on the device) -> the three f32 maps [D/8,S/4,S/4], [D/4,S/8,S/8], [D,S/16,S/16], on the
+    kernels."""
+
+    def __init__(self, weights):
+        self.weights, self.config = weights, weights.config
+        self._on = {}
+
+    def _device(self, dev):
+        hit = self._on.get(dev)
+        if hit is None:
+            cfg = self.config
+            tensors = self.weights.to(dev).table()
+            table = (C.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+            glob = (C.c_int32 * max(1, len(cfg.global_attention_blocks)))(*cfg.global_attention_blocks)
+            i4 = C.c_int32 * 4
+            c = _lib.GsrSam2Config(cfg.image_size, cfg.fpn_hidden_size, sum(1 << int(l) for l in set(cfg.fpn_top_down_levels)),
+                                   len(cfg.global_attention_blocks), i4(*cfg.blocks_per_stage), i4(*cfg.dims()), i4(*cfg.heads()),
+                                   i4(*cfg.window_size_per_stage), (C.c_int32 * 2)(*cfg.query_stride), cfg.layer_norm_eps, glob)
+            nbytes = _lib.lib().gsr_sam2_workspace_bytes(C.byref(c))
+            hit = self._on[dev] = dict(tensors=tensors, table=table, n=len(tensors), cfg=c, keep=glob, nbytes=nbytes,
+                                       ws=workspace(nbytes, dev) if nbytes else None)
+        return hit
+
+    @torch.no_grad()
+    def encode(self, pixel_values):
+        if not isinstance(pixel_values, torch.Tensor) or not pixel_values.is_cuda:
+            raise _lib.GsrError("sam2: pixel_values must live on the device (no CPU path; see sam2_host)")
+        S, cfg = self.config.image_size, self.config
+        x = pixel_values.detach().reshape(-1, S, S) if pixel_values.numel() == 3 * S * S else pixel_values
+        if tuple(x.shape) != (3, S, S):
+            raise ValueError(f"sam2: expected [3,{S},{S}], got {list(pixel_values.shape)}")
+        x = x.to(torch.float32).contiguous()
+        dev = x.device
+        d = self._device(dev)
+        D, g = cfg.fpn_hidden_size, cfg.grids()
+        outs = [torch.empty(ch, gi, gi, dtype=torch.float32, device=dev) for ch, gi in ((D // 8, g[0]), (D // 4, g[1]), (D, g[2]))]
+        _lib.check(_lib.lib().gsr_sam2_encode(C.byref(d["cfg"]), d["table"], d["n"], ptr(x), ptr(d["ws"]), d["nbytes"], ptr(outs[0]),
+                                              ptr(outs[1]), ptr(outs[2]), stream(dev)))
+        return outs
+
+
+def preprocess2(image_u8, image_size=1024):
+    """HxWx3 uint8 -> (pixel_values f32 [3,S,S] on the host, input_size (S, S), mask_size (oh, ow)).  The reference's resize to
+    a long side <= 1024 (mask_size is that picture's size, which the masks come out at), then SAM2's transform: a resize to
+    S x S that ignores the aspect ratio, / 255, the ImageNet mean and std.  No padding."""
+    from PIL import Image
+    img = Image.fromarray(np.ascontiguousarray(image_u8, np.uint8)[..., :3])
+    w, h = img.size
+    if max(h, w) > S1.MAX_SIDE:
+        scale = S1.MAX_SIDE / max(h, w)
+        img = img.resize((int(w * scale), int(h * scale)), Image.BILINEAR)
+    ow, oh = img.size
+    if (oh, ow) != (image_size, image_size):
+        img = img.resize((image_size, image_size), Image.BILINEAR)
+    x = torch.from_numpy(np.asarray(img, np.uint8).copy()).permute(2, 0, 1).to(torch.float32) / 255.0
+    x = (x - torch.tensor(IMAGE_MEAN).view(3, 1, 1)) / torch.tensor(IMAGE_STD).view(3, 1, 1)
+    return x.contiguous(), (image_size, image_size), (oh, ow)
+
+
+# ---------------------------------------------------------------- the generator
+class Sam2MaskGenerator(S1.SamMaskGenerator):
+    """The reference's SAM2AutomaticMaskGenerator for one full-image crop, with SamMaskGenerator's interface.  host=True: the
+    encoder through transformers' Sam2Model in fp32 and the selection through sam.select_host(direct=True), on the same device."""
+
+    def __init__(self, weights, points_per_side=32, points_per_batch=64, pred_iou_thresh=0.86, stability_score_thresh=0.92,
+                 stability_score_offset=1.0, box_nms_thresh=0.7, host=False, device="cuda", decoder="torch"):
+        if decoder == "hip":
+            raise NotImplementedError("sam2: decoder='hip' is not built: SAM2's mask decoder has a fourth mask token, an object-score "
+                                      "token and the two high-resolution skips (conv_s0 / conv_s1), which csrc/sam_decoder.hip lacks")
+        if decoder != "torch":
+            raise ValueError(f"sam2: decoder {decoder!r} is not 'torch'")
+        self.weights, self.config, self.device, self.host = weights, weights.config, torch.device(device), bool(host)
+        self.decoder = decoder
+        self.points_per_side, self.points_per_batch = int(points_per_side), int(points_per_batch)
+        self.pred_iou_thresh, self.stability_score_thresh = float(pred_iou_thresh), float(stability_score_thresh)
+        self.stability_score_offset, self.box_nms_thresh = float(stability_score_offset), float(box_nms_thresh)
+        self.encoder = None if host else Sam2ImageEncoder(weights)
+        self._host_model = self._modules = None
+        self.last_ms = {}
+
+    def _decoder(self):
+        if self._modules is None:
+            self._modules = host_decoder2(self.weights, torch.float32, self.device)
+        return self._modules
+
+    @torch.no_grad()
+    def embed(self, image):
+        """HxWx3 uint8 -> dict(emb: the three f32 maps on the device, input_size (S, S), mask_size)."""
+        x, input_size, mask_size = preprocess2(image, self.config.image_size)
+        x = x.to(self.device)
+        if self.host:
+            if self._host_model is None:
+                self._host_model = host_model(self.weights, torch.float32, self.device)
+            emb = sam2_host(self.weights, x, torch.float32, self.device, self._host_model)
+        else:
+            emb = self.encoder.encode(x)
+        return dict(emb=[m.to(torch.float32) for m in emb], input_size=input_size, mask_size=mask_size)
+
+    @torch.no_grad()
+    def decode(self, emb, points):
+        """emb: the three maps, points f32 [P,2] (x, y) in the S x S frame -> (low_res f32 [P,3,L,L], iou f32 [P,3]):
+        transformers' modules in fp32, points_per_batch at a time."""
+        low, iou = decode_host2(self.weights, emb, points, torch.float32, self.device, self._decoder(), self.points_per_batch)
+        return low.to(torch.float32).contiguous(), iou.to(torch.float32).contiguous()
+
+    @torch.no_grad()
+    def select(self, low_res, iou, input_size, mask_size):
+        """SamMaskGenerator.select's gates in the same order, on planes resampled in ONE step from the L x L logits to
+        mask_size (SAM2's postprocess_masks); input_size is not read."""
+        args = (self.pred_iou_thresh, self.stability_score_thresh, self.stability_score_offset, self.box_nms_thresh)
+        if self.host:
+            return S1.select_host(low_res, iou, input_size, mask_size, *args, direct=True)
+        if not low_res.is_cuda:
+            raise _lib.GsrError("sam2: select needs device tensors (no CPU path; see sam.select_host(direct=True))")
+        dev, Lr = low_res.device, int(low_res.shape[-1])
+        logits = low_res.reshape(-1, Lr, Lr).to(torch.float32).contiguous()
+        scores = iou.reshape(-1).to(torch.float32).contiguous()
+        n = logits.shape[0]
+        oh, ow = mask_size
+        L = _lib.lib()
+        first = scores > self.pred_iou_thresh
+        skip = (~first).to(torch.uint8)
+        counts = torch.empty(n, 3, dtype=torch.int32, device=dev)
+        boxes = torch.empty(n, 4, dtype=torch.float32, device=dev)
+        _lib.check(L.gsr_sam_mask_score_direct(ptr(logits), n, Lr, oh, ow, S1.MASK_THRESHOLD, self.stability_score_offset, ptr(skip),
+                                               ptr(counts), ptr(boxes), stream(dev)))
+        stab = counts[:, 1].to(torch.float32) / counts[:, 2].to(torch.float32)
+        keep_in = (first & (stab >= self.stability_score_thresh)).to(torch.uint8)
+        kept = torch.empty(n, dtype=torch.int32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        nbytes = L.gsr_sam_nms_workspace_bytes(n)
+        ws = workspace(nbytes, dev)
+        _lib.check(L.gsr_sam_nms(ptr(boxes), ptr(scores), ptr(keep_in), n, self.box_nms_thresh, ptr(ws), nbytes, ptr(kept), ptr(count),
+                                 stream(dev)))
+        m = int(count.item())           # the one synchronisation
+        index = kept[:m].contiguous()
+        masks = torch.empty(m, oh, ow, dtype=torch.uint8, device=dev)
+        _lib.check(L.gsr_sam_mask_emit_direct(ptr(logits), n, Lr, oh, ow, S1.MASK_THRESHOLD, ptr(index), m, ptr(masks), stream(dev)))
+        idx = index.to(torch.int64)
+        return dict(masks=masks, index=idx, area=counts[idx, 0].to(torch.int64), boxes=boxes[idx], predicted_iou=scores[idx],
+                    stability_score=stab[idx], keep_in=keep_in.to(torch.bool), stability_all=stab)

@@ -2,6 +2,7 @@
 
     python -m gaussmart_amd.sam_cli -s SCAN -o OUT --views i j k ... --sam_checkpoint FILE_OR_DIR [--model_type vit_h|vit_l|vit_b] [--host]
         [--decoder torch|hip]
+    python -m gaussmart_amd.sam_cli --sam2 -s SCAN -o OUT --views ... --sam_checkpoint DIR [--model_type large|base_plus|small|tiny] [--host]
         [--points_per_side 32] [--pred_iou_thresh 0.86] [--stability_score_thresh 0.92]      (the reference's values)
 
 View i is the i-th file of sorted(listdir(SCAN/images)).  Writes OUT/segments/masks/segments_NNN.npz (keys masks, boxes,
@@ -11,7 +12,10 @@ LOCAL .pth under segment_anything's names or a LOCAL directory under transformer
 nothing is downloaded.  --host runs transformers' encoder in fp32 and the torch selection on the same device.  --decoder hip
 runs the prompt encoder and the mask decoder on the kernels of csrc/sam_decoder.hip (fp16 operands); torch, the default, runs
 transformers' modules in fp32.
-Not built: SAM2 (--sam2), crop layers, min_mask_region_area, and the camera clustering that picks the views (step 1).
+--sam2 is the reference's --sam2 branch (SAM2AutomaticMaskGenerator on sam2-hiera-large): the Hiera encoder and its neck on
+the kernels of csrc/sam2.hip, the same files and JSON lines.  Its --sam_checkpoint is a LOCAL directory under transformers'
+Sam2Model names (gaussmart_amd.sam2.load_sam2_weights); its decoder is transformers' (--decoder hip is refused).
+Not built: crop layers, min_mask_region_area, and the camera clustering that picks the views (step 1).
 """
 import argparse
 import json
@@ -30,8 +34,9 @@ def main(argv=None):
     ap.add_argument("-o", "--output_path", required=True)
     ap.add_argument("--views", type=int, nargs="+", required=True, help="indices into sorted(listdir(SCAN/images))")
     ap.add_argument("--sam_checkpoint", required=True, help="a local .pth (segment_anything) or directory (transformers)")
-    ap.add_argument("--model_type", choices=("vit_h", "vit_l", "vit_b"), default=None,
-                    help="checked against the checkpoint's own shape when given")
+    ap.add_argument("--sam2", action="store_true", help="SAM2 (Hiera) instead of SAM; --sam_checkpoint is then a local directory")
+    ap.add_argument("--model_type", choices=("vit_h", "vit_l", "vit_b", "large", "base_plus", "small", "tiny"), default=None,
+                    help="checked against the checkpoint's own shape when given (vit_*: SAM; the others: --sam2)")
     ap.add_argument("--host", action="store_true", help="transformers' encoder in fp32 and the torch selection")
     ap.add_argument("--decoder", choices=("torch", "hip"), default="torch", help="the prompt encoder and mask decoder: transformers' or the kernels")
     ap.add_argument("--device", default="cuda")
@@ -50,15 +55,34 @@ def main(argv=None):
     if bad:
         print(f"sam_cli: views {bad} are outside the {len(files)} images of {image_dir}", file=sys.stderr)
         raise SystemExit(2)
-    weights = S.load_sam_weights(args.sam_checkpoint)
-    if args.model_type is not None:
+    if args.model_type is not None and (args.model_type in ("vit_h", "vit_l", "vit_b")) == args.sam2:
+        print(f"sam_cli: --model_type {args.model_type} does not go with {'--sam2' if args.sam2 else 'SAM (no --sam2)'}", file=sys.stderr)
+        raise SystemExit(2)
+    if args.sam2:
+        from . import sam2 as S2
+        weights = S2.load_sam2_weights(args.sam_checkpoint)
+        if args.model_type is not None:
+            want, have = S2.Sam2Config.preset(args.model_type), weights.config
+            if (want.embed_dim, want.num_heads, tuple(want.blocks_per_stage)) != (have.embed_dim, have.num_heads, tuple(have.blocks_per_stage)):
+                print(f"sam_cli: {args.sam_checkpoint} is not a {args.model_type} (embed {have.embed_dim}, blocks {tuple(have.blocks_per_stage)})",
+                      file=sys.stderr)
+                raise SystemExit(2)
+        gen = S2.Sam2MaskGenerator(weights, points_per_side=args.points_per_side, pred_iou_thresh=args.pred_iou_thresh,
+                                   stability_score_thresh=args.stability_score_thresh, host=args.host, device=args.device,
+                                   decoder=args.decoder)
+        mask_size = lambda image: S2.preprocess2(image, weights.config.image_size)[2]
+    else:
+        weights = S.load_sam_weights(args.sam_checkpoint)
+        mask_size = lambda image: S.preprocess(image, weights.config.image_size)[2]
+    if args.model_type is not None and not args.sam2:
         want, have = S.SamConfig.preset(args.model_type), weights.config
         if (want.hidden_size, want.num_hidden_layers, want.num_attention_heads) != (have.hidden_size, have.num_hidden_layers, have.num_attention_heads):
             print(f"sam_cli: {args.sam_checkpoint} is not a {args.model_type} (hidden {have.hidden_size}, {have.num_hidden_layers} layers)",
                   file=sys.stderr)
             raise SystemExit(2)
-    gen = S.SamMaskGenerator(weights, points_per_side=args.points_per_side, pred_iou_thresh=args.pred_iou_thresh,
-                             stability_score_thresh=args.stability_score_thresh, host=args.host, device=args.device, decoder=args.decoder)
+    if not args.sam2:
+        gen = S.SamMaskGenerator(weights, points_per_side=args.points_per_side, pred_iou_thresh=args.pred_iou_thresh,
+                                 stability_score_thresh=args.stability_score_thresh, host=args.host, device=args.device, decoder=args.decoder)
     mask_dir = os.path.join(args.output_path, "segments", "masks")
     copy_dir = os.path.join(args.output_path, "segments", "images")
     os.makedirs(mask_dir, exist_ok=True)
@@ -71,7 +95,7 @@ def main(argv=None):
         if masks:
             S.save_segments_boxes(masks, out)
         else:               # the layout of an empty view: [0,h,w] masks
-            e = S.preprocess(image, weights.config.image_size)[2]
+            e = mask_size(image)
             np.savez(out, masks=np.zeros((0, *e), bool), boxes=np.zeros((0, 4), np.int64), areas=np.zeros((0,), np.int64))
         shutil.copy(path, os.path.join(copy_dir, files[i]))
         print(json.dumps({"view": i, "image": files[i], "masks": len(masks), "host": bool(args.host), "decoder": args.decoder,

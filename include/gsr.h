@@ -49,8 +49,9 @@ extern "C" {
                                 16: frame kernels of the trajectory and viewer pictures (gsr_frame_*);
                                 17: DINOv3 ViT encoder and its cosine term (GsrDinoConfig, gsr_dino_*);
                                 18: SAM image encoder and mask selection (GsrSamConfig, gsr_sam_*); still 18 with SAM's
-                                    prompt encoder and mask decoder (gsr_sam_dec_*, gsr_sam_decode): additions only, no
-                                    existing struct or signature changed */
+                                    prompt encoder and mask decoder (gsr_sam_dec_*, gsr_sam_decode) and with SAM2's image
+                                    encoder (GsrSam2Config, gsr_sam2_*): additions only, no existing struct or signature
+                                    changed */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -1252,6 +1253,10 @@ int32_t gsr_dino_cosine(const float* a, const float* b, int32_t n, float lambda1
  *              and their count, on the device.
  *   SM_EMIT    for index[m] (mask numbers; outside 0..n-1: a zero plane) the > tau set as uint8 [m,oh,ow], from the same
  *              device function as SM_SCORE: a pixel SM_SCORE counted is set here, bit for bit.  m <= 65535.
+ *   one step   gsr_sam_mask_score_direct / _emit_direct: SM_SCORE and SM_EMIT with SAM2's geometry (postprocess_masks): the value
+ *              at output pixel (y, x) is ONE F.interpolate((L, L) -> (oh, ow), bilinear, align_corners=False) of the logits:
+ *              the axis rule above with scale = fp32(L) / fp32(out) and the four taps read from the logits themselves.  The
+ *              same kernels; everything else as SM_SCORE / SM_EMIT state it.
  * Weight table of gsr_sam_encode: a HOST array of gsr_sam_num_weights(layers) DEVICE pointers to fp16 arrays (16-byte
  * aligned), none NULL, in this order (names: SamVisionEncoder.state_dict()):
  *   GSR_SAM_W_PATCH_W patch_embed.projection.weight [hidden,768]; _PATCH_B its bias; _POS pos_embed [g,g,hidden];
@@ -1298,6 +1303,10 @@ int32_t gsr_sam_mask_score(const float* logits, int32_t n, int32_t L, int32_t ih
                            float delta, const uint8_t* skip, int32_t* counts, float* boxes, gsr_stream_t stream);
 int32_t gsr_sam_mask_emit(const float* logits, int32_t n, int32_t L, int32_t ih, int32_t iw, int32_t oh, int32_t ow, float tau,
                           const int32_t* index, int32_t m, uint8_t* out, gsr_stream_t stream);
+int32_t gsr_sam_mask_score_direct(const float* logits, int32_t n, int32_t L, int32_t oh, int32_t ow, float tau, float delta,
+                                  const uint8_t* skip, int32_t* counts, float* boxes, gsr_stream_t stream);
+int32_t gsr_sam_mask_emit_direct(const float* logits, int32_t n, int32_t L, int32_t oh, int32_t ow, float tau, const int32_t* index,
+                                 int32_t m, uint8_t* out, gsr_stream_t stream);
 size_t gsr_sam_nms_workspace_bytes(int32_t n);
 int32_t gsr_sam_nms(const float* boxes, const float* scores, const uint8_t* keep_in, int32_t n, float theta, void* ws,
                     size_t ws_bytes, int32_t* kept, int32_t* count, gsr_stream_t stream);
@@ -1309,7 +1318,7 @@ int32_t gsr_sam_nms(const float* boxes, const float* scores, const uint8_t* keep
  * transposed convolutions (sam_decoder.hip; Python: gaussmart_amd/sam.py).  g = image_size / 16 with 1 <= g <= 64, T = g g (any
  * value); P points, 1 <= P <= 65535.  One prompt is ONE foreground point (label 1) plus the padding token: 7 tokens per point
  * (iou, mask 0..3, point, not-a-point).  multimask output: masks 1..3 and IoU columns 1..3; mask 0's hypernetwork is not
- * computed.  Boxes, mask prompts, several points per prompt and SAM2 are not built.
+ * computed.  Boxes, mask prompts, several points per prompt and SAM2's mask decoder are not built.
  * Precision: every weight is fp16 except the positional matrix; every product with a weight is DN_LINEAR (fp16 operands, one
  * k-ascending fp32 chain per element, rows independent); LayerNorm statistics (DN_NORM's formula), softmax and the token stream
  * are fp32; the per-point image stream is STORED AS fp16 between stages.  No split-K, no float atomics: a point's bits do not
@@ -1391,6 +1400,100 @@ size_t gsr_sam_decode_workspace_bytes(int32_t g, int32_t P);
 int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, int32_t n_weights, const float* emb, const float* pe,
                        const float* points, int32_t P, int32_t image_size, void* ws, size_t ws_bytes, float* low_res, float* iou,
                        gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- SAM2: the Hiera image encoder and its FPN neck
+ * transformers' Sam2VisionModel (models/sam2/modeling_sam2.py: Sam2HieraDetModel and Sam2VisionNeck) plus what
+ * Sam2Model.get_image_features / get_image_embeddings add for a still image, as inference kernels (sam2.hip; Python:
+ * gaussmart_amd/sam2.py); what the reference's SAMSegmentation(sam2=True) runs inside SAM2AutomaticMaskGenerator.  Four stages;
+ * stage i has the grid g_i = (image_size / 4) >> i (g_0 <= 256, a multiple of 8), the width dims[i] = 2 dims[i - 1], heads[i]
+ * heads of head_dim dims[i] / heads[i] in {56, 64, 72, 80, 96}, blocks[i] blocks and the window windows[i]; the blocks are numbered
+ * through the stages and those in global_host attend over the whole grid.  MLP ratio 4, erf GELU, ln_eps 1e-6, query stride
+ * 2 x 2, one image per call.  EVERY weight is fp16 except no_memory_embedding; the residual stream, the LayerNorm statistics
+ * and the softmax are fp32, as SV_* states for SAM.  Rules, with every rounding:
+ *   HV_LINEAR  DN_LINEAR for any K that is a multiple of 8: the 16-byte loads past K give zeros, so the last chunk of 64 adds
+ *              exact zeros to the k-ascending chain.  K a multiple of 64 runs DN_LINEAR's own kernels: the same bits.  Epilogues:
+ *              GSR_DINO_EPI_BIAS, _GELU, _RESID, and GSR_SAM2_EPI_RESID1 (resid = resid + (acc + bias), one fp32 addition after
+ *              the bias's) and GSR_SAM2_EPI_F32 (acc + bias stored as fp32).
+ *   HV_EMBED   pixel_values f32 [3,S,S], normalised by the caller, ROUNDED TO fp16; the 7x7 stride-4 padding-3 convolution is
+ *              a product over K = 152: k = c 49 + ky 7 + kx for k < 147 (Conv2d's own weight order), pixel (4 py + ky - 3,
+ *              4 px + kx - 3), zero outside the image (only the top and left padding is ever read) and for k >= 147, where the
+ *              weight rows are zero-padded too; v = acc + fp32(bias[n]), then v + fp32(pos[y][x][n]): two fp32 additions,
+ *              stored as fp32 [g_0 g_0,dims[0]].  pos is an fp16 [g_0,g_0,dims[0]] table the caller computes once:
+ *              F.interpolate(pos_embed, (g_0, g_0), bicubic) + pos_embed_window tiled (Sam2HieraDetModel._get_pos_embed), in
+ *              fp32, ROUNDED TO fp16.
+ *   block      n = DN_NORM(stream) fp16.  First block of stage i > 0 (on grid g_(i-1), width dims[i-1], window windows[i-1]):
+ *              residual = HV_POOL(proj(n) + bias as fp32) on grid g_i; every other block: residual = stream.  qkv =
+ *              HV_LINEAR(n, qkv.weight, qkv.bias) ROUNDED TO fp16 [T,3 dims[i]] (q of head h in columns h head_dim .., k at
+ *              dims[i] + .., v at 2 dims[i] + ..); HV_ATTN; stream = residual + (attn.proj(att) + bias), one fp32 addition
+ *              after the bias's; n = DN_NORM(stream); mlp.proj_in with erf GELU ROUNDED TO fp16; stream += mlp.proj_out
+ *              (+ bias) likewise.
+ *   HV_ATTN    qkv fp16 [g,g,3 hidden]; window w (0: the whole grid), query stride 1 or 2, heads, head_dim.  Windows are the
+ *              non-overlapping w x w blocks of the grid (g a multiple of w).  stride 2: the query of pooled position (i, j) of
+ *              a window is the elementwise maximum of the four fp16 q rows (2 i .. 2 i + 1, 2 j .. 2 j + 1) of that window
+ *              (exact), and the output lies on the g / 2 grid at (wy w / 2 + i, wx w / 2 + j); the keys are all w w tokens of
+ *              the window.  Score, fp32: t2 = ((sum_d q_d k_d) * fp32(head_dim^-1/2)) * fp32(log2 e), TWO fp32 roundings after
+ *              the fp32 chain of the product; no bias terms.  Then SV_ATTN's one pass: KV tiles of 64 keys (row-major in the
+ *              window), running maximum m and sum l in fp32, p = 2^(t2 - m) (v_exp_f32), l adds the UNROUNDED p, p ROUNDED TO
+ *              fp16 for the P V product (fp16 v, fp32 accumulation, rescaled by 2^(m_old - m_new)); out = acc / l in fp32,
+ *              ROUNDED TO fp16 [T_out,hidden].  head_dim 56 and 64 run the tile of width 64, 72 and 80 the tile of 80, 96 the
+ *              tile of 96 (six k-steps); the columns of q, k and v past head_dim are zeros in the tile and never stored.  Keys
+ *              past w w are never read.  A workgroup owns up to 128 queries of one head of one window and has one wave per 32
+ *              of them; a window's bits depend on its own tokens only.
+ *   HV_POOL    out[y][x][c] = max of the four in[2 y + a][2 x + b][c], fp32 [g,g,C] -> [g/2,g/2,C]: exact.
+ *   HV_NECK    the four stage-end streams ROUNDED TO fp16; lateral_i = HV_LINEAR(stream_i, convs[3 - i].weight [D,dims[i]], its
+ *              bias) stored as fp32 (the 1x1 convolutions; convs[0] belongs to the widest, lowest-resolution map); from level 2
+ *              down to 0: prev_i = lateral_i + prev_(i+1)[y / 2][x / 2] (nearest, one fp32 addition) if bit i of top_down_mask
+ *              is set, else lateral_i; prev_3 = lateral_3.  out0 = conv_s0(fp16(prev_0)) + bias [D/8,g_0,g_0], out1 =
+ *              conv_s1(fp16(prev_1)) + bias [D/4,g_1,g_1] (HV_LINEAR over K = D, stored as fp32), out2 = prev_2 +
+ *              no_memory_embedding (f32, one fp32 addition) [D,g_2,g_2].  The neck's sine position encodings are not computed:
+ *              the image path does not read them.
+ * Weight table of gsr_sam2_encode: a HOST array of gsr_sam2_num_weights(total blocks) DEVICE pointers to fp16 arrays (16-byte
+ * aligned) unless stated, in this order (names: Sam2Model.state_dict() under vision_encoder.):
+ *   GSR_SAM2_W_PATCH_W backbone.patch_embed.projection.weight as [dims[0],152] (147 columns and 5 zeros); _PATCH_B its bias; _POS
+ *   the position table of HV_EMBED;
+ *   per block b at GSR_SAM2_W_BLOCK0 + GSR_SAM2_W_PER_BLOCK b + GSR_SAM2_B_*: backbone.blocks.b.layer_norm1.weight, .bias,
+ *   attn.qkv.weight [3 dim_out,dim], .bias, attn.proj.weight, .bias, layer_norm2.weight, .bias, mlp.proj_in.weight, .bias,
+ *   mlp.proj_out.weight, .bias, proj.weight [dim_out,dim], .bias (the last two NULL unless the block starts a stage);
+ *   last (GSR_SAM2_W_NECK entries; gsr_sam2_neck takes these alone): for stage i = 0 .. 3 neck.convs.(3 - i).weight [D,dims[i]]
+ *   and .bias; mask_decoder.conv_s0.weight [D/8,D], .bias; mask_decoder.conv_s1.weight [D/4,D], .bias; no_memory_embedding
+ *   F32 [D].
+ * Entry points (caller's stream, caller's buffers, nothing synchronises):
+ *   gsr_sam2_embed / _linear / _attn / _pool / _neck : one rule each; ws from the *_workspace_bytes beside it.  _neck:
+ *       streams_host is a HOST array of the four DEVICE streams f32 [g_i g_i,dims[i]]; the outputs are out0, out1, out2 above.
+ *   gsr_sam2_encode : pixel_values f32 [3,S,S] -> out0, out1, out2; ws: gsr_sam2_workspace_bytes(cfg) (0 when refused).
+ * Refused with GSR_E_INVALID before anything is launched, with a message: a grid that is not a multiple of its window (a
+ * stage start: the previous grid and the previous window), a query stride other than 2 x 2, a stage that does not double its
+ * width, a global block that starts a stage, a head_dim that is not built, a null required pointer, a short workspace, a
+ * weight table of the wrong length. */
+typedef struct GsrSam2Config {
+    int32_t image_size, fpn_hidden, top_down_mask, num_global;
+    int32_t blocks[4], dims[4], heads[4], windows[4];
+    int32_t query_stride[2];
+    float ln_eps;
+    const int32_t* global_host;     /* HOST array of num_global block numbers */
+} GsrSam2Config;
+enum { GSR_SAM2_EPI_RESID1 = 4, GSR_SAM2_EPI_F32 = 5 };
+enum { GSR_SAM2_W_PATCH_W = 0, GSR_SAM2_W_PATCH_B, GSR_SAM2_W_POS, GSR_SAM2_W_BLOCK0 };
+enum { GSR_SAM2_B_NORM1_W = 0, GSR_SAM2_B_NORM1_B, GSR_SAM2_B_QKV_W, GSR_SAM2_B_QKV_B, GSR_SAM2_B_OUT_W, GSR_SAM2_B_OUT_B,
+       GSR_SAM2_B_NORM2_W, GSR_SAM2_B_NORM2_B, GSR_SAM2_B_MLP1_W, GSR_SAM2_B_MLP1_B, GSR_SAM2_B_MLP2_W, GSR_SAM2_B_MLP2_B,
+       GSR_SAM2_B_PROJ_W, GSR_SAM2_B_PROJ_B, GSR_SAM2_W_PER_BLOCK };
+enum { GSR_SAM2_W_NECK = 13 };
+size_t gsr_sam2_embed_workspace_bytes(int32_t image_size);
+int32_t gsr_sam2_embed(const float* pixel_values, int32_t image_size, int32_t embed, const void* patch_w, const void* patch_b,
+                       const void* pos_table, void* ws, size_t ws_bytes, float* out, gsr_stream_t stream);
+int32_t gsr_sam2_linear(const void* x, const void* w, const void* bias, const void* lambda, int64_t M, int32_t K, int32_t N,
+                        int32_t epilogue, void* out, gsr_stream_t stream);
+int32_t gsr_sam2_attn(const void* qkv, int32_t g, int32_t window, int32_t query_stride, int32_t heads, int32_t head_dim, void* out,
+                      gsr_stream_t stream);
+int32_t gsr_sam2_pool(const float* x, int32_t g, int32_t channels, float* out, gsr_stream_t stream);
+size_t gsr_sam2_neck_workspace_bytes(int32_t g0, int32_t embed, int32_t fpn_hidden);
+int32_t gsr_sam2_neck(const float* const* streams_host, int32_t g0, int32_t embed, int32_t fpn_hidden, int32_t top_down_mask,
+                      const void* const* neck_weights_host, void* ws, size_t ws_bytes, float* out0, float* out1, float* out2,
+                      gsr_stream_t stream);
+size_t gsr_sam2_workspace_bytes(const GsrSam2Config* cfg);
+int32_t gsr_sam2_num_weights(int32_t total_blocks);
+int32_t gsr_sam2_encode(const GsrSam2Config* cfg, const void* const* weights_host, int32_t n_weights, const float* pixel_values,
+                        void* ws, size_t ws_bytes, float* out0, float* out1, float* out2, gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only
