@@ -25,6 +25,9 @@ GSR_SAM2_EPI_RESID1, GSR_SAM2_EPI_F32 = 4, 5
 GSR_SAM2_W_BLOCK0, GSR_SAM2_W_PER_BLOCK, GSR_SAM2_W_NECK = 3, 14, 13     # include/gsr.h: the weight table of gsr_sam2_encode
 # include/gsr.h: the weight table of gsr_sam_decode (head, per two-way layer, final attention, up-scaling, hypernetworks, IoU head)
 GSR_SAMD_W_LAYER0, GSR_SAMD_W_PER_LAYER, GSR_SAMD_W_FINAL, GSR_SAMD_W_UP, GSR_SAMD_W_HYPER, GSR_SAMD_W_IOU, GSR_SAMD_W_COUNT = 6, 36, 78, 88, 94, 112, 118
+# include/gsr.h: the weight table of gsr_sam2_decode is gsr_sam_decode's under SAM2's names plus the object-score token
+GSR_SAMD_W_POINT1 = 1
+GSR_SAM2D_W_OBJ_TOKEN, GSR_SAM2D_W_COUNT = 118, 119
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_SCRATCH, GSR_BUF_SCRATCH2 = range(5)
 GSR_BUF_SYNC_SH = 100     # not a buffer: "the SH colour pass is about to be enqueued" (GSR_FLAG_DEFER_COLOR)
@@ -404,7 +407,16 @@ def lib():
                 ("gsr_sam2_neck", C.c_int32, [C.POINTER(vp)] + [C.c_int32] * 4 + [C.POINTER(vp), vp, sz, vp, vp, vp, vp]),
                 ("gsr_sam2_workspace_bytes", sz, [C.POINTER(GsrSam2Config)]),
                 ("gsr_sam2_num_weights", C.c_int32, [C.c_int32]),
-                ("gsr_sam2_encode", C.c_int32, [C.POINTER(GsrSam2Config), C.POINTER(vp), C.c_int32, vp, vp, sz, vp, vp, vp, vp])):
+                ("gsr_sam2_encode", C.c_int32, [C.POINTER(GsrSam2Config), C.POINTER(vp), C.c_int32, vp, vp, sz, vp, vp, vp, vp]),
+                ("gsr_sam2_dec_t2i", C.c_int32, [vp] * 4 + [C.c_int32] * 3 + [vp, vp]),
+                ("gsr_sam2_dec_i2t_workspace_bytes", sz, [C.c_int32] * 2),
+                ("gsr_sam2_dec_i2t", C.c_int32, [vp] * 5 + [C.c_int32] * 3 + [vp] * 4 + [C.c_float, vp, sz, vp, vp]),
+                ("gsr_sam2_dec_upscale_workspace_bytes", sz, [C.c_int32] * 2),
+                ("gsr_sam2_dec_upscale", C.c_int32, [vp, C.c_int32, C.c_int32] + [vp] * 10 + [sz, vp, vp]),
+                ("gsr_sam2_dec_num_weights", C.c_int32, []),
+                ("gsr_sam2_decode_workspace_bytes", sz, [C.c_int32] * 2),
+                ("gsr_sam2_decode", C.c_int32, [C.c_int32, C.POINTER(vp), C.c_int32, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, sz, vp, vp,
+                                                vp])):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]

@@ -4,17 +4,27 @@
 // Every matrix product with a weight is DN_LINEAR (vit.hip, through vit_common.h): fp16 operands, one k-ascending fp32
 // chain per output element, rows independent of each other.  The attention cores, the LayerNorms of the image stream and the
 // mask product are the kernels of this file.  No split-K, no float atomics: a point's bits depend on its own data only.
+// SAM2's decoder (Sam2PromptEncoder / Sam2MaskDecoder; the S2D_* deltas in include/gsr.h) runs the same body: the kernels that
+// walk a point's tokens take their number as a template parameter (7: SAM, 8: SAM2 with the object-score token in front), the
+// eps of the four block norms is an argument, and the up-scaling takes the two high-resolution skips when they are given.
 #include "vit_common.h"
 
 #define SD_C 256           // hidden
 #define SD_CI 128           // internal width of the cross attentions: 8 heads of 16
 #define SD_HEADS_N 8
-#define SD_TOK 7            // iou, 4 mask tokens, the point, not-a-point
+#define SD_TOK 7            // SAM: iou, 4 mask tokens, the point, not-a-point
+#define SD_TOK2 8           // SAM2: obj_score, iou, 4 mask tokens, the point, not-a-point
 #define SD_MLP 2048
 #define SD_MAX_GRID 64
 #define SD_MAX_POINTS 65535
 #define SD_EPS 1e-6f        // SamMaskDecoderConfig.layer_norm_eps and SamLayerNorm's default
-#define SD_EPS_FINAL 1e-5f  // layer_norm_final_attn is a plain nn.LayerNorm
+#define SD_EPS_FINAL 1e-5f  // layer_norm_final_attn is a plain nn.LayerNorm; so are SAM2's layer_norm1..4
+// Where SAM2's feat_s0 is added.  1 (the product): in conv2's epilogue (DN_EPI_SKIP_GELU).  0 (a developer build, `make
+// BUILD=build_ab OUT=../lib_ab/libgsr_hip.so EXTRA_DEFS=-DSD_SKIP0_EPILOGUE=0`): conv2 stored as fp32, then one elementwise
+// kernel.  The same bits; profiles/sam2_bench.txt has both times (the up-scaling of 256 points at g = 64: 3.31 against 3.50 ms).
+#ifndef SD_SKIP0_EPILOGUE
+#define SD_SKIP0_EPILOGUE 1
+#endif
 
 // ---------------------------------------------------------------- SD_PROMPT
 // out[p][0][c] = sinf(arg_c) + fp32(point1[c]), out[p][0][128 + c] = cosf(arg_c) + fp32(point1[128 + c]), out[p][1][:] = fp32(nap);
@@ -77,20 +87,23 @@ __global__ void __launch_bounds__(256) sd_image_kernel(const float* __restrict__
 }
 
 // ---------------------------------------------------------------- SD_TOKENS (elementwise parts)
-// tok[p][j]: j = 0 iou_token, 1..4 mask_tokens, 5 and 6 the two sparse tokens of the point; written twice (queries and their
-// positional term are the same tensor at the start)
-__global__ void __launch_bounds__(256) sd_tokens_kernel(const dn_half* __restrict__ iou_tok, const dn_half* __restrict__ mask_tok,
-                                                        const float* __restrict__ sparse, float* __restrict__ tok0,
-                                                        float* __restrict__ q) {
+// tok[p][j], with o = TOK - 7 (SAM2: row 0 is obj_score_token): j = o iou_token, o + 1 .. o + 4 mask_tokens, o + 5 and o + 6 the
+// two sparse tokens of the point; written twice (queries and their positional term are the same tensor at the start)
+template <int TOK>
+__global__ void __launch_bounds__(256) sd_tokens_kernel(const dn_half* __restrict__ obj_tok, const dn_half* __restrict__ iou_tok,
+                                                        const dn_half* __restrict__ mask_tok, const float* __restrict__ sparse,
+                                                        float* __restrict__ tok0, float* __restrict__ q) {
+    constexpr int o = TOK - SD_TOK;
     const int64_t p = blockIdx.x;
     const int c = threadIdx.x;
-    for (int j = 0; j < SD_TOK; ++j) {
+    for (int j = 0; j < TOK; ++j) {
         float v;
-        if (j == 0) v = (float)iou_tok[c];
-        else if (j < 5) v = (float)mask_tok[(j - 1) * SD_C + c];
-        else v = sparse[(p * 2 + (j - 5)) * SD_C + c];
-        tok0[(p * SD_TOK + j) * SD_C + c] = v;
-        q[(p * SD_TOK + j) * SD_C + c] = v;
+        if (j < o) v = (float)obj_tok[c];
+        else if (j == o) v = (float)iou_tok[c];
+        else if (j < o + 5) v = (float)mask_tok[(j - o - 1) * SD_C + c];
+        else v = sparse[(p * 2 + (j - o - 5)) * SD_C + c];
+        tok0[(p * TOK + j) * SD_C + c] = v;
+        q[(p * TOK + j) * SD_C + c] = v;
     }
 }
 
@@ -106,18 +119,20 @@ __global__ void __launch_bounds__(256) sd_relu_kernel(dn_half* __restrict__ x, i
     if (i < n && x[i] < (dn_half)0.f) x[i] = (dn_half)0.f;
 }
 
-// token self-attention: 7 queries, 7 keys, 8 heads of 32; q, k, v f32 [P,7,256]; thread = (head, query); out fp16
+// token self-attention: TOK queries, TOK keys, 8 heads of 32; q, k, v f32 [P,TOK,256]; thread = (head, query), 8 TOK <= 64 of
+// them (TOK = 8 fills the workgroup); out fp16
+template <int TOK>
 __global__ void __launch_bounds__(64) sd_self_attn_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                           const float* __restrict__ v, dn_half* __restrict__ out) {
     const int64_t p = blockIdx.x;
     const int t = threadIdx.x;
-    if (t >= SD_HEADS_N * SD_TOK) return;
-    const int h = t / SD_TOK, i = t - h * SD_TOK;
-    const float* qr = q + (p * SD_TOK + i) * SD_C + h * 32;
-    float s[SD_TOK], m = -INFINITY;
+    if (t >= SD_HEADS_N * TOK) return;
+    const int h = t / TOK, i = t - h * TOK;
+    const float* qr = q + (p * TOK + i) * SD_C + h * 32;
+    float s[TOK], m = -INFINITY;
 #pragma unroll
-    for (int j = 0; j < SD_TOK; ++j) {
-        const float* kr = k + (p * SD_TOK + j) * SD_C + h * 32;
+    for (int j = 0; j < TOK; ++j) {
+        const float* kr = k + (p * TOK + j) * SD_C + h * 32;
         float acc = 0.f;
         for (int d = 0; d < 32; ++d) acc = fmaf(qr[d], kr[d], acc);
         s[j] = acc * 0.17677669529663688110f;       // 32^-1/2
@@ -125,32 +140,33 @@ __global__ void __launch_bounds__(64) sd_self_attn_kernel(const float* __restric
     }
     float l = 0.f;
 #pragma unroll
-    for (int j = 0; j < SD_TOK; ++j) {
+    for (int j = 0; j < TOK; ++j) {
         s[j] = expf(s[j] - m);
         l += s[j];
     }
-    dn_half* o = out + (p * SD_TOK + i) * SD_C + h * 32;
+    dn_half* o = out + (p * TOK + i) * SD_C + h * 32;
     for (int d = 0; d < 32; ++d) {
         float acc = 0.f;
 #pragma unroll
-        for (int j = 0; j < SD_TOK; ++j) acc = fmaf(s[j], v[(p * SD_TOK + j) * SD_C + h * 32 + d], acc);
+        for (int j = 0; j < TOK; ++j) acc = fmaf(s[j], v[(p * TOK + j) * SD_C + h * 32 + d], acc);
         o[d] = (dn_half)(acc / l);
     }
 }
 
 // ---------------------------------------------------------------- SD_T2I
-// One workgroup per (point, head): 7 queries of 16 over T keys.  Thread t takes keys t, t + 256, ... in order; the key is
+// One workgroup per (point, head): TOK queries of 16 over T keys.  Thread t takes keys t, t + 256, ... in order; the key is
 // fp32(kx) + kpe (kpe NULL: fp32(kx)), the score (sum_d q_d k_d, d ascending, fmaf) * scale.  Pass 1: the maximum per query
 // (xor butterfly over the wave, then the four waves).  Pass 2 computes the same scores again, p = expf(s - m), and adds p and
 // p v per thread in key order; the 64 lanes are added by a xor butterfly, the four waves in order.  out = fp16(acc / l).
+template <int TOK>
 __global__ void __launch_bounds__(256) sd_t2i_kernel(const float* __restrict__ q, const dn_half* __restrict__ kx,
                                                      const float* __restrict__ kpe, const dn_half* __restrict__ v, int T,
                                                      int64_t kv_stride, float scale, dn_half* __restrict__ out) {
-    __shared__ float qs[SD_TOK][16];
-    __shared__ float red[4][SD_TOK * 17];
+    __shared__ float qs[TOK][16];
+    __shared__ float red[4][TOK * 17];
     const int64_t p = blockIdx.x;
     const int h = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (t < SD_TOK * 16) qs[t >> 4][t & 15] = q[(p * SD_TOK + (t >> 4)) * SD_CI + h * 16 + (t & 15)];
+    if (t < TOK * 16) qs[t >> 4][t & 15] = q[(p * TOK + (t >> 4)) * SD_CI + h * 16 + (t & 15)];
     __syncthreads();
     const dn_half* kp = kx + p * kv_stride + h * 16;
     const dn_half* vp = v + p * kv_stride + h * 16;
@@ -165,47 +181,47 @@ __global__ void __launch_bounds__(256) sd_t2i_kernel(const float* __restrict__ q
             for (int d = 0; d < 16; ++d) kk[d] = kk[d] + pp[(int64_t)key * SD_CI + d];
         }
 #pragma unroll
-        for (int j = 0; j < SD_TOK; ++j) {
+        for (int j = 0; j < TOK; ++j) {
             float acc = 0.f;
 #pragma unroll
             for (int d = 0; d < 16; ++d) acc = fmaf(qs[j][d], kk[d], acc);
             s[j] = acc * scale;
         }
     };
-    float m[SD_TOK];
+    float m[TOK];
 #pragma unroll
-    for (int j = 0; j < SD_TOK; ++j) m[j] = -INFINITY;
+    for (int j = 0; j < TOK; ++j) m[j] = -INFINITY;
     for (int key = t; key < T; key += 256) {
-        float s[SD_TOK];
+        float s[TOK];
         scores(key, s);
 #pragma unroll
-        for (int j = 0; j < SD_TOK; ++j) m[j] = fmaxf(m[j], s[j]);
+        for (int j = 0; j < TOK; ++j) m[j] = fmaxf(m[j], s[j]);
     }
 #pragma unroll
-    for (int j = 0; j < SD_TOK; ++j) m[j] = wave_max_f32(m[j]);
+    for (int j = 0; j < TOK; ++j) m[j] = wave_max_f32(m[j]);
     if (lane == 0)
 #pragma unroll
-        for (int j = 0; j < SD_TOK; ++j) red[wave][j] = m[j];
+        for (int j = 0; j < TOK; ++j) red[wave][j] = m[j];
     __syncthreads();
 #pragma unroll
-    for (int j = 0; j < SD_TOK; ++j) m[j] = fmaxf(fmaxf(red[0][j], red[1][j]), fmaxf(red[2][j], red[3][j]));
+    for (int j = 0; j < TOK; ++j) m[j] = fmaxf(fmaxf(red[0][j], red[1][j]), fmaxf(red[2][j], red[3][j]));
     __syncthreads();        // red is written again below
 
-    float l[SD_TOK], acc[SD_TOK][16];
+    float l[TOK], acc[TOK][16];
 #pragma unroll
-    for (int j = 0; j < SD_TOK; ++j) {
+    for (int j = 0; j < TOK; ++j) {
         l[j] = 0.f;
 #pragma unroll
         for (int d = 0; d < 16; ++d) acc[j][d] = 0.f;
     }
     for (int key = t; key < T; key += 256) {
-        float s[SD_TOK], vv[16];
+        float s[TOK], vv[16];
         scores(key, s);
         const vit_h8 a = *reinterpret_cast<const vit_h8*>(vp + (int64_t)key * SD_CI), b = *reinterpret_cast<const vit_h8*>(vp + (int64_t)key * SD_CI + 8);
 #pragma unroll
         for (int d = 0; d < 8; ++d) { vv[d] = (float)a[d]; vv[8 + d] = (float)b[d]; }
 #pragma unroll
-        for (int j = 0; j < SD_TOK; ++j) {
+        for (int j = 0; j < TOK; ++j) {
             const float pr = expf(s[j] - m[j]);
             l[j] += pr;
 #pragma unroll
@@ -213,56 +229,69 @@ __global__ void __launch_bounds__(256) sd_t2i_kernel(const float* __restrict__ q
         }
     }
 #pragma unroll
-    for (int j = 0; j < SD_TOK; ++j) {
+    for (int j = 0; j < TOK; ++j) {
         l[j] = wave_sum_f32(l[j]);
 #pragma unroll
         for (int d = 0; d < 16; ++d) acc[j][d] = wave_sum_f32(acc[j][d]);
     }
     if (lane == 0)
 #pragma unroll
-        for (int j = 0; j < SD_TOK; ++j) {
+        for (int j = 0; j < TOK; ++j) {
             red[wave][j * 17 + 16] = l[j];
 #pragma unroll
             for (int d = 0; d < 16; ++d) red[wave][j * 17 + d] = acc[j][d];
         }
     __syncthreads();
-    if (t < SD_TOK * 16) {
+    if (t < TOK * 16) {
         const int j = t >> 4, d = t & 15;
         const float lt = ((red[0][j * 17 + 16] + red[1][j * 17 + 16]) + red[2][j * 17 + 16]) + red[3][j * 17 + 16];
         const float at = ((red[0][j * 17 + d] + red[1][j * 17 + d]) + red[2][j * 17 + d]) + red[3][j * 17 + d];
-        out[(p * SD_TOK + j) * SD_CI + h * 16 + d] = (dn_half)(at / lt);
+        out[(p * TOK + j) * SD_CI + h * 16 + d] = (dn_half)(at / lt);
     }
 }
 
+template <int TOK>
 static int sd_t2i(const float* q, const dn_half* kx, const float* kpe, const dn_half* v, int P, int T, int shared, float scale,
                   dn_half* out, hipStream_t s) {
-    hipLaunchKernelGGL(sd_t2i_kernel, dim3((unsigned)P, SD_HEADS_N), dim3(256), 0, s, q, kx, kpe, v, T,
+    hipLaunchKernelGGL(sd_t2i_kernel<TOK>, dim3((unsigned)P, SD_HEADS_N), dim3(256), 0, s, q, kx, kpe, v, T,
                        shared ? (int64_t)0 : (int64_t)T * SD_CI, scale, out);
     GSR_LAUNCH_CHECK();
     return GSR_OK;
 }
 
-extern "C" int32_t gsr_sam_dec_t2i(const float* q, const void* kx, const float* kpe, const void* v, int32_t P, int32_t T,
-                                   int32_t shared, void* out, gsr_stream_t stream_) {
+template <int TOK>
+static int sd_t2i_entry(const float* q, const void* kx, const float* kpe, const void* v, int P, int T, int shared, void* out,
+                        gsr_stream_t stream_) {
     GSR_TRY(sd_check_points(P));
     if (T < 1 || T > SD_MAX_GRID * SD_MAX_GRID) { gsr_set_error("sam dec t2i: T %d is outside 1 .. %d", T, SD_MAX_GRID * SD_MAX_GRID); return GSR_E_INVALID; }
     if (!q || !kx || !v || !out) { gsr_set_error("sam dec t2i: q / kx / v / out is null"); return GSR_E_INVALID; }
-    return sd_t2i(q, static_cast<const dn_half*>(kx), kpe, static_cast<const dn_half*>(v), P, T, shared != 0, 0.25f,
-                  static_cast<dn_half*>(out), static_cast<hipStream_t>(stream_));
+    return sd_t2i<TOK>(q, static_cast<const dn_half*>(kx), kpe, static_cast<const dn_half*>(v), P, T, shared != 0, 0.25f,
+                       static_cast<dn_half*>(out), static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int32_t gsr_sam_dec_t2i(const float* q, const void* kx, const float* kpe, const void* v, int32_t P, int32_t T,
+                                   int32_t shared, void* out, gsr_stream_t stream_) {
+    return sd_t2i_entry<SD_TOK>(q, kx, kpe, v, P, T, shared, out, stream_);
+}
+
+extern "C" int32_t gsr_sam2_dec_t2i(const float* q, const void* kx, const float* kpe, const void* v, int32_t P, int32_t T,
+                                    int32_t shared, void* out, gsr_stream_t stream_) {
+    return sd_t2i_entry<SD_TOK2>(q, kx, kpe, v, P, T, shared, out, stream_);
 }
 
 // ---------------------------------------------------------------- SD_I2T
-// thread = (image token, head); the 7 keys and values of the point are in LDS.  q = fp32(qx) + qpe; s_j = (sum_d q_d k_jd) *
+// thread = (image token, head); the TOK keys and values of the point are in LDS.  q = fp32(qx) + qpe; s_j = (sum_d q_d k_jd) *
 // 1/4, d ascending, fmaf; p_j = expf(s_j - max); ctx_d = (sum_j p_j v_jd) / (sum_j p_j), j ascending; stored as fp16.
+template <int TOK>
 __global__ void __launch_bounds__(256) sd_i2t_kernel(const dn_half* __restrict__ qx, const float* __restrict__ qpe,
                                                      const float* __restrict__ k, const float* __restrict__ v, int T,
                                                      int64_t q_stride, dn_half* __restrict__ ctx) {
-    __shared__ float ks[SD_TOK * SD_CI], vs[SD_TOK * SD_CI];
+    __shared__ float ks[TOK * SD_CI], vs[TOK * SD_CI];
     const int64_t p = blockIdx.y;
     const int t = threadIdx.x;
-    for (int i = t; i < SD_TOK * SD_CI; i += 256) {
-        ks[i] = k[p * SD_TOK * SD_CI + i];
-        vs[i] = v[p * SD_TOK * SD_CI + i];
+    for (int i = t; i < TOK * SD_CI; i += 256) {
+        ks[i] = k[p * TOK * SD_CI + i];
+        vs[i] = v[p * TOK * SD_CI + i];
     }
     __syncthreads();
     const int tok = (int)blockIdx.x * 32 + (t >> 3), h = t & 7;
@@ -273,9 +302,9 @@ __global__ void __launch_bounds__(256) sd_i2t_kernel(const dn_half* __restrict__
     float qq[16];
 #pragma unroll
     for (int d = 0; d < 8; ++d) { qq[d] = (float)a[d] + pr[d]; qq[8 + d] = (float)b[d] + pr[8 + d]; }
-    float s[SD_TOK], m = -INFINITY;
+    float s[TOK], m = -INFINITY;
 #pragma unroll
-    for (int j = 0; j < SD_TOK; ++j) {
+    for (int j = 0; j < TOK; ++j) {
         float acc = 0.f;
 #pragma unroll
         for (int d = 0; d < 16; ++d) acc = fmaf(qq[d], ks[j * SD_CI + h * 16 + d], acc);
@@ -284,7 +313,7 @@ __global__ void __launch_bounds__(256) sd_i2t_kernel(const dn_half* __restrict__
     }
     float l = 0.f;
 #pragma unroll
-    for (int j = 0; j < SD_TOK; ++j) {
+    for (int j = 0; j < TOK; ++j) {
         s[j] = expf(s[j] - m);
         l += s[j];
     }
@@ -293,7 +322,7 @@ __global__ void __launch_bounds__(256) sd_i2t_kernel(const dn_half* __restrict__
     for (int d = 0; d < 16; ++d) {
         float acc = 0.f;
 #pragma unroll
-        for (int j = 0; j < SD_TOK; ++j) acc = fmaf(s[j], vs[j * SD_CI + h * 16 + d], acc);
+        for (int j = 0; j < TOK; ++j) acc = fmaf(s[j], vs[j * SD_CI + h * 16 + d], acc);
         o[d >> 3][d & 7] = (dn_half)(acc / l);
     }
     dn_half* dst = ctx + (p * T + tok) * SD_CI + h * 16;
@@ -328,17 +357,18 @@ __global__ void __launch_bounds__(256) sd_addnorm_kernel(const dn_half* x, const
     *reinterpret_cast<vit_h4*>(x_out + row * SD_C + 4 * lane) = o;
 }
 
-// ctx fp16 [P T,128] and att f32 [P T,256] are the caller's
+// ctx fp16 [P T,128] and att f32 [P T,256] are the caller's; eps is layer_norm4's
+template <int TOK>
 static int sd_i2t(const dn_half* qx, const float* qpe, const float* k, const float* v, const dn_half* x, int P, int T, int shared,
-                  const dn_half* ow, const dn_half* ob, const dn_half* lw, const dn_half* lb, dn_half* ctx, float* att, dn_half* x_out,
-                  hipStream_t s) {
+                  const dn_half* ow, const dn_half* ob, const dn_half* lw, const dn_half* lb, float eps, dn_half* ctx, float* att,
+                  dn_half* x_out, hipStream_t s) {
     const int64_t rows = (int64_t)P * T;
-    hipLaunchKernelGGL(sd_i2t_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)P), dim3(256), 0, s, qx, qpe, k, v, T,
+    hipLaunchKernelGGL(sd_i2t_kernel<TOK>, dim3((unsigned)((T + 31) / 32), (unsigned)P), dim3(256), 0, s, qx, qpe, k, v, T,
                        shared ? (int64_t)0 : (int64_t)T * SD_CI, ctx);
     GSR_LAUNCH_CHECK();
     GSR_TRY(dn_linear(ctx, ow, ob, nullptr, att, rows, SD_CI, SD_C, DN_EPI_F32, s));
     hipLaunchKernelGGL(sd_addnorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, att, rows, T,
-                       shared ? (int64_t)0 : (int64_t)T * SD_C, lw, lb, SD_EPS, x_out);
+                       shared ? (int64_t)0 : (int64_t)T * SD_C, lw, lb, eps, x_out);
     GSR_LAUNCH_CHECK();
     return GSR_OK;
 }
@@ -360,9 +390,10 @@ extern "C" size_t gsr_sam_dec_i2t_workspace_bytes(int32_t P, int32_t T) {
     return SdI2tLayout(P, T, nullptr).total;
 }
 
-extern "C" int32_t gsr_sam_dec_i2t(const void* qx, const float* qpe, const float* k, const float* v, const void* x, int32_t P, int32_t T,
-                                   int32_t shared, const void* out_w, const void* out_b, const void* ln_w, const void* ln_b, void* ws,
-                                   size_t ws_bytes, void* x_out, gsr_stream_t stream_) {
+template <int TOK>
+static int sd_i2t_entry(const void* qx, const float* qpe, const float* k, const float* v, const void* x, int P, int T, int shared,
+                        const void* out_w, const void* out_b, const void* ln_w, const void* ln_b, float eps, void* ws, size_t ws_bytes,
+                        void* x_out, gsr_stream_t stream_) {
     GSR_TRY(sd_check_points(P));
     if (T < 1 || T > SD_MAX_GRID * SD_MAX_GRID) { gsr_set_error("sam dec i2t: T %d is outside 1 .. %d", T, SD_MAX_GRID * SD_MAX_GRID); return GSR_E_INVALID; }
     if (!qx || !qpe || !k || !v || !x || !out_w || !out_b || !ln_w || !ln_b || !x_out) {
@@ -375,24 +406,74 @@ extern "C" int32_t gsr_sam_dec_i2t(const void* qx, const float* qpe, const float
         return GSR_E_INVALID;
     }
     auto hp = [](const void* p) { return static_cast<const dn_half*>(p); };
-    return sd_i2t(hp(qx), qpe, k, v, hp(x), P, T, shared != 0, hp(out_w), hp(out_b), hp(ln_w), hp(ln_b), lay.ctx, lay.att,
-                  static_cast<dn_half*>(x_out), static_cast<hipStream_t>(stream_));
+    return sd_i2t<TOK>(hp(qx), qpe, k, v, hp(x), P, T, shared != 0, hp(out_w), hp(out_b), hp(ln_w), hp(ln_b), eps, lay.ctx, lay.att,
+                       static_cast<dn_half*>(x_out), static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int32_t gsr_sam_dec_i2t(const void* qx, const float* qpe, const float* k, const float* v, const void* x, int32_t P, int32_t T,
+                                   int32_t shared, const void* out_w, const void* out_b, const void* ln_w, const void* ln_b, void* ws,
+                                   size_t ws_bytes, void* x_out, gsr_stream_t stream_) {
+    return sd_i2t_entry<SD_TOK>(qx, qpe, k, v, x, P, T, shared, out_w, out_b, ln_w, ln_b, SD_EPS, ws, ws_bytes, x_out, stream_);
+}
+
+// the workspace does not depend on the number of tokens
+extern "C" size_t gsr_sam2_dec_i2t_workspace_bytes(int32_t P, int32_t T) { return gsr_sam_dec_i2t_workspace_bytes(P, T); }
+
+extern "C" int32_t gsr_sam2_dec_i2t(const void* qx, const float* qpe, const float* k, const float* v, const void* x, int32_t P, int32_t T,
+                                    int32_t shared, const void* out_w, const void* out_b, const void* ln_w, const void* ln_b, float eps,
+                                    void* ws, size_t ws_bytes, void* x_out, gsr_stream_t stream_) {
+    if (!(eps > 0.f)) { gsr_set_error("sam2 dec i2t: eps %g is not positive", (double)eps); return GSR_E_INVALID; }
+    return sd_i2t_entry<SD_TOK2>(qx, qpe, k, v, x, P, T, shared, out_w, out_b, ln_w, ln_b, eps, ws, ws_bytes, x_out, stream_);
 }
 
 // ---------------------------------------------------------------- SD_UP
+// SAM2's two high-resolution skips in the layouts of the two convolutions' outputs, once per call and shared by every point:
+// s1t[(t 4 + tap) 64 + c] = feat_s1[c][2 y + dy][2 x + dx] and s0t[((t 4 + tap1) 4 + tap2) 32 + c] = feat_s0[c][4 y + 2 dy1 + dy2]
+// [4 x + 2 dx1 + dx2], t = y g + x, tap = dy 2 + dx.  Thread i writes s0t[i] and, for i < 256 T, s1t[i].
+__global__ void __launch_bounds__(256) sd_skips_kernel(const float* __restrict__ s0, const float* __restrict__ s1, int g,
+                                                       float* __restrict__ s0t, float* __restrict__ s1t) {
+    const int T = g * g;
+    const int i = (int)blockIdx.x * 256 + threadIdx.x;
+    if (i >= T * 512) return;
+    {
+        const int c = i & 31, tap2 = (i >> 5) & 3, tap1 = (i >> 7) & 3, t = i >> 9;
+        const int y = t / g, x = t - y * g;
+        const int Y = 4 * y + 2 * (tap1 >> 1) + (tap2 >> 1), X = 4 * x + 2 * (tap1 & 1) + (tap2 & 1);
+        s0t[i] = s0[((int64_t)c * 4 * g + Y) * 4 * g + X];
+    }
+    if (i < T * 256) {
+        const int c = i & 63, tap = (i >> 6) & 3, t = i >> 8;
+        const int y = t / g, x = t - y * g;
+        const int Y = 2 * y + (tap >> 1), X = 2 * x + (tap & 1);
+        s1t[i] = s1[((int64_t)c * 2 * g + Y) * 2 * g + X];
+    }
+}
+
 // rows of 64 channels (one output pixel of the first transposed convolution each): fp16(gelu(LayerNorm(row))); one wave per
-// row, a lane per channel
-__global__ void __launch_bounds__(256) sd_up_norm_kernel(const float* __restrict__ u, int64_t rows, const dn_half* __restrict__ g,
+// row, a lane per channel.  skip (SAM2, else NULL): row r takes skip[r mod skip_rows] first, one fp32 addition before the
+// statistics.
+__global__ void __launch_bounds__(256) sd_up_norm_kernel(const float* __restrict__ u, int64_t rows, const float* __restrict__ skip,
+                                                         int skip_rows, const dn_half* __restrict__ g,
                                                          const dn_half* __restrict__ beta, dn_half* __restrict__ y) {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const float x = u[row * 64 + lane];
+    float x = u[row * 64 + lane];
+    if (skip) x = x + skip[(row % skip_rows) * 64 + lane];
     const float mean = wave_sum_f32(x) / 64.0f;
     const float d = x - mean;
     const float rstd = 1.0f / sqrtf(wave_sum_f32(d * d) / 64.0f + SD_EPS);
     y[row * 64 + lane] = (dn_half)vit_gelu(d * rstd * (float)g[lane] + (float)beta[lane]);
 }
+
+#if !SD_SKIP0_EPILOGUE
+// y[r][n] = fp16(gelu(c[r][n] + skip[r mod skip_rows][n])) over rows of 128
+__global__ void __launch_bounds__(256) sd_skip_gelu_kernel(const float* __restrict__ c, const float* __restrict__ skip, int64_t n,
+                                                           int64_t skip_n, dn_half* __restrict__ y) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = (dn_half)vit_gelu(c[i] + skip[i % skip_n]);
+}
+#endif
 
 // low_res[p][m][Y][X] = sum_c hyper[m][p][c] fp32(c2[((p T + t) 4 + tap1) 128 + tap2 32 + c]), c ascending, fmaf; t = (Y >> 2) g +
 // (X >> 2), tap1 = ((Y >> 1) & 1) 2 + ((X >> 1) & 1), tap2 = (Y & 1) 2 + (X & 1).  A thread per output pixel, X fastest.
@@ -422,65 +503,121 @@ __global__ void __launch_bounds__(256) sd_mask_kernel(const dn_half* __restrict_
     for (int m = 0; m < 3; ++m) low_res[((p * 3 + m) * L + Y) * L + X] = acc[m];
 }
 
-// u32 f32 [P T,256] (later fp16 [P T 4,128] in the same bytes) and u16 fp16 [P T 4,64] are the caller's
+// u32 f32 [P T,256] (later fp16 [P T 4,128] in the same bytes) and u16 fp16 [P T 4,64] are the caller's; s0t and s1t are
+// sd_skips_kernel's tables (SAM2) or both NULL (SAM); c32 f32 [P T 4,128] exists in the SD_SKIP0_EPILOGUE=0 build only
 static int sd_upscale(const dn_half* x, int g, int P, const dn_half* c1w, const dn_half* c1b, const dn_half* lw, const dn_half* lb,
-                      const dn_half* c2w, const dn_half* c2b, const float* hyper, float* u32, dn_half* u16, float* low_res,
-                      hipStream_t s) {
-    const int64_t rows = (int64_t)P * g * g;
+                      const dn_half* c2w, const dn_half* c2b, const float* hyper, const float* s0t, const float* s1t, float* u32,
+                      dn_half* u16, float* c32, float* low_res, hipStream_t s) {
+    const int T = g * g;
+    const int64_t rows = (int64_t)P * T;
     GSR_TRY(dn_linear(x, c1w, c1b, nullptr, u32, rows, SD_C, SD_C, DN_EPI_F32, s));
-    hipLaunchKernelGGL(sd_up_norm_kernel, dim3((unsigned)(rows)), dim3(256), 0, s, u32, rows * 4, lw, lb, u16);
+    hipLaunchKernelGGL(sd_up_norm_kernel, dim3((unsigned)(rows)), dim3(256), 0, s, u32, rows * 4, s1t, 4 * T, lw, lb, u16);
     GSR_LAUNCH_CHECK();
     dn_half* c2 = reinterpret_cast<dn_half*>(u32);
-    GSR_TRY(dn_linear(u16, c2w, c2b, nullptr, c2, rows * 4, 64, 128, DN_EPI_GELU, s));
+    if (s0t) {
+#if SD_SKIP0_EPILOGUE
+        GSR_TRY(dn_linear(u16, c2w, c2b, reinterpret_cast<const dn_half*>(s0t), c2, rows * 4, 64, 128, DN_EPI_SKIP_GELU, s, {4 * T, 0, 0}));
+#else
+        GSR_TRY(dn_linear(u16, c2w, c2b, nullptr, c32, rows * 4, 64, 128, DN_EPI_F32, s));
+        const int64_t n = rows * 4 * 128;
+        hipLaunchKernelGGL(sd_skip_gelu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c32, s0t, n, (int64_t)T * 512, c2);
+        GSR_LAUNCH_CHECK();
+#endif
+    } else
+        GSR_TRY(dn_linear(u16, c2w, c2b, nullptr, c2, rows * 4, 64, 128, DN_EPI_GELU, s));
     const int L = 4 * g;
     hipLaunchKernelGGL(sd_mask_kernel, dim3((unsigned)((L * L + 255) / 256), (unsigned)P), dim3(256), 0, s, c2, hyper, g, P, low_res);
     GSR_LAUNCH_CHECK();
     return GSR_OK;
 }
 
+static int sd_skips(const float* feat_s0, const float* feat_s1, int g, float* s0t, float* s1t, hipStream_t s) {
+    hipLaunchKernelGGL(sd_skips_kernel, dim3((unsigned)(g * g * 2)), dim3(256), 0, s, feat_s0, feat_s1, g, s0t, s1t);
+    GSR_LAUNCH_CHECK();
+    return GSR_OK;
+}
+
 struct SdUpLayout {
     size_t total;
-    float* u32;
+    float *u32, *s0t, *s1t, *c32 = nullptr;
     dn_half* u16;
-    SdUpLayout(int g, int P, void* ws) {
+    SdUpLayout(int g, int P, bool skips, void* ws) {
         GsrWsCursor cur(ws);
         u32 = cur.take<float>((size_t)P * g * g * SD_C * 4);
         u16 = cur.take<dn_half>((size_t)P * g * g * 4 * 64 * 2);
+        s0t = skips ? cur.take<float>((size_t)g * g * 512 * 4) : nullptr;
+        s1t = skips ? cur.take<float>((size_t)g * g * 256 * 4) : nullptr;
+#if !SD_SKIP0_EPILOGUE
+        if (skips) c32 = cur.take<float>((size_t)P * g * g * 4 * 128 * 4);
+#endif
         total = cur.off;
     }
 };
 
 extern "C" size_t gsr_sam_dec_upscale_workspace_bytes(int32_t g, int32_t P) {
     if (g < 1 || g > SD_MAX_GRID || P < 1 || P > SD_MAX_POINTS) return 0;
-    return SdUpLayout(g, P, nullptr).total;
+    return SdUpLayout(g, P, false, nullptr).total;
 }
 
-extern "C" int32_t gsr_sam_dec_upscale(const void* x, int32_t g, int32_t P, const void* conv1_w, const void* conv1_b, const void* ln_w,
-                                       const void* ln_b, const void* conv2_w, const void* conv2_b, const float* hyper, void* ws,
-                                       size_t ws_bytes, float* low_res, gsr_stream_t stream_) {
+extern "C" size_t gsr_sam2_dec_upscale_workspace_bytes(int32_t g, int32_t P) {
+    if (g < 1 || g > SD_MAX_GRID || P < 1 || P > SD_MAX_POINTS) return 0;
+    return SdUpLayout(g, P, true, nullptr).total;
+}
+
+// feat_s0 and feat_s1 both NULL: SAM
+static int sd_upscale_entry(const void* x, int g, int P, const void* conv1_w, const void* conv1_b, const void* ln_w, const void* ln_b,
+                            const void* conv2_w, const void* conv2_b, const float* hyper, const float* feat_s0, const float* feat_s1,
+                            void* ws, size_t ws_bytes, float* low_res, gsr_stream_t stream_) {
     GSR_TRY(sd_check_grid(g));
     GSR_TRY(sd_check_points(P));
     if (!x || !conv1_w || !conv1_b || !ln_w || !ln_b || !conv2_w || !conv2_b || !hyper || !low_res) {
         gsr_set_error("sam dec upscale: x / a weight / hyper / low_res is null");
         return GSR_E_INVALID;
     }
-    SdUpLayout lay(g, P, ws);
+    const bool skips = feat_s0 != nullptr;
+    SdUpLayout lay(g, P, skips, ws);
     if (!ws || ws_bytes < lay.total) {
         gsr_set_error("ws_bytes: sam dec upscale workspace too small (%zu < %zu bytes)", ws_bytes, lay.total);
         return GSR_E_INVALID;
     }
+    hipStream_t s = static_cast<hipStream_t>(stream_);
+    if (skips) GSR_TRY(sd_skips(feat_s0, feat_s1, g, lay.s0t, lay.s1t, s));
     auto hp = [](const void* p) { return static_cast<const dn_half*>(p); };
-    return sd_upscale(hp(x), g, P, hp(conv1_w), hp(conv1_b), hp(ln_w), hp(ln_b), hp(conv2_w), hp(conv2_b), hyper, lay.u32, lay.u16,
-                      low_res, static_cast<hipStream_t>(stream_));
+    return sd_upscale(hp(x), g, P, hp(conv1_w), hp(conv1_b), hp(ln_w), hp(ln_b), hp(conv2_w), hp(conv2_b), hyper, lay.s0t, lay.s1t,
+                      lay.u32, lay.u16, lay.c32, low_res, s);
+}
+
+extern "C" int32_t gsr_sam_dec_upscale(const void* x, int32_t g, int32_t P, const void* conv1_w, const void* conv1_b, const void* ln_w,
+                                       const void* ln_b, const void* conv2_w, const void* conv2_b, const float* hyper, void* ws,
+                                       size_t ws_bytes, float* low_res, gsr_stream_t stream_) {
+    return sd_upscale_entry(x, g, P, conv1_w, conv1_b, ln_w, ln_b, conv2_w, conv2_b, hyper, nullptr, nullptr, ws, ws_bytes, low_res,
+                            stream_);
+}
+
+extern "C" int32_t gsr_sam2_dec_upscale(const void* x, int32_t g, int32_t P, const void* conv1_w, const void* conv1_b, const void* ln_w,
+                                        const void* ln_b, const void* conv2_w, const void* conv2_b, const float* hyper,
+                                        const float* feat_s0, const float* feat_s1, void* ws, size_t ws_bytes, float* low_res,
+                                        gsr_stream_t stream_) {
+    if (!feat_s0 || !feat_s1) { gsr_set_error("sam2 dec upscale: feat_s0 / feat_s1 is null"); return GSR_E_INVALID; }
+    return sd_upscale_entry(x, g, P, conv1_w, conv1_b, ln_w, ln_b, conv2_w, conv2_b, hyper, feat_s0, feat_s1, ws, ws_bytes, low_res,
+                            stream_);
 }
 
 // ---------------------------------------------------------------- SD_HEADS (gather)
-// rows[k][p] = fp16(tokens[p][k == 0 ? 0 : k + 1]): the iou token and mask tokens 1..3
+// rows[k][p] = fp16(tokens[p][o + (k == 0 ? 0 : k + 1)]), o = TOK - 7: the iou token and mask tokens 1..3
+template <int TOK>
 __global__ void __launch_bounds__(256) sd_heads_gather_kernel(const float* __restrict__ q, int P, dn_half* __restrict__ rows) {
+    constexpr int o = TOK - SD_TOK;
     const int64_t p = blockIdx.x;
     const int c = threadIdx.x;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) rows[((int64_t)k * P + p) * SD_C + c] = (dn_half)q[(p * SD_TOK + (k == 0 ? 0 : k + 1)) * SD_C + c];
+    for (int k = 0; k < 4; ++k) rows[((int64_t)k * P + p) * SD_C + c] = (dn_half)q[(p * TOK + o + (k == 0 ? 0 : k + 1)) * SD_C + c];
+}
+
+// SAM2's IoU head ends in a sigmoid: x = 1 / (1 + expf(-x)), every operation one fp32 rounding
+__global__ void __launch_bounds__(256) sd_sigmoid_kernel(float* __restrict__ x, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) x[i] = 1.0f / (1.0f + expf(-x[i]));
 }
 
 // ---------------------------------------------------------------- the whole decoder
@@ -495,8 +632,10 @@ struct SdLayout {
     // per point and image token
     dn_half *x16, *b1, *b2;
     float* a32;
-    SdLayout(int g, int P, void* ws) {
-        const size_t T = (size_t)g * g, R = (size_t)P * SD_TOK, PT = (size_t)P * T;
+    // SAM2's skips, per image
+    float *s0t, *s1t, *c32 = nullptr;
+    SdLayout(int g, int P, int tok, bool skips, void* ws) {
+        const size_t T = (size_t)g * g, R = (size_t)P * tok, PT = (size_t)P * T;
         GsrWsCursor cur(ws);
         E16 = cur.take<dn_half>(T * SD_C * 2);
         PE16 = cur.take<dn_half>(T * SD_C * 2);
@@ -525,38 +664,35 @@ struct SdLayout {
         b1 = cur.take<dn_half>(2 * half_bytes);
         b2 = b1 ? reinterpret_cast<dn_half*>(reinterpret_cast<char*>(b1) + half_bytes) : nullptr;
         a32 = cur.take<float>(PT * SD_C * 4);
+        s0t = skips ? cur.take<float>(T * 512 * 4) : nullptr;
+        s1t = skips ? cur.take<float>(T * 256 * 4) : nullptr;
+#if !SD_SKIP0_EPILOGUE
+        if (skips) c32 = cur.take<float>(PT * 4 * 128 * 4);
+#endif
         total = cur.off;
     }
 };
 
-extern "C" int32_t gsr_sam_dec_num_weights(void) { return GSR_SAMD_W_COUNT; }
+// What SAM2's decoder has and SAM's has not.  SAM: {SD_EPS, NULL, NULL, NULL, false}.
+struct SdModel {
+    float eps;                      // layer_norm1..4 of the two-way layers
+    const dn_half* obj_tok;         // row 0 of the tokens (TOK = 8)
+    const float *feat_s0, *feat_s1; // the skips of the up-scaling
+    bool sigmoid;                   // the IoU head's last activation
+};
 
-extern "C" size_t gsr_sam_decode_workspace_bytes(int32_t g, int32_t P) {
-    if (g < 1 || g > SD_MAX_GRID || P < 1 || P > SD_MAX_POINTS) return 0;
-    return SdLayout(g, P, nullptr).total;
-}
-
-extern "C" int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, int32_t n_weights, const float* emb, const float* pe,
-                                  const float* points, int32_t P, int32_t image_size, void* ws, size_t ws_bytes, float* low_res,
-                                  float* iou, gsr_stream_t stream_) {
-    GSR_TRY(sd_check_grid(g));
-    GSR_TRY(sd_check_points(P));
-    if (image_size != 16 * g) { gsr_set_error("sam decoder: image_size %d is not 16 x grid %d", image_size, g); return GSR_E_INVALID; }
-    if (!weights_host || n_weights != GSR_SAMD_W_COUNT) {
-        gsr_set_error("sam decoder: the weight table is null or has %d entries (%d are needed)", n_weights, (int)GSR_SAMD_W_COUNT);
-        return GSR_E_INVALID;
-    }
-    for (int i = 0; i < n_weights; ++i)
-        if (!weights_host[i]) { gsr_set_error("sam decoder: weight %d of the table is null", i); return GSR_E_INVALID; }
-    if (!emb || !pe || !points || !low_res || !iou) { gsr_set_error("sam decoder: emb / pe / points / low_res / iou is null"); return GSR_E_INVALID; }
-    SdLayout lay(g, P, ws);
+// One body for both models.  The arguments are checked by the callers; weights_host has the GSR_SAMD_* slots.
+template <int TOK>
+static int sd_decode(const SdModel& model, int g, const void* const* weights_host, const float* emb, const float* pe, const float* points,
+                     int P, int image_size, void* ws, size_t ws_bytes, float* low_res, float* iou, hipStream_t s) {
+    const bool skips = model.feat_s0 != nullptr;
+    SdLayout lay(g, P, TOK, skips, ws);
     if (!ws || ws_bytes < lay.total) {
         gsr_set_error("ws_bytes: sam decoder workspace too small (%zu < %zu bytes)", ws_bytes, lay.total);
         return GSR_E_INVALID;
     }
-    hipStream_t s = static_cast<hipStream_t>(stream_);
     const int T = g * g;
-    const int64_t R = (int64_t)P * SD_TOK, PT = (int64_t)P * T;
+    const int64_t R = (int64_t)P * TOK, PT = (int64_t)P * T;
     auto W = [&](int i) { return static_cast<const dn_half*>(weights_host[i]); };
     auto lin = [&](const dn_half* x, int wi, int bi, void* out, int64_t M, int K, int N, int epi) -> int {
         return dn_linear(x, W(wi), bi < 0 ? nullptr : W(bi), nullptr, out, M, K, N, epi, s);
@@ -582,14 +718,15 @@ extern "C" int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, in
     // SD_PROMPT and the tokens
     GSR_TRY(sd_prompt(points, P, image_size, static_cast<const float*>(weights_host[GSR_SAMD_W_GAUSS]), W(GSR_SAMD_W_POINT1),
                     W(GSR_SAMD_W_NOT_A_POINT), lay.sparse, s));
-    hipLaunchKernelGGL(sd_tokens_kernel, dim3((unsigned)P), dim3(256), 0, s, W(GSR_SAMD_W_IOU_TOKEN), W(GSR_SAMD_W_MASK_TOKENS), lay.sparse,
-                       lay.tok0, q);
+    hipLaunchKernelGGL(sd_tokens_kernel<TOK>, dim3((unsigned)P), dim3(256), 0, s, model.obj_tok, W(GSR_SAMD_W_IOU_TOKEN),
+                       W(GSR_SAMD_W_MASK_TOKENS), lay.sparse, lay.tok0, q);
     GSR_LAUNCH_CHECK();
 
     // SD_IMAGE
     hipLaunchKernelGGL(sd_image_kernel, dim3((unsigned)((T * SD_C + 255) / 256)), dim3(256), 0, s, emb, pe, W(GSR_SAMD_W_NO_MASK), T, lay.E16,
                        lay.PE16);
     GSR_LAUNCH_CHECK();
+    if (skips) GSR_TRY(sd_skips(model.feat_s0, model.feat_s1, g, lay.s0t, lay.s1t, s));
     const int l0 = GSR_SAMD_W_LAYER0, l1 = GSR_SAMD_W_LAYER0 + GSR_SAMD_W_PER_LAYER, fin = GSR_SAMD_W_FINAL;
     GSR_TRY(lin(lay.PE16, l0 + GSR_SAMD_L_T2I + 2, l0 + GSR_SAMD_L_T2I + 3, lay.pe_proj[0], T, SD_C, SD_CI, DN_EPI_F32));
     GSR_TRY(lin(lay.PE16, l0 + GSR_SAMD_L_I2T + 0, l0 + GSR_SAMD_L_I2T + 1, lay.pe_proj[1], T, SD_C, SD_CI, DN_EPI_F32));
@@ -608,7 +745,7 @@ extern "C" int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, in
             GSR_TRY(lin(lay.x16, a + 2, -1, lay.b1, PT, SD_C, SD_CI, DN_EPI_BIAS));
             GSR_TRY(lin(lay.x16, a + 4, a + 5, lay.b2, PT, SD_C, SD_CI, DN_EPI_BIAS));
         }
-        GSR_TRY(sd_t2i(lay.qf, first ? lay.kx0 : lay.b1, kpe, first ? lay.v0 : lay.b2, P, T, first, 0.25f, lay.c16, s));
+        GSR_TRY(sd_t2i<TOK>(lay.qf, first ? lay.kx0 : lay.b1, kpe, first ? lay.v0 : lay.b2, P, T, first, 0.25f, lay.c16, s));
         return lin(lay.c16, a + 6, a + 7, q, R, SD_CI, SD_C, DN_EPI_RESID1);
     };
 
@@ -626,19 +763,19 @@ extern "C" int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, in
         }
         GSR_TRY(lin(lay.h16, sa + 0, sa + 1, lay.qf, R, SD_C, SD_C, DN_EPI_F32));
         GSR_TRY(lin(lay.h16, sa + 2, sa + 3, lay.kf, R, SD_C, SD_C, DN_EPI_F32));
-        hipLaunchKernelGGL(sd_self_attn_kernel, dim3((unsigned)P), dim3(64), 0, s, lay.qf, lay.kf, lay.vf, lay.c16);
+        hipLaunchKernelGGL(sd_self_attn_kernel<TOK>, dim3((unsigned)P), dim3(64), 0, s, lay.qf, lay.kf, lay.vf, lay.c16);
         GSR_LAUNCH_CHECK();
         GSR_TRY(lin(lay.c16, sa + 6, sa + 7, q, R, SD_C, SD_C, l == 0 ? DN_EPI_F32 : DN_EPI_RESID1));
-        GSR_TRY(norm(b + GSR_SAMD_L_NORM1, SD_EPS));
+        GSR_TRY(norm(b + GSR_SAMD_L_NORM1, model.eps));
         // SD_T2I
         GSR_TRY(t2i(b + GSR_SAMD_L_T2I, l == 0, lay.pe_proj[2 * l]));
-        GSR_TRY(norm(b + GSR_SAMD_L_NORM2, SD_EPS));
+        GSR_TRY(norm(b + GSR_SAMD_L_NORM2, model.eps));
         // SD_TOKENS: MLP
         GSR_TRY(addcast(q, nullptr, lay.h16));
         GSR_TRY(lin(lay.h16, b + GSR_SAMD_L_MLP + 0, b + GSR_SAMD_L_MLP + 1, lay.m16, R, SD_C, SD_MLP, DN_EPI_BIAS));
         GSR_TRY(relu(lay.m16, R * SD_MLP));
         GSR_TRY(lin(lay.m16, b + GSR_SAMD_L_MLP + 2, b + GSR_SAMD_L_MLP + 3, q, R, SD_MLP, SD_C, DN_EPI_RESID1));
-        GSR_TRY(norm(b + GSR_SAMD_L_NORM3, SD_EPS));
+        GSR_TRY(norm(b + GSR_SAMD_L_NORM3, model.eps));
         // SD_I2T
         const int it = b + GSR_SAMD_L_I2T;
         GSR_TRY(addcast(q, lay.tok0, lay.h16));
@@ -646,14 +783,15 @@ extern "C" int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, in
         GSR_TRY(lin(lay.h16, it + 2, it + 3, lay.kf, R, SD_C, SD_CI, DN_EPI_F32));
         GSR_TRY(lin(lay.h16b, it + 4, it + 5, lay.vf, R, SD_C, SD_CI, DN_EPI_F32));
         if (l > 0) GSR_TRY(lin(lay.x16, it + 0, -1, lay.b1, PT, SD_C, SD_CI, DN_EPI_BIAS));
-        GSR_TRY(sd_i2t(l == 0 ? lay.qx0 : lay.b1, lay.pe_proj[2 * l + 1], lay.kf, lay.vf, l == 0 ? lay.E16 : lay.x16, P, T, l == 0, W(it + 6),
-                     W(it + 7), W(b + GSR_SAMD_L_NORM4), W(b + GSR_SAMD_L_NORM4 + 1), lay.b2, lay.a32, lay.x16, s));
+        GSR_TRY(sd_i2t<TOK>(l == 0 ? lay.qx0 : lay.b1, lay.pe_proj[2 * l + 1], lay.kf, lay.vf, l == 0 ? lay.E16 : lay.x16, P, T, l == 0,
+                          W(it + 6), W(it + 7), W(b + GSR_SAMD_L_NORM4), W(b + GSR_SAMD_L_NORM4 + 1), model.eps, lay.b2, lay.a32, lay.x16,
+                          s));
     }
     GSR_TRY(t2i(fin, 0, lay.pe_proj[4]));
     GSR_TRY(norm(fin + 8, SD_EPS_FINAL));
 
     // SD_HEADS
-    hipLaunchKernelGGL(sd_heads_gather_kernel, dim3((unsigned)P), dim3(256), 0, s, q, P, lay.heads16);
+    hipLaunchKernelGGL(sd_heads_gather_kernel<TOK>, dim3((unsigned)P), dim3(256), 0, s, q, P, lay.heads16);
     GSR_LAUNCH_CHECK();
     for (int k = 0; k < 4; ++k) {
         const int a = k == 0 ? GSR_SAMD_W_IOU : GSR_SAMD_W_HYPER + 6 * (k - 1);
@@ -666,7 +804,62 @@ extern "C" int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, in
         else
             GSR_TRY(lin(lay.t16b, a + 4, a + 5, lay.hyper + (int64_t)(k - 1) * P * 32, P, SD_C, 32, DN_EPI_F32));
     }
+    if (model.sigmoid) {
+        hipLaunchKernelGGL(sd_sigmoid_kernel, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, s, iou, (int64_t)3 * P);
+        GSR_LAUNCH_CHECK();
+    }
     // SD_UP
     const int up = GSR_SAMD_W_UP;
-    return sd_upscale(lay.x16, g, P, W(up), W(up + 1), W(up + 2), W(up + 3), W(up + 4), W(up + 5), lay.hyper, lay.a32, lay.b1, low_res, s);
+    return sd_upscale(lay.x16, g, P, W(up), W(up + 1), W(up + 2), W(up + 3), W(up + 4), W(up + 5), lay.hyper, lay.s0t, lay.s1t, lay.a32,
+                      lay.b1, lay.c32, low_res, s);
+}
+
+// the refusals the two models share; `count` is the length of the model's weight table
+static int sd_decode_check(int g, const void* const* weights_host, int n_weights, int count, const float* emb, const float* pe,
+                           const float* points, int P, int image_size, const float* low_res, const float* iou) {
+    GSR_TRY(sd_check_grid(g));
+    GSR_TRY(sd_check_points(P));
+    if (image_size != 16 * g) { gsr_set_error("sam decoder: image_size %d is not 16 x grid %d", image_size, g); return GSR_E_INVALID; }
+    if (!weights_host || n_weights != count) {
+        gsr_set_error("sam decoder: the weight table is null or has %d entries (%d are needed)", n_weights, count);
+        return GSR_E_INVALID;
+    }
+    for (int i = 0; i < n_weights; ++i)
+        if (!weights_host[i]) { gsr_set_error("sam decoder: weight %d of the table is null", i); return GSR_E_INVALID; }
+    if (!emb || !pe || !points || !low_res || !iou) { gsr_set_error("sam decoder: emb / pe / points / low_res / iou is null"); return GSR_E_INVALID; }
+    return GSR_OK;
+}
+
+extern "C" int32_t gsr_sam_dec_num_weights(void) { return GSR_SAMD_W_COUNT; }
+
+extern "C" size_t gsr_sam_decode_workspace_bytes(int32_t g, int32_t P) {
+    if (g < 1 || g > SD_MAX_GRID || P < 1 || P > SD_MAX_POINTS) return 0;
+    return SdLayout(g, P, SD_TOK, false, nullptr).total;
+}
+
+extern "C" int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, int32_t n_weights, const float* emb, const float* pe,
+                                  const float* points, int32_t P, int32_t image_size, void* ws, size_t ws_bytes, float* low_res,
+                                  float* iou, gsr_stream_t stream_) {
+    GSR_TRY(sd_decode_check(g, weights_host, n_weights, GSR_SAMD_W_COUNT, emb, pe, points, P, image_size, low_res, iou));
+    const SdModel sam = {SD_EPS, nullptr, nullptr, nullptr, false};
+    return sd_decode<SD_TOK>(sam, g, weights_host, emb, pe, points, P, image_size, ws, ws_bytes, low_res, iou,
+                             static_cast<hipStream_t>(stream_));
+}
+
+// ---------------------------------------------------------------- SAM2
+extern "C" int32_t gsr_sam2_dec_num_weights(void) { return GSR_SAM2D_W_COUNT; }
+
+extern "C" size_t gsr_sam2_decode_workspace_bytes(int32_t g, int32_t P) {
+    if (g < 1 || g > SD_MAX_GRID || P < 1 || P > SD_MAX_POINTS) return 0;
+    return SdLayout(g, P, SD_TOK2, true, nullptr).total;
+}
+
+extern "C" int32_t gsr_sam2_decode(int32_t g, const void* const* weights_host, int32_t n_weights, const float* feat_s0,
+                                   const float* feat_s1, const float* emb, const float* pe, const float* points, int32_t P,
+                                   int32_t image_size, void* ws, size_t ws_bytes, float* low_res, float* iou, gsr_stream_t stream_) {
+    GSR_TRY(sd_decode_check(g, weights_host, n_weights, GSR_SAM2D_W_COUNT, emb, pe, points, P, image_size, low_res, iou));
+    if (!feat_s0 || !feat_s1) { gsr_set_error("sam2 decoder: feat_s0 / feat_s1 is null"); return GSR_E_INVALID; }
+    const SdModel sam2 = {SD_EPS_FINAL, static_cast<const dn_half*>(weights_host[GSR_SAM2D_W_OBJ_TOKEN]), feat_s0, feat_s1, true};
+    return sd_decode<SD_TOK2>(sam2, g, weights_host, emb, pe, points, P, image_size, ws, ws_bytes, low_res, iou,
+                              static_cast<hipStream_t>(stream_));
 }

@@ -147,6 +147,9 @@ __global__ void __launch_bounds__(256) dn_linear_kernel(const dn_half* __restric
                     static_cast<float*>(out_)[m * N + n] = v;
                 } else if (EPI == DN_EPI_POS) {         // SAM's embedding: (acc + bias) + fp32(pos[m][n]), stored as fp32
                     static_cast<float*>(out_)[m * N + n] = v + (float)lam[m * N + n];
+                } else if (EPI == DN_EPI_SKIP_GELU) {   // SAM2's up-scaling: one fp32 addition after the bias's, then the GELU
+                    const float skip = reinterpret_cast<const float*>(lam)[(m % Np) * N + n];
+                    static_cast<dn_half*>(out_)[m * N + n] = (dn_half)vit_gelu(v + skip);
                 } else {                                // DN_EPI_EMBED
                     const int64_t b = m / Np, p = m - b * Np;
                     static_cast<float*>(out_)[(b * T + prefix + p) * N + n] = v;
@@ -160,7 +163,8 @@ __global__ void __launch_bounds__(256) dn_linear_kernel(const dn_half* __restric
 static int dn_linear_launch(const dn_half* x, const dn_half* w, const dn_half* bias, const dn_half* lam, void* out, int64_t M, int K,
                             int N, int epi, hipStream_t s, DnEmbedRows embed) {
     if (!x || !w || !out) { gsr_set_error("dino linear: x / w / out is null"); return GSR_E_INVALID; }
-    if ((epi == DN_EPI_RESID || epi == DN_EPI_POS) && !lam) { gsr_set_error("dino linear: the residual epilogue needs lambda"); return GSR_E_INVALID; }
+    if ((epi == DN_EPI_RESID || epi == DN_EPI_POS || epi == DN_EPI_SKIP_GELU) && !lam) { gsr_set_error("dino linear: the residual epilogue needs lambda"); return GSR_E_INVALID; }
+    if (epi == DN_EPI_SKIP_GELU && embed.Np < 1) { gsr_set_error("dino linear: the skip epilogue needs the rows of its table"); return GSR_E_INVALID; }
     if ((M + DN_BM - 1) / DN_BM > 0x7fffffffLL || (N + DN_BM - 1) / DN_BM > 65535) {
         gsr_set_error("dino linear: M %lld or N %d exceeds the launch grid", (long long)M, N);
         return GSR_E_UNSUPPORTED;
@@ -180,6 +184,7 @@ static int dn_linear_launch(const dn_half* x, const dn_half* w, const dn_half* b
     case DN_EPI_RESID1: DN_LINEAR_LAUNCH(DN_EPI_RESID1); break;
     case DN_EPI_F32: DN_LINEAR_LAUNCH(DN_EPI_F32); break;
     case DN_EPI_POS: DN_LINEAR_LAUNCH(DN_EPI_POS); break;
+    case DN_EPI_SKIP_GELU: DN_LINEAR_LAUNCH(DN_EPI_SKIP_GELU); break;
     default: gsr_set_error("dino linear: epilogue %d is not one of GSR_DINO_EPI_*", epi); return GSR_E_INVALID;
     }
 #undef DN_LINEAR_LAUNCH

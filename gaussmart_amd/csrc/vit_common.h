@@ -19,7 +19,7 @@ typedef float vit_f32x16 __attribute__((ext_vector_type(16)));
     } while (0)
 
 // ---------------------------------------------------------------- DN_LINEAR and DN_NORM (vit.hip)
-// 0..3 are DINO's and keep their bits; 4..6 were added for SAM's encoder (no LayerScale, fp32 stores).
+// 0..3 are DINO's and keep their bits; 4..6 were added for SAM's encoder (no LayerScale, fp32 stores), 7 for SAM2's decoder.
 enum {
     DN_EPI_BIAS = 0,    // fp16(acc + bias)
     DN_EPI_GELU = 1,    // fp16(gelu(acc + bias))
@@ -27,10 +27,12 @@ enum {
     DN_EPI_EMBED = 3,   // DINO's patch rows behind the prefix tokens, fp32
     DN_EPI_RESID1 = 4,  // resid = resid + (acc + bias), fp32
     DN_EPI_F32 = 5,     // acc + bias, fp32
-    DN_EPI_POS = 6      // (acc + bias) + fp32(lam[m N + n]), fp32: lam is an fp16 [M,N] table here
+    DN_EPI_POS = 6,     // (acc + bias) + fp32(lam[m N + n]), fp32: lam is an fp16 [M,N] table here
+    DN_EPI_SKIP_GELU = 7    // fp16(gelu((acc + bias) + tab[(m mod Np) N + n])): lam points to an F32 [Np,N] table here
 };
 
-// DN_EPI_EMBED's scatter: row b Np + p of the product is stored as row b T + prefix + p.  No other epilogue reads it.
+// DN_EPI_EMBED's scatter: row b Np + p of the product is stored as row b T + prefix + p.  DN_EPI_SKIP_GELU reads Np alone
+// (the rows of its table); no other epilogue reads any of it.
 struct DnEmbedRows {
     int64_t Np;
     int T, prefix;

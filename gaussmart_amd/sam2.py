@@ -3,7 +3,8 @@
 stability_score_thresh=0.92)) with the image encoder (the Hiera trunk, the FPN neck and the three maps the mask decoder reads)
 computed by the kernels of csrc/sam2.hip (include/gsr.h: HV_EMBED, HV_LINEAR, HV_ATTN, HV_POOL, HV_NECK) and the mask selection
 by SM_SCORE / SM_NMS / SM_EMIT with SAM2's one-step resampling.  The prompt encoder and the mask decoder are transformers' own
-torch modules, run on the device in fp32 as they are.
+torch modules, run on the device in fp32 as they are (decoder="torch", the default), or the kernels of csrc/sam_decoder.hip
+(decoder="hip"; include/gsr.h: the SD_* rules with the S2D_* deltas, fp16 operands).
 
     from gaussmart_amd.sam2 import Sam2MaskGenerator, load_sam2_weights
     gen = Sam2MaskGenerator(load_sam2_weights("/models/sam2-hiera-large"))     # a LOCAL directory, see load_sam2_weights
@@ -19,8 +20,10 @@ What differs from the reference, on purpose:
     generator ignores it.
   * a stage whose grid is not a multiple of its window is refused (Hiera pads such windows).  sam2-hiera-large's windows
     (8, 4, 16, 8) divide its grids at 1024 x 1024; the (8, 4, 14, 7) of the tiny, small and base-plus checkpoints do not.
-  * decoder="hip" is not built: SAM2's decoder has a fourth mask token, an object-score token and the two high-resolution
-    skips, which csrc/sam_decoder.hip does not have.
+  * decoder="hip": both decoders have four mask tokens; SAM2's differs from SAM's in an object-score token in front (eight
+    tokens per point), eps 1e-5 in the four block norms, the two high-resolution skips of the up-scaling and a sigmoid on
+    the IoU head.  Not built: the object-score output, boxes and mask prompts, several points per prompt, single-mask output
+    with its dynamic stability selection.  host=True runs the torch modules only and refuses decoder="hip".
 `sam2_host`, `decode_host2` and `sam.select_host(direct=True)` are the torch twins (any device): they back `host=True` and the
 tests."""
 import ctypes as C
@@ -55,6 +58,23 @@ ENC_BLOCK = ("layer_norm1.weight", "layer_norm1.bias", "attn.qkv.weight", "attn.
              "layer_norm2.weight", "layer_norm2.bias", "mlp.proj_in.weight", "mlp.proj_in.bias", "mlp.proj_out.weight", "mlp.proj_out.bias",
              "proj.weight", "proj.bias")
 assert len(ENC_BLOCK) == _lib.GSR_SAM2_W_PER_BLOCK
+
+# the weight table of gsr_sam2_decode, in the order of include/gsr.h: gsr_sam_decode's slots under Sam2Model.state_dict()'s names
+# (row 1 of point_embed.weight in the slot of SAM's point_embed.1.weight), then the object-score token
+POINT_EMBED, OBJ_TOKEN = "prompt_encoder.point_embed.weight", "mask_decoder.obj_score_token.weight"
+_RENAMED = (("out_proj.", "o_proj."), ("mlp.lin1.", "mlp.proj_in."), ("mlp.lin2.", "mlp.proj_out."))
+
+
+def _sam2_name(k):
+    for a, b in _RENAMED:
+        k = k.replace(a, b)
+    return k
+
+
+DEC_HEAD = (S1.DEC_HEAD[0], POINT_EMBED) + S1.DEC_HEAD[2:]
+DEC_LAYER, DEC_FINAL = tuple(_sam2_name(k) for k in S1.DEC_LAYER), tuple(_sam2_name(k) for k in S1.DEC_FINAL)
+assert len(DEC_HEAD) == _lib.GSR_SAMD_W_LAYER0 and DEC_HEAD[_lib.GSR_SAMD_W_POINT1] == POINT_EMBED
+assert _lib.GSR_SAM2D_W_OBJ_TOKEN == _lib.GSR_SAMD_W_COUNT and _lib.GSR_SAM2D_W_COUNT == _lib.GSR_SAMD_W_COUNT + 1
 
 
 @dataclass
@@ -279,6 +299,31 @@ class Sam2Weights:
         assert len(out) == _lib.GSR_SAM2_W_BLOCK0 + _lib.GSR_SAM2_W_PER_BLOCK * cfg.total_blocks + _lib.GSR_SAM2_W_NECK
         return out
 
+    def decoder_table(self):
+        """The tensors of gsr_sam2_decode's weight table, in its order, on the tensors' device: fp16 copies (self.tensors keeps
+        its fp32 ones), except the positional matrix (fp32, as it is).  The two transposed convolutions [ci,co,2,2] are re-laid
+        as [(dy 2 + dx) co_n + co][ci] and their biases repeated per tap, as SamWeights.decoder_table does."""
+        t, md = self.tensors, "mask_decoder."
+        names = list(DEC_HEAD)
+        for l in range(S1.DEC_LAYERS):
+            names += [f"{md}transformer.layers.{l}.{k}" for k in DEC_LAYER]
+        names += [f"{md}transformer.{k}" for k in DEC_FINAL] + [md + k for k in S1.DEC_UP + S1.DEC_HYPER + S1.DEC_IOU] + [OBJ_TOKEN]
+        out = []
+        for k in names:
+            v = t[k]
+            if k == DEC_HEAD[0]:
+                out.append(v.to(torch.float32).contiguous())
+                continue
+            if k == POINT_EMBED:
+                v = v[1:2]
+            elif k.startswith(md + "upscale_conv") and k.endswith(".weight"):
+                v = v.permute(2, 3, 1, 0).reshape(4 * v.shape[1], v.shape[0])
+            elif k.startswith(md + "upscale_conv"):
+                v = v.repeat(4)
+            out.append(v.to(torch.float16).contiguous())
+        assert len(out) == _lib.GSR_SAM2D_W_COUNT
+        return out
+
     def sub(self, prefix):
         """The tensors under `prefix`, with it removed (a sub-module's state dict), in fp32."""
         return {k[len(prefix):]: t.to(torch.float32) for k, t in self.tensors.items() if k.startswith(prefix)}
@@ -451,22 +496,22 @@ def preprocess2(image_u8, image_size=1024):
 # ---------------------------------------------------------------- the generator
 class Sam2MaskGenerator(S1.SamMaskGenerator):
     """The reference's SAM2AutomaticMaskGenerator for one full-image crop, with SamMaskGenerator's interface.  host=True: the
-    encoder through transformers' Sam2Model in fp32 and the selection through sam.select_host(direct=True), on the same device."""
+    encoder through transformers' Sam2Model in fp32 and the selection through sam.select_host(direct=True), on the same device.
+    decoder="hip": the prompt encoder and the mask decoder through gsr_sam2_decode instead of transformers' modules."""
 
     def __init__(self, weights, points_per_side=32, points_per_batch=64, pred_iou_thresh=0.86, stability_score_thresh=0.92,
                  stability_score_offset=1.0, box_nms_thresh=0.7, host=False, device="cuda", decoder="torch"):
-        if decoder == "hip":
-            raise NotImplementedError("sam2: decoder='hip' is not built: SAM2's mask decoder has a fourth mask token, an object-score "
-                                      "token and the two high-resolution skips (conv_s0 / conv_s1), which csrc/sam_decoder.hip lacks")
-        if decoder != "torch":
-            raise ValueError(f"sam2: decoder {decoder!r} is not 'torch'")
+        if decoder not in ("torch", "hip"):
+            raise ValueError(f"sam2: decoder {decoder!r} is not 'torch' or 'hip'")
+        if host and decoder == "hip":
+            raise NotImplementedError("sam2: host=True runs the torch modules only; decoder='hip' is not built for it")
         self.weights, self.config, self.device, self.host = weights, weights.config, torch.device(device), bool(host)
         self.decoder = decoder
         self.points_per_side, self.points_per_batch = int(points_per_side), int(points_per_batch)
         self.pred_iou_thresh, self.stability_score_thresh = float(pred_iou_thresh), float(stability_score_thresh)
         self.stability_score_offset, self.box_nms_thresh = float(stability_score_offset), float(box_nms_thresh)
         self.encoder = None if host else Sam2ImageEncoder(weights)
-        self._host_model = self._modules = None
+        self._host_model = self._modules = self._hip = None
         self.last_ms = {}
 
     def _decoder(self):
@@ -487,10 +532,59 @@ class Sam2MaskGenerator(S1.SamMaskGenerator):
             emb = self.encoder.encode(x)
         return dict(emb=[m.to(torch.float32) for m in emb], input_size=input_size, mask_size=mask_size)
 
+    # -- the weight table of gsr_sam2_decode and the positional embedding of the grid (host_decoder2's wide, in fp32)
+    def _decoder_hip(self):
+        if self._hip is None:
+            if self.config.fpn_hidden_size != S1.DECODER_CHANNELS:
+                raise NotImplementedError(f"sam2: decoder='hip' is built for {S1.DECODER_CHANNELS} channels, not {self.config.fpn_hidden_size}")
+            g = self.config.image_size // 16
+            w = Sam2Weights.__new__(Sam2Weights)
+            w.config = self.config
+            w.tensors = {k: t.to(self.device) for k, t in self.weights.tensors.items() if not k.startswith(VISION)}
+            tensors = w.decoder_table()
+            table = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+            G = tensors[0]
+            c = (torch.arange(g, device=self.device, dtype=torch.float32) + 0.5) / g
+            xy = 2 * torch.stack([c[None, :].expand(g, g), c[:, None].expand(g, g)], -1) - 1
+            arg = 2 * np.pi * (xy @ G)
+            wide = torch.cat([torch.sin(arg), torch.cos(arg)], -1).permute(2, 0, 1).contiguous()
+            self._hip = dict(tensors=tensors, table=table, n=len(tensors), wide=wide)
+        return self._hip
+
+    def _decode_hip(self, emb, points):
+        if not all(m.is_cuda for m in emb):
+            raise _lib.GsrError("sam2: decoder='hip' needs the three maps on the device (no CPU path; see decode_host2)")
+        d, L, S = self._decoder_hip(), _lib.lib(), self.config.image_size
+        g, D = S // 16, self.config.fpn_hidden_size
+        dev = emb[2].device
+        s0, s1, top = (m.reshape(ch, n, n).to(torch.float32).contiguous() for m, ch, n in zip(emb, (D // 8, D // 4, D), (4 * g, 2 * g, g)))
+        pts = points.to(device=dev, dtype=torch.float32).reshape(-1, 2).contiguous()
+        P = pts.shape[0]
+        low = torch.empty(P, 3, 4 * g, 4 * g, dtype=torch.float32, device=dev)
+        iou = torch.empty(P, 3, dtype=torch.float32, device=dev)
+        if P == 0:
+            return low, iou
+        budget = S1.DECODER_WORKSPACE_BUDGET
+        one = L.gsr_sam2_decode_workspace_bytes(g, 1)
+        per = max(1, L.gsr_sam2_decode_workspace_bytes(g, 2) - one)
+        chunk = int(min(P, 65535, max(1, 1 + (budget - one) // per)))
+        while chunk > 1 and L.gsr_sam2_decode_workspace_bytes(g, chunk) > budget:
+            chunk -= 1
+        nbytes = L.gsr_sam2_decode_workspace_bytes(g, chunk)
+        ws = workspace(nbytes, dev)
+        for k in range(0, P, chunk):
+            n = min(chunk, P - k)
+            _lib.check(L.gsr_sam2_decode(g, d["table"], d["n"], ptr(s0), ptr(s1), ptr(top), ptr(d["wide"]), ptr(pts[k:k + n]), n, S,
+                                         ptr(ws), nbytes, ptr(low[k:k + n]), ptr(iou[k:k + n]), stream(dev)))
+        return low, iou
+
     @torch.no_grad()
     def decode(self, emb, points):
-        """emb: the three maps, points f32 [P,2] (x, y) in the S x S frame -> (low_res f32 [P,3,L,L], iou f32 [P,3]):
-        transformers' modules in fp32, points_per_batch at a time."""
+        """emb: the three maps, points f32 [P,2] (x, y) in the S x S frame -> (low_res f32 [P,3,L,L], iou f32 [P,3]).
+        decoder="torch": transformers' modules in fp32, points_per_batch at a time; "hip": gsr_sam2_decode, as many points per
+        call as sam.DECODER_WORKSPACE_BUDGET bytes of workspace hold."""
+        if self.decoder == "hip":
+            return self._decode_hip(emb, points)
         low, iou = decode_host2(self.weights, emb, points, torch.float32, self.device, self._decoder(), self.points_per_batch)
         return low.to(torch.float32).contiguous(), iou.to(torch.float32).contiguous()
 

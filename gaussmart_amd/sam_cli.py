@@ -3,6 +3,7 @@
     python -m gaussmart_amd.sam_cli -s SCAN -o OUT --views i j k ... --sam_checkpoint FILE_OR_DIR [--model_type vit_h|vit_l|vit_b] [--host]
         [--decoder torch|hip]
     python -m gaussmart_amd.sam_cli --sam2 -s SCAN -o OUT --views ... --sam_checkpoint DIR [--model_type large|base_plus|small|tiny] [--host]
+        [--decoder torch|hip]
         [--points_per_side 32] [--pred_iou_thresh 0.86] [--stability_score_thresh 0.92]      (the reference's values)
 
 View i is the i-th file of sorted(listdir(SCAN/images)).  Writes OUT/segments/masks/segments_NNN.npz (keys masks, boxes,
@@ -14,8 +15,11 @@ runs the prompt encoder and the mask decoder on the kernels of csrc/sam_decoder.
 transformers' modules in fp32.
 --sam2 is the reference's --sam2 branch (SAM2AutomaticMaskGenerator on sam2-hiera-large): the Hiera encoder and its neck on
 the kernels of csrc/sam2.hip, the same files and JSON lines.  Its --sam_checkpoint is a LOCAL directory under transformers'
-Sam2Model names (gaussmart_amd.sam2.load_sam2_weights); its decoder is transformers' (--decoder hip is refused).
-Not built: crop layers, min_mask_region_area, and the camera clustering that picks the views (step 1).
+Sam2Model names (gaussmart_amd.sam2.load_sam2_weights).  --decoder hip runs SAM2's prompt encoder and mask decoder on the same
+kernels of csrc/sam_decoder.hip (eight tokens per point, the two high-resolution skips, a sigmoid on the IoU head); with --host
+it is refused, since --host runs the torch modules only.
+Not built: crop layers, min_mask_region_area, the camera clustering that picks the views (step 1), and for SAM2 the
+object-score output, boxes and mask prompts, several points per prompt and single-mask output.
 """
 import argparse
 import json

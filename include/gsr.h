@@ -49,8 +49,9 @@ extern "C" {
                                 16: frame kernels of the trajectory and viewer pictures (gsr_frame_*);
                                 17: DINOv3 ViT encoder and its cosine term (GsrDinoConfig, gsr_dino_*);
                                 18: SAM image encoder and mask selection (GsrSamConfig, gsr_sam_*); still 18 with SAM's
-                                    prompt encoder and mask decoder (gsr_sam_dec_*, gsr_sam_decode) and with SAM2's image
-                                    encoder (GsrSam2Config, gsr_sam2_*): additions only, no existing struct or signature
+                                    prompt encoder and mask decoder (gsr_sam_dec_*, gsr_sam_decode), with SAM2's image
+                                    encoder (GsrSam2Config, gsr_sam2_*) and with SAM2's prompt encoder and mask decoder
+                                    (gsr_sam2_dec_*, gsr_sam2_decode): additions only, no existing struct or signature
                                     changed */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
@@ -1318,7 +1319,7 @@ int32_t gsr_sam_nms(const float* boxes, const float* scores, const uint8_t* keep
  * transposed convolutions (sam_decoder.hip; Python: gaussmart_amd/sam.py).  g = image_size / 16 with 1 <= g <= 64, T = g g (any
  * value); P points, 1 <= P <= 65535.  One prompt is ONE foreground point (label 1) plus the padding token: 7 tokens per point
  * (iou, mask 0..3, point, not-a-point).  multimask output: masks 1..3 and IoU columns 1..3; mask 0's hypernetwork is not
- * computed.  Boxes, mask prompts, several points per prompt and SAM2's mask decoder are not built.
+ * computed.  Boxes, mask prompts and several points per prompt are not built.  SAM2's decoder is the next section.
  * Precision: every weight is fp16 except the positional matrix; every product with a weight is DN_LINEAR (fp16 operands, one
  * k-ascending fp32 chain per element, rows independent); LayerNorm statistics (DN_NORM's formula), softmax and the token stream
  * are fp32; the per-point image stream is STORED AS fp16 between stages.  No split-K, no float atomics: a point's bits do not
@@ -1400,6 +1401,61 @@ size_t gsr_sam_decode_workspace_bytes(int32_t g, int32_t P);
 int32_t gsr_sam_decode(int32_t g, const void* const* weights_host, int32_t n_weights, const float* emb, const float* pe,
                        const float* points, int32_t P, int32_t image_size, void* ws, size_t ws_bytes, float* low_res, float* iou,
                        gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- SAM2: the prompt encoder and the mask decoder
+ * transformers' Sam2PromptEncoder and Sam2MaskDecoder (models/sam2/modeling_sam2.py, stock configuration) for one foreground
+ * point per prompt and multimask output, on the kernels of the section above (sam_decoder.hip; Python: gaussmart_amd/sam2.py).
+ * Sizes, limits and precision are SD_*'s: hidden 256, two two-way layers, 8 heads, widths 256 and 128, MLP 2048 with ReLU, four
+ * mask tokens, skip_first_layer_pe, 1 <= g <= 64, 1 <= P <= 65535, fp16 operands with one k-ascending fp32 chain per element,
+ * fp32 token stream, statistics and softmax, the per-point image stream stored as fp16, no split-K, no float atomics, a
+ * point's bits independent of the other points of the call.  Every SD_* rule holds as written except for these deltas:
+ *   S2D_TOKENS 8 tokens per point: obj_score_token, iou_token, mask tokens 0..3, the point, not-a-point.  The IoU token is
+ *              row 1 and the mask tokens are rows 2..5; wherever SD_TOKENS, SD_T2I and SD_I2T say 7, read 8.  The object-score
+ *              token takes part in every attention.  Its head (pred_obj_score_head) is NOT computed: the automatic mask
+ *              generator ignores the object score, and so does gaussmart_amd.sam2.decode_host2.
+ *   S2D_EPS    layer_norm1..4 of both two-way layers are plain nn.LayerNorm: eps 1e-5 (SAM: 1e-6).  layer_norm_final_attn
+ *              keeps 1e-5 and upscale_layer_norm keeps 1e-6.
+ *   S2D_UP     the two high-resolution maps of the image encoder (gsr_sam2_encode's out0 and out1), the same for every point
+ *              and never copied per point: feat_s0 f32 [32,4g,4g], feat_s1 f32 [64,2g,2g].  u = (conv1(stream) + bias) +
+ *              feat_s1[co][2 y + dy][2 x + dx]: ONE fp32 addition after the bias's, BEFORE the statistics of the channel
+ *              LayerNorm over 64 (eps 1e-6), then exact GELU, ROUNDED TO fp16.  c2 = fp16(gelu((conv2(.) + bias) + feat_s0[co]
+ *              [4 y + 2 dy1 + dy2][4 x + 2 dx1 + dx2])): ONE fp32 addition after the bias's, before the GELU, in the product's
+ *              epilogue.  Once per call the two maps are re-laid as f32 [T,4,64] and f32 [T,4,4,32], the layouts of the two
+ *              convolutions' outputs (tap-major).
+ *   S2D_HEADS  iou = 1 / (1 + expf(-z)) on the IoU head's fp32 output z (columns 1..3): the negation exact, expf precise, the
+ *              addition and the quotient one fp32 rounding each.
+ * SD_PROMPT holds as it is with row 1 of prompt_encoder.point_embed.weight [4,256] in point_embed.1's place.
+ * Weight table of gsr_sam2_decode: gsr_sam2_dec_num_weights() (= GSR_SAM2D_W_COUNT = 119) entries.  Entries 0 ..
+ * GSR_SAMD_W_COUNT - 1 are GSR_SAMD_*'s slots under Sam2Model.state_dict()'s names: o_proj in the out_proj slots, mlp.proj_in /
+ * mlp.proj_out in the mlp.lin1 / mlp.lin2 slots, row 1 of prompt_encoder.point_embed.weight in GSR_SAMD_W_POINT1; then
+ *   GSR_SAM2D_W_OBJ_TOKEN mask_decoder.obj_score_token.weight [1,256].
+ * Entry points (caller's stream, caller's buffers, nothing synchronises):
+ *   gsr_sam2_dec_t2i     gsr_sam_dec_t2i with q f32 [P,8,128] and out fp16 [P,8,128].
+ *   gsr_sam2_dec_i2t     gsr_sam_dec_i2t with k, v f32 [P,8,128] and layer_norm4's eps (> 0) as an argument; the workspace of
+ *                        gsr_sam2_dec_i2t_workspace_bytes.
+ *   gsr_sam2_dec_upscale gsr_sam_dec_upscale with S2D_UP's feat_s0 and feat_s1; ws: gsr_sam2_dec_upscale_workspace_bytes.
+ *   gsr_sam2_decode      everything: feat_s0, feat_s1 as above; emb, pe f32 [256,g,g]; points f32 [P,2]; image_size = 16 g;
+ *                        low_res f32 [P,3,4g,4g]; iou f32 [P,3].  ws: gsr_sam2_decode_workspace_bytes(g, P).
+ * GSR_E_INVALID before any launch: g outside 1 .. 64, P outside 1 .. 65535, image_size != 16 g, a null pointer or a null
+ * table entry, a table of the wrong length, a short workspace.  The *_workspace_bytes functions return 0 for a refused shape.
+ * Not built: the object-score output, boxes and mask prompts, several points per prompt, single-mask output with its dynamic
+ * stability selection. */
+enum { GSR_SAM2D_W_OBJ_TOKEN = GSR_SAMD_W_COUNT, GSR_SAM2D_W_COUNT = GSR_SAMD_W_COUNT + 1 };
+int32_t gsr_sam2_dec_t2i(const float* q, const void* kx, const float* kpe, const void* v, int32_t P, int32_t T, int32_t shared,
+                         void* out, gsr_stream_t stream);
+size_t gsr_sam2_dec_i2t_workspace_bytes(int32_t P, int32_t T);
+int32_t gsr_sam2_dec_i2t(const void* qx, const float* qpe, const float* k, const float* v, const void* x, int32_t P, int32_t T,
+                         int32_t shared, const void* out_w, const void* out_b, const void* ln_w, const void* ln_b, float eps, void* ws,
+                         size_t ws_bytes, void* x_out, gsr_stream_t stream);
+size_t gsr_sam2_dec_upscale_workspace_bytes(int32_t g, int32_t P);
+int32_t gsr_sam2_dec_upscale(const void* x, int32_t g, int32_t P, const void* conv1_w, const void* conv1_b, const void* ln_w,
+                             const void* ln_b, const void* conv2_w, const void* conv2_b, const float* hyper, const float* feat_s0,
+                             const float* feat_s1, void* ws, size_t ws_bytes, float* low_res, gsr_stream_t stream);
+int32_t gsr_sam2_dec_num_weights(void);
+size_t gsr_sam2_decode_workspace_bytes(int32_t g, int32_t P);
+int32_t gsr_sam2_decode(int32_t g, const void* const* weights_host, int32_t n_weights, const float* feat_s0, const float* feat_s1,
+                        const float* emb, const float* pe, const float* points, int32_t P, int32_t image_size, void* ws,
+                        size_t ws_bytes, float* low_res, float* iou, gsr_stream_t stream);
 
 /* ---------------------------------------------------------------- SAM2: the Hiera image encoder and its FPN neck
  * transformers' Sam2VisionModel (models/sam2/modeling_sam2.py: Sam2HieraDetModel and Sam2VisionNeck) plus what

@@ -1,9 +1,15 @@
 """Time SAM2 mask generation on one GPU: the Hiera encoder and FPN neck of csrc/sam2.hip, whole and stage by stage at 1024x1024,
 next to transformers' Sam2Model.get_image_embeddings in fp32 (the reference's precision) and in fp16 on the same GPU; HV_ATTN
 per block kind of Hiera-large (8x8, 4x4 and 16x16 windows, the three pooled stage starts, the global block over 4096 keys);
-the one-step mask selection next to its torch twin; and an image's time split into embed / decode / select.
+the one-step mask selection next to its torch twin; the decoder kernels of csrc/sam_decoder.hip with SAM2's eight tokens and
+two skips, stage by stage and as a whole for 1024 points, next to decode_host2 in fp32 and in fp16; and an image's time split
+into embed / decode / select with either decoder.
 
-    python scripts/sam2_bench.py [--out profiles/sam2_bench.txt] [--model_type large] [--points_per_side 32]
+    python scripts/sam2_bench.py [--out profiles/sam2_bench.txt] [--model_type large] [--points_per_side 32] [--ab_lib FILE]
+
+--ab_lib: a second build of the library with feat_s0 added by a kernel of its own instead of conv2's epilogue (`make -C
+gaussmart_amd/csrc BUILD=build_ab OUT=../lib_ab/libgsr_hip.so EXTRA_DEFS=-DSD_SKIP0_EPILOGUE=0`); its up-scaling is timed in
+alternation with the product's, in the same process.
 
 Random weights (gaussmart_amd.sam2.random_sam2_weights) and seeded inputs: nothing outside the repository is read.  Every
 figure is the median of `--repeats` timed calls (device events around one call each, after `--warmup` untimed calls of the
@@ -201,20 +207,141 @@ def selection(dev, args, out, points=1024):
         torch.cuda.empty_cache()
 
 
-def image(cfg, w, dev, args, out):
+CHUNK = 256         # points per call of the stage entry points: about what sam.DECODER_WORKSPACE_BUDGET gives the whole decoder at g = 64
+
+
+def decoder_stages(cfg, w, dev, args, out, points=1024):
+    """The stage entry points of csrc/sam_decoder.hip with SAM2's eight tokens at the grid of `cfg` (random inputs of the right
+    shapes).  Every entry is the time of `points` points in calls of CHUNK, as often as one decode runs that stage."""
+    L, s, chk = _lib.lib(), stream(dev), _lib.check
+    g = cfg.image_size // 16
+    T, P, calls = g * g, CHUNK, points // CHUNK
+    gen = torch.Generator().manual_seed(4)
+    h16 = lambda *shape: torch.randn(*shape, generator=gen).to(torch.float16).to(dev)
+    f32 = lambda *shape: torch.randn(*shape, generator=gen).to(dev)
+    table = [t.to(dev) for t in w.decoder_table()]
+    out(f" decoder stages, g = {g} (T = {T} image tokens), {points} points in {calls} calls of {P}, 8 tokens per point; per decode:")
+    total = []
+
+    def entry(name, fn, n, flop=None):
+        """n calls of fn, timed as one"""
+        def run():
+            for _ in range(n):
+                fn()
+        total.append(attempt(out, name, run, dev, args, None if flop is None else flop * n))
+    q, kpe, o16 = f32(P, 8, 128), f32(T, 128), torch.empty(P, 8, 128, dtype=torch.float16, device=dev)
+    kx, v = h16(P, T, 128), h16(P, T, 128)
+    flop = 4.0 * P * 8 * T * 128
+    entry("t2i attention, per-image keys (layer 0), x 1", lambda: chk(L.gsr_sam2_dec_t2i(
+        ptr(q), ptr(kx), ptr(kpe), ptr(v), P, T, 1, ptr(o16), s)), calls, flop)
+    entry("t2i attention, per-point keys (layer 1, final), x 2", lambda: chk(L.gsr_sam2_dec_t2i(
+        ptr(q), ptr(kx), ptr(kpe), ptr(v), P, T, 0, ptr(o16), s)), 2 * calls, flop)
+    x, xo = h16(P, T, 256), torch.empty(P, T, 256, dtype=torch.float16, device=dev)
+    entry("image-stream products 256->128 (k, v, q), x 5", lambda: chk(L.gsr_dino_linear(
+        ptr(x), ptr(table[_lib.GSR_SAMD_W_LAYER0 + 12]), None, None, P * T, 256, 128, 0, ptr(kx), s)), 5 * calls, 2.0 * P * T * 256 * 128)
+    k8, v8 = f32(P, 8, 128), f32(P, 8, 128)
+    it, n4 = _lib.GSR_SAMD_W_LAYER0 + 28, _lib.GSR_SAMD_W_LAYER0 + 26
+    nb = L.gsr_sam2_dec_i2t_workspace_bytes(P, T)
+    ws = workspace(nb, dev)
+    flop = 4.0 * P * T * 8 * 128 + 2.0 * P * T * 128 * 256
+    for shared, name in ((1, "per-image stream (layer 0)"), (0, "per-point stream (layer 1)")):
+        entry(f"i2t, {name}, x 1", lambda shared=shared: chk(L.gsr_sam2_dec_i2t(
+            ptr(kx), ptr(kpe), ptr(k8), ptr(v8), ptr(x), P, T, shared, ptr(table[it + 6]), ptr(table[it + 7]), ptr(table[n4]),
+            ptr(table[n4 + 1]), 1e-5, ptr(ws), nb, ptr(xo), s)), calls, flop)
+    del ws
+    up = _lib.GSR_SAMD_W_UP
+    hyper, low = f32(3, P, 32), torch.empty(P, 3, 4 * g, 4 * g, device=dev)
+    s0, s1 = f32(32, 4 * g, 4 * g), f32(64, 2 * g, 2 * g)
+    flop = 2.0 * P * T * (256 * 256 + 4 * 64 * 128 + 16 * 32 * 3)
+
+    def upscale(lib):
+        nb = lib.gsr_sam2_dec_upscale_workspace_bytes(g, P)
+        ws = workspace(nb, dev)
+        return lambda: chk(lib.gsr_sam2_dec_upscale(ptr(x), g, P, *[ptr(t) for t in table[up:up + 6]], ptr(hyper), ptr(s0), ptr(s1), ptr(ws), nb,
+                                                    ptr(low), s)), ws
+    fn, ws = upscale(L)
+    entry("upscale (conv1 + s1, norm, GELU, conv2 + s0, GELU, masks), x 1", fn, calls, flop)
+    rows, hid = h16(points, 256), torch.empty(points, 256, dtype=torch.float16, device=dev)
+    hw, hb = table[_lib.GSR_SAMD_W_HYPER], table[_lib.GSR_SAMD_W_HYPER + 1]
+    entry("heads (4 MLPs: 12 products on [points,256]; no ReLU pass)", lambda: [chk(L.gsr_dino_linear(
+        ptr(rows), ptr(hw), ptr(hb), None, points, 256, 256, 0, ptr(hid), s)) for _ in range(12)], 1)
+    if all(t is not None for t in total):
+        out(f"  {'sum of the stages above':<52s} {sum(total):9.3f} ms")
+    if args.ab_lib:
+        B = C.CDLL(args.ab_lib)
+        for name in ("gsr_sam2_dec_upscale", "gsr_sam2_dec_upscale_workspace_bytes"):
+            getattr(B, name).restype, getattr(B, name).argtypes = getattr(L, name).restype, getattr(L, name).argtypes
+        fn_b, ws_b = upscale(B)
+        fn()
+        ref = low.clone()
+        fn_b()
+        out(f" feat_s0 in conv2's epilogue (A, the product) or by a kernel of its own on conv2 stored as fp32 (B): {P} points per call, "
+            f"alternated; the same bits: {bool(torch.equal(ref, low))}")
+        for rnd in range(3):
+            attempt(out, f"A upscale, round {rnd}", fn, dev, args, flop)
+            attempt(out, f"B upscale, round {rnd}", fn_b, dev, args, flop)
+
+
+def decoder_whole(cfg, w, dev, args, out, points=1024):
+    """The whole prompt encoder and mask decoder for `points` points: the kernels next to decode_host2 in fp32 (what the
+    generator runs by default) and in fp16 (the strongest stock alternative), on the same GPU in the same run."""
+    g, S = cfg.image_size // 16, cfg.image_size
+    gen5 = torch.Generator().manual_seed(5)
+    maps = [torch.randn(shape, generator=gen5).to(torch.float16).float().to(dev) for shape in ((32, 4 * g, 4 * g), (64, 2 * g, 2 * g), (256, g, g))]
+    pts = S1.point_grid(int(round(points ** 0.5)), (S, S))
+    out(f" whole decoder, g = {g}, {len(pts)} points (decoder='hip' chunks them by {S1.DECODER_WORKSPACE_BUDGET >> 20} MiB of workspace; "
+        f"decode_host2 takes 64 at a time):")
+    gen = S2.Sam2MaskGenerator(w, device=dev, decoder="hip")
+    t = {}
+    try:
+        with torch.no_grad():
+            t["hip"] = timed(lambda: gen.decode(maps, pts), dev, args.warmup, args.repeats)
+        out(fmt("kernels (gsr_sam2_decode)", t["hip"]))
+        ours = gen.decode(maps, pts)
+    except Exception as e:
+        out(f"  kernels (gsr_sam2_decode) failed: {type(e).__name__}: {e}")
+        ours = None
+    for dtype, label in ((torch.float32, "fp32 (the generator's default)"), (torch.float16, "fp16")):
+        try:
+            modules = S2.host_decoder2(w, dtype, dev)
+            with torch.no_grad():
+                t[label[:4]] = timed(lambda: S2.decode_host2(w, maps, pts, dtype, dev, modules), dev, args.warmup, args.repeats)
+            out(fmt(f"decode_host2 {label}", t[label[:4]]))
+            if ours is not None:
+                lo, io = S2.decode_host2(w, maps, pts, dtype, dev, modules)
+                out(f"  max |kernels - decode_host2 {label[:4]}|: masks {float((lo.float() - ours[0]).abs().max()):.3e}, "
+                    f"iou {float((io.float() - ours[1]).abs().max()):.3e}")
+            del modules
+        except Exception as e:
+            out(f"  decode_host2 {label} failed: {type(e).__name__}: {e}")
+        torch.cuda.empty_cache()
+    if "hip" in t and "fp16" in t:
+        margin = t["fp16"][0] - t["hip"][0]
+        spread = max(t["hip"][2] - t["hip"][1], t["fp16"][2] - t["fp16"][1])
+        verdict = "below" if margin > spread else "NOT below"
+        out(f"  kernels {verdict} decode_host2 fp16: margin {margin:.3f} ms against a spread of {spread:.3f} ms (the larger min..max)")
+    if "hip" in t and "fp32" in t:
+        out(f"  kernels {'below' if t['hip'][0] < t['fp32'][0] else 'NOT below'} decode_host2 fp32: {t['fp32'][0] / t['hip'][0]:.2f} x")
+
+
+def image(cfg, w, dev, args, out, decoder="torch"):
     rng = np.random.default_rng(3)
     img = rng.integers(0, 255, (768, 1024, 3), dtype=np.uint8)
-    gen = S2.Sam2MaskGenerator(w, points_per_side=args.points_per_side, device=dev)
+    gen = S2.Sam2MaskGenerator(w, points_per_side=args.points_per_side, device=dev, decoder=decoder)
     rows = []
     for _ in range(args.warmup + 3):
         gen.generate_device(img)
         rows.append(dict(gen.last_ms))
     last = rows[-1]
     total = sum(last.values())
-    out(f" one 1024x768 image, {args.points_per_side ** 2} points (host preprocessing inside embed; the last of {len(rows)} runs):")
+    out(f" one 1024x768 image, {args.points_per_side ** 2} points, decoder={decoder!r} (host preprocessing inside embed; the last of "
+        f"{len(rows)} runs):")
     for k in ("embed", "decode", "select"):
         out(f"  {k:<52s} {last[k]:9.3f} ms  ({100 * last[k] / total:.1f} % of the image)")
-    out("  decode is transformers' Sam2PromptEncoder and Sam2MaskDecoder in fp32 torch, as they are")
+    if decoder == "torch":
+        out("  decode is transformers' Sam2PromptEncoder and Sam2MaskDecoder in fp32 torch, as they are")
+    else:
+        out("  decode is gsr_sam2_decode: the kernels of csrc/sam_decoder.hip")
 
 
 def main(argv=None):
@@ -224,6 +351,7 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--points_per_side", type=int, default=32)
+    ap.add_argument("--ab_lib", default=None, help="a -DSD_SKIP0_EPILOGUE=0 build of the library, for the up-scaling's A/B entry")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("sam2_bench: no HIP device; timings are taken on the GPU only")
@@ -244,7 +372,11 @@ def main(argv=None):
         f"weights) on {torch.cuda.get_device_name(0)}; torch {torch.__version__}, transformers {transformers.__version__}")
     out(f"median of {args.repeats} timed calls after {args.warmup} warm-up calls, (min .. max); TFLOP/s = operations counted from the shapes / median")
     for name, section in (("encoder", lambda: encoder(cfg, w, dev, args, out)), ("attention", lambda: attention(cfg, dev, args, out)),
-                          ("selection", lambda: selection(dev, args, out)), ("image", lambda: image(cfg, w, dev, args, out))):
+                          ("selection", lambda: selection(dev, args, out)),
+                          ("decoder stages", lambda: decoder_stages(cfg, w, dev, args, out)),
+                          ("decoder", lambda: decoder_whole(cfg, w, dev, args, out)),
+                          ("image (torch)", lambda: image(cfg, w, dev, args, out, "torch")),
+                          ("image (hip)", lambda: image(cfg, w, dev, args, out, "hip"))):
         try:
             section()
         except Exception as e:
