@@ -15,11 +15,24 @@ import torch
 from . import _lib
 
 
+def camera_pose_key(view):
+    """What a per-camera cache depends on: the image size and the two pose tensors, each as (the object, its version counter).
+    The key holds the tensors themselves, so that `is` cannot meet a recycled id; an in-place write (`copy_`, `mul_`, ...) moves
+    the version counter, an assignment changes the object.  Reading either costs no device-to-host copy."""
+    wvt, full = view.world_view_transform, view.full_proj_transform
+    return (view.image_width, view.image_height, wvt, wvt._version, full, full._version)
+
+
+def same_camera_pose(a, b):
+    return len(a) == len(b) and all((x is y) if isinstance(x, torch.Tensor) else (x == y) for x, y in zip(a, b))
+
+
 def camera_kinv(view):
     """Inverse pixel intrinsics as the reference derives them (utils/point_utils.py:10-17), cached
-    on the camera as 9 host floats (one device->host copy per camera, ever)."""
+    on the camera as 9 host floats (one device->host copy per camera and pose: camera_pose_key)."""
+    key = camera_pose_key(view)
     cached = getattr(view, "_gsr_kinv", None)
-    if cached is not None and cached[0] == (view.image_width, view.image_height):
+    if cached is not None and same_camera_pose(cached[0], key):
         return cached[1]
     wvt = view.world_view_transform.detach().float().cpu()
     full = view.full_proj_transform.detach().float().cpu()
@@ -29,7 +42,7 @@ def camera_kinv(view):
     intrins = ((c2w.T @ full) @ ndc2pix)[:3, :3].T
     kinv = (C.c_float * 9)(*intrins.inverse().reshape(-1).tolist())
     try:
-        view._gsr_kinv = ((W, H), kinv)
+        view._gsr_kinv = (key, kinv)
     except Exception:
         pass
     return kinv

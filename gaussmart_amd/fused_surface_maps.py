@@ -7,20 +7,25 @@ objective, not the fused one (fused_objective.py):
 Same values and gradients as the torch formulation in gaussian_renderer.render() (tests/test_gpu_surface_maps.py), one launch
 each way instead of ~40 elementwise / GEMM / cross / normalize kernels over the frame.  rend_alpha = allmap[1:2] and rend_dist =
 allmap[6:7] stay plain slices.  At pixels with alpha = 0 torch's own backward leaves 0 / 0 on allmap[0:2]; this node writes 0
-there (no splat covers such a pixel; the rasterizer's backward never reads its gradient).
+there (no splat covers such a pixel; the rasterizer's backward never reads its gradient).  surf_normal is exactly 0 on the image
+border, whose incoming gradient is never read; where |cross| <= 1e-12 both directions follow F.normalize's scaling by 1e12;
+d_allmap[6] is 0 (tests/objective_cases.maps_chain states all of it, tests/test_gpu_objective_parity.py holds it per pixel).
 """
 import ctypes as C
 
 import torch
 
 from . import _lib
+from .fused_regularizer import camera_pose_key, same_camera_pose
 
 
 def camera_world_rays(view):
     """(c2w[:3,:3] K^-1, world_view[:3,:3]) as two arrays of 9 host floats, cached on the camera: ray(x, y) = first * [x, y, 1]
-    is the reference's rays_d (utils/point_utils.py:9-24), the second rotates view-space normals to world space."""
+    is the reference's rays_d (utils/point_utils.py:9-24), the second rotates view-space normals to world space.  The cache
+    follows the camera's pose (fused_regularizer.camera_pose_key)."""
+    key = camera_pose_key(view)
     cached = getattr(view, "_gsr_world_rays", None)
-    if cached is not None and cached[0] == (view.image_width, view.image_height):
+    if cached is not None and same_camera_pose(cached[0], key):
         return cached[1], cached[2]
     wvt = view.world_view_transform.detach().double().cpu()
     full = view.full_proj_transform.detach().double().cpu()
@@ -32,7 +37,7 @@ def camera_world_rays(view):
     rays = (C.c_float * 9)(*m.reshape(-1).tolist())
     rot = (C.c_float * 9)(*wvt[:3, :3].reshape(-1).tolist())
     try:
-        view._gsr_world_rays = ((W, H), rays, rot)
+        view._gsr_world_rays = (key, rays, rot)
     except Exception:
         pass
     return rays, rot

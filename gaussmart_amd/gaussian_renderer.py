@@ -21,6 +21,7 @@ import math
 import torch
 
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians_raw
+from .fused_regularizer import camera_pose_key, same_camera_pose
 from .sh import eval_sh
 
 _HipRasterizer = GaussianRasterizer   # tests may monkeypatch `GaussianRasterizer`; the raw path is HIP-only
@@ -28,10 +29,10 @@ _HipRasterizer = GaussianRasterizer   # tests may monkeypatch `GaussianRasterize
 
 def _camera_rays(view, device, dtype):
     """Per-pixel ray directions / origin in world space (utils/point_utils.py:9-24), cached on the
-    camera because they only depend on it."""
+    camera because they only depend on it (on its size and pose: fused_regularizer.camera_pose_key)."""
     cache = getattr(view, "_gsr_rays", None)
-    key = (str(device), dtype, view.image_width, view.image_height)
-    if cache is not None and cache[0] == key:
+    key = (str(device), dtype) + camera_pose_key(view)
+    if cache is not None and same_camera_pose(cache[0], key):
         return cache[1], cache[2]
     wvt = view.world_view_transform.to(device=device, dtype=dtype)
     c2w = wvt.T.inverse()

@@ -25,6 +25,10 @@ The photometric loss: what is counted, from the kernel text of loss_fwd_kernel /
 The regularizers: reg_chain is reg_fwd_kernel / reg_bwd_kernel in camera space with the nine fp32 numbers of camera_kinv.
 Every intermediate carries the magnitudes of its terms (the cross products and the normalisation are where they matter).
 A tile's sums: wave tree 6 levels + 2: 8 roundings.
+
+The surface maps: maps_chain is maps_fwd_kernel / maps_bwd_kernel with the world-space rays and the rotation of
+fused_surface_maps.camera_world_rays, for an arbitrary upstream gradient of the seven output planes (MAPS_CASES: every kind of
+allmap at every size, on the rotated camera).
 """
 import functools
 import math
@@ -383,10 +387,11 @@ def reg_chain(am, kinv, r, ln, ld, gs, bars=False):
     torch.nan_to_num(v, 0, 0) does; -inf does not occur: depth is positive), and no gradient passes: channels 0 and 1 get exactly
     0.  A NaN or infinite median passes none either.  Every channel is finite, channel 6 is kd = ld * gs / (H W) at every pixel.
     Where |cross| <= 1e-12 the normal is cross * 1e12 and reg_bwd_kernel lets NO gradient through it (maps_bwd_kernel scales by
-    1e12 there instead, as autograd of F.normalize does).  The difference reaches only pixels with alpha == 0: short of a surface
-    seen exactly edge-on (parallel differences), the cross product of a pixel vanishes only when one of its finite differences
-    does, which -- the two rays differ -- needs both neighbours at depth 0, that is both to be holes, and those two are the only
-    pixels that finite difference hands a gradient to.  This twin follows reg_bwd_kernel: zero."""
+    1e12 there instead, as autograd of F.normalize does).  Short of a surface seen exactly edge-on (parallel differences), the
+    cross product of a pixel vanishes only when one of its finite differences does, which -- the two rays differ -- needs both
+    neighbours at depth 0, that is both to be holes, and those two are the only pixels that finite difference hands a gradient
+    to.  It can be below 1e-12 without vanishing, though: on a surface closer than about 1e-6 W (the `micro` kind) every pixel is,
+    and the difference reaches lit pixels there.  This twin follows reg_bwd_kernel: zero."""
     mode = "bar" if bars else mode_of(am)
     H, W = am.shape[-2:]
     D, A, M, Dist = am[0], am[1], am[5], am[6]
@@ -437,10 +442,10 @@ def reg_chain(am, kinv, r, ln, ld, gs, bars=False):
 REG_MUTATIONS = ("forward_differences", "border_normal_kept", "alpha_attached", "inf_kept", "ratio_exchanged", "half_pixel_rays")
 
 
-def reg_autograd64(am, kinv, r, ln, ld, gs, mut=None):
-    """The same objective written for autograd in fp64 (the oracle's formulation in camera space, with the guards of the contract
-    above), and one wrong reading of it per REG_MUTATIONS -> (err [H,W], (tile sums), d_allmap [7,H,W])."""
-    a = am.double().clone().requires_grad_(True)
+def _surf64(a, m, r, mut=None, eps_passes=False):
+    """surf_depth [H,W] and surf_normal * alpha [H,W,3] of allmap `a` (fp64, possibly an autograd leaf) with the rays m [x, y, 1],
+    written for autograd with the guards of the contract of reg_chain, and one wrong reading of it per `mut`.  eps_passes: where
+    |cross| <= 1e-12 the gradient passes through the scaling by 1e12 (F.normalize, maps_bwd_kernel) or not at all (reg_bwd_kernel)."""
     H, W = a.shape[-2:]
     D, A, M = a[0], a[1], a[5]
     q = (D / A).detach()
@@ -452,7 +457,7 @@ def reg_autograd64(am, kinv, r, ln, ld, gs, mut=None):
     sd = r1 * e + r2 * med
     off = 0.5 if mut == "half_pixel_rays" else 0.0
     gy, gx = torch.meshgrid(torch.arange(H, dtype=torch.float64) + off, torch.arange(W, dtype=torch.float64) + off, indexing="ij")
-    rays = torch.stack([gx, gy, torch.ones_like(gx)], -1) @ kinv.double().T
+    rays = torch.stack([gx, gy, torch.ones_like(gx)], -1) @ m.double().T
     P = sd[..., None] * rays
     if mut == "border_normal_kept":
         P = F.pad(P.permute(2, 0, 1)[None], (1, 1, 1, 1), mode="replicate")[0].permute(1, 2, 0)
@@ -463,14 +468,24 @@ def reg_autograd64(am, kinv, r, ln, ld, gs, mut=None):
     c = torch.cross(dx, dy, dim=-1)
     ln_c = c.norm(dim=-1, keepdim=True)
     n = c / ln_c.clamp_min(1e-12)
-    n = torch.where(ln_c > 1e-12, n, n.detach())
+    if not eps_passes:
+        n = torch.where(ln_c > 1e-12, n, n.detach())
     if mut == "border_normal_kept":
         sn = n
     else:
         sn = torch.zeros(H, W, 3, dtype=torch.float64)
         if H >= 3 and W >= 3:
             sn = F.pad(n.permute(2, 0, 1), (1, 1, 1, 1)).permute(1, 2, 0)
-    sn = sn * (A if mut == "alpha_attached" else A.detach())[..., None]
+    if mut != "no_alpha":
+        sn = sn * (A if mut == "alpha_attached" else A.detach())[..., None]
+    return sd, sn
+
+
+def reg_autograd64(am, kinv, r, ln, ld, gs, mut=None):
+    """The same objective written for autograd in fp64 (the oracle's formulation in camera space, with the guards of the contract
+    above), and one wrong reading of it per REG_MUTATIONS -> (err [H,W], (tile sums), d_allmap [7,H,W])."""
+    a = am.double().clone().requires_grad_(True)
+    _, sn = _surf64(a, kinv, r, mut)
     err = 1.0 - (a[2:5].permute(1, 2, 0) * sn).sum(-1)
     (gs * (ln * err.mean() + ld * a[6].mean())).backward()
     err = err.detach()
@@ -479,13 +494,24 @@ def reg_autograd64(am, kinv, r, ln, ld, gs, mut=None):
 
 REG_SIZES = {(2, 7): "no interior pixel", (3, 3): "one interior pixel", (16, 16): "one tile", (17, 33): "tile straddling",
              (31, 18): "tile straddling", (48, 40): "nine tiles"}
-REG_KINDS = ("full", "holes", "island", "one_hole", "plane", "nonfinite")
+REG_NOISE_KINDS = ("full", "holes", "island", "one_hole", "plane", "nonfinite")
+# structured depth, what every real render has: the cross product of the two finite differences has to cancel
+REG_SURFACE_KINDS = ("sphere", "far", "micro", "grazing", "step")
+REG_KINDS = REG_NOISE_KINDS + REG_SURFACE_KINDS
 REG_RATIOS = (0.0, 0.3, 1.0)
 REG_LAMBDAS = ((0.05, 100.0), (1.0, 0.0), (0.0, 1.0))
 REG_GRAD_SCALE = 2.5
-# every kind at every size; the ratio and the lambdas rotate so that each kind and each size meets every one of them
-REG_CASES = [(kind, size, REG_RATIOS[(i + j) % 3], REG_LAMBDAS[(i + 2 * j + (i // 3)) % 3])
-             for i, size in enumerate(REG_SIZES) for j, kind in enumerate(REG_KINDS)]
+
+
+def _reg_rotation(i, j):
+    return REG_RATIOS[(i + j) % 3], REG_LAMBDAS[(i + 2 * j + (i // 3)) % 3]
+
+
+# every kind at every size; the ratio and the lambdas rotate so that each kind and each size meets every one of them.  The
+# structured kinds are appended: the cases of the noise kinds keep their places, ratios and lambdas
+REG_CASES = [(kind, size) + _reg_rotation(i, j) for i, size in enumerate(REG_SIZES) for j, kind in enumerate(REG_NOISE_KINDS)] + \
+            [(kind, size) + _reg_rotation(i, len(REG_NOISE_KINDS) + j) for i, size in enumerate(REG_SIZES)
+             for j, kind in enumerate(REG_SURFACE_KINDS)]
 
 
 def reg_case_id(case):
@@ -500,13 +526,15 @@ def reg_camera(size, rotated=False):
     return jittered_cameras(2, W, H, seed=H + W, amount=0.4)[1 if rotated else 0]
 
 
-def reg_camera_f64(size, rotated=False):
+def reg_camera_f64(size, rotated=False, centred=False):
     """-> (world_view_transform, full_proj_transform) in fp64 from the camera's fp64 R and T.  The camera's own fp32 matrices are
-    orthogonal to 4e-8 only, and the rotation drops out of the normal error no better than that."""
+    orthogonal to 4e-8 only, and the rotation drops out of the normal error no better than that.  centred: the same rotation and
+    intrinsics with the camera centre at the world origin."""
     cam = reg_camera(size, rotated)
     w2c = torch.eye(4, dtype=torch.float64)
     w2c[:3, :3] = torch.as_tensor(cam.R, dtype=torch.float64).T
-    w2c[:3, 3] = torch.as_tensor(cam.T, dtype=torch.float64)
+    if not centred:
+        w2c[:3, 3] = torch.as_tensor(cam.T, dtype=torch.float64)
     wvt = w2c.T.contiguous()
     return wvt, wvt @ cam.projection_matrix.double().cpu()
 
@@ -525,9 +553,39 @@ def reg_kinv(size, rotated=False, dtype=torch.float32):
     return ((c2w.T @ full) @ ndc2pix)[:3, :3].T.inverse()
 
 
+def _surface_depth(kind, size, g):
+    """The z-depth [H,W] (fp64) of a surface seen through the camera-space rays of reg_kinv(size) (z = 1), and where it is hit.
+      sphere   centre (0, 0, 6), radius 2: a silhouette, holes around it
+      far      the plane of `plane` through (0, 0, 3000)
+      micro    the same plane through (0, 0, 1.5e-6): every cross product is below F.normalize's eps, 1e-12.  The rays of two
+               neighbours differ by about 1.15 / W (60 degrees across the width), so below W = 16 the plane comes closer by W / 16
+      grazing  a plane through (0, 0, 6) whose normal is 85 degrees from the view axis; holes where the ray misses it or the depth
+               exceeds 1e6
+      step     depth 2 on the left half, 9 on the right, plus 0.01 * noise"""
+    H, W = size
+    gy, gx = torch.meshgrid(torch.arange(H, dtype=torch.float64), torch.arange(W, dtype=torch.float64), indexing="ij")
+    rays = torch.stack([gx, gy, torch.ones_like(gx)], -1) @ reg_kinv(size).double().T
+    if kind == "sphere":
+        centre, radius = torch.tensor([0.0, 0.0, 6.0], dtype=torch.float64), 2.0
+        b, a = rays @ centre, (rays * rays).sum(-1)
+        disc = b * b - a * (centre @ centre - radius * radius)
+        return (b - torch.sqrt(disc.clamp_min(0.0))) / a, disc > 0
+    if kind == "step":
+        left = (torch.arange(W) < W // 2)[None, :].expand(H, W)
+        depth = torch.where(left, 2.0, 9.0).double() + 0.01 * torch.rand(H, W, generator=g).double()
+        return depth, torch.ones(H, W, dtype=torch.bool)
+    n = torch.tensor([0.0, -1.0, -0.0875] if kind == "grazing" else [0.3, -0.2, -1.0], dtype=torch.float64)
+    n = n / n.norm()
+    z0 = {"far": 3000.0, "micro": 1.5e-6 * min(1.0, W / 16.0), "grazing": 6.0}[kind]
+    depth = (n[2] * z0) / (rays @ n)
+    return depth, (depth > 0) & (depth < 1e6)
+
+
 @functools.lru_cache(maxsize=None)
 def reg_allmap(kind, size):
-    """-> allmap fp32 [7,H,W]: alpha * depth, alpha, alpha * normal, median depth, distortion (as tests/test_gpu_surface_maps.py)."""
+    """-> allmap fp32 [7,H,W]: alpha * depth, alpha, alpha * normal, median depth, distortion (as tests/test_gpu_surface_maps.py).
+    alpha is 0 or in [0.05, 1]: D / A is finite in fp32 wherever it is in fp64.  REG_NOISE_KINDS draw the depth per pixel (but
+    `plane`); REG_SURFACE_KINDS (_surface_depth) are surfaces, with a random rendered normal and a median within 2 % of the depth."""
     H, W = size
     g = torch.Generator().manual_seed(100 * REG_KINDS.index(kind) + 7 * H + W)
     alpha = 0.05 + 0.95 * torch.rand(1, H, W, generator=g)
@@ -541,8 +599,12 @@ def reg_allmap(kind, size):
         alpha = torch.where(lit, alpha, torch.zeros_like(alpha))
     elif kind == "one_hole":
         alpha[0, cy, cx] = 0.0
+    if kind in REG_SURFACE_KINDS:
+        depth, lit = _surface_depth(kind, size, g)
+        alpha = torch.where(lit[None], alpha, torch.zeros_like(alpha))
+        depth = torch.where(lit, depth, torch.zeros_like(depth))[None].float()
     nrm = torch.randn(3, H, W, generator=g) * alpha
-    if kind == "plane":                                      # the rendered normal IS the surface normal: error ~ 0, 1 - dot cancels
+    if kind == "plane":                                     # the rendered normal IS the surface normal: error ~ 0, 1 - dot cancels
         kinv = reg_kinv(size).double()
         gy, gx = torch.meshgrid(torch.arange(H, dtype=torch.float64), torch.arange(W, dtype=torch.float64), indexing="ij")
         rays = torch.stack([gx, gy, torch.ones_like(gx)], -1) @ kinv.T
@@ -551,7 +613,8 @@ def reg_allmap(kind, size):
         depth = ((n[2] * 6.0) / (rays @ n))[None].float()    # the plane through (0, 0, 6); rays have z = 1, so this is the z-depth
         alpha = torch.ones(1, H, W)
         nrm = n.float()[:, None, None].expand(3, H, W)
-    med = torch.where(alpha > 0, depth * (0.8 + 0.4 * torch.rand(1, H, W, generator=g)), torch.zeros_like(depth))
+    spread = 0.04 if kind in REG_SURFACE_KINDS else 0.4      # the structured kinds stay surfaces at every depth ratio
+    med = torch.where(alpha > 0, depth * ((1.0 - spread / 2) + spread * torch.rand(1, H, W, generator=g)), torch.zeros_like(depth))
     if kind == "plane":
         med = depth
     am = torch.cat([alpha * depth, alpha, nrm, med, alpha * torch.rand(1, H, W, generator=g)]).float().contiguous()
@@ -573,6 +636,146 @@ def reg_allmap(kind, size):
 def reg_truth(case):
     kind, size, r, (ln, ld) = case
     return reg_chain(reg_allmap(kind, size).double(), reg_kinv(size).double(), f32(r), f32(ln), f32(ld), REG_GRAD_SCALE, bars=True)
+
+
+# ------------------------------------------------------------------------------------------------ surface maps
+def maps_chain(am, rays9, rot9, r, gout, bars=False):
+    """maps_fwd_kernel and maps_bwd_kernel on allmap [7,H,W] (fp32 or fp64; bars: fp64 in E arithmetic) with the world-space rays
+    rays9 [3,3] = c2w[:3,:3] K^-1 and the rotation rot9 [3,3] = world_view_transform[:3,:3], the numbers of
+    fused_surface_maps.camera_world_rays: the seven output planes (rend_normal, surf_depth, surf_normal * alpha) and, for the
+    upstream gradient gout [7,H,W], the seven channels of d_allmap.  `len` is |cross| at the interior pixels.
+
+    What differs from reg_chain: the rays carry the rotation; out[0:3] = rot . n and d_allmap[2:5] = rot^T . gout[0:3], three
+    products and two additions each; the gradient of surf_normal is whatever arrives, times alpha (detached); surf_depth has a
+    gradient of its own; d_allmap[6] = 0; and where |cross| <= 1e-12 the normal is cross * 1e12 with the gradient gout * 1e12, as
+    autograd of F.normalize has it.  1e-12 and 1e12 are fp32 constants there: one rounding each, which shows only in that regime.
+    The contract at pixels without a splat is reg_chain's: finite everywhere, channels 0 and 1 exactly 0."""
+    mode = "bar" if bars else mode_of(am)
+    H, W = am.shape[-2:]
+    D, A, M = am[0], am[1], am[5]
+    ok_e, ok_m = torch.isfinite(D / A), torch.isfinite(M)
+    Dc, Ac, Mc = where(ok_e, D, 0.0), where(ok_e, A, 1.0), where(ok_m, M, 0.0)
+    L = lambda t: lift(mode, t)
+    r_ = scalar(mode, r)
+    sd = (1.0 - r_) * (L(Dc) / L(Ac)) + r_ * L(Mc)
+    xs = L(torch.arange(W, dtype=am.dtype)[None, :].expand(H, W).contiguous())
+    ys = L(torch.arange(H, dtype=am.dtype)[:, None].expand(H, W).contiguous())
+    m = [[scalar(mode, float(rays9[i, j])) for j in range(3)] for i in range(3)]
+    rot = [[scalar(mode, float(rot9[i, j])) for j in range(3)] for i in range(3)]
+    R = [(m[k][0] * xs + m[k][1] * ys) + m[k][2] for k in range(3)]
+    up, dn, rt, lf, mid = (slice(2, None), slice(1, -1)), (slice(0, -2), slice(1, -1)), (slice(1, -1), slice(2, None)), \
+        (slice(1, -1), slice(0, -2)), (slice(1, -1), slice(1, -1))
+    dx = [sd[up] * R[k][up] - sd[dn] * R[k][dn] for k in range(3)]
+    dy = [sd[rt] * R[k][rt] - sd[lf] * R[k][lf] for k in range(3)]
+    c = _cross(dx, dy)
+    ln_c = sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2])
+    big = val(ln_c) > 1e-12
+    inv = rcp(where(big, ln_c, scalar(mode, 1e-12, exact=False)), 1)
+    alpha, N = L(A)[mid], [L(am[2 + k]) for k in range(3)]
+    out = [(rot[j][0] * N[0] + rot[j][1] * N[1]) + rot[j][2] * N[2] for j in range(3)] + [sd] + \
+          [embed((c[k] * inv) * alpha, H, W) for k in range(3)]
+    # backward
+    G = [L(gout[k]) for k in range(4)]
+    g = [L(gout[4 + k][mid]) * alpha for k in range(3)]
+    il = rcp(where(big, ln_c, 1.0), 1)
+    s = [c[k] * il for k in range(3)]
+    sg = (s[0] * g[0] + s[1] * g[1]) + s[2] * g[2]
+    e12 = scalar(mode, 1e12, exact=False)
+    gc = [where(big, (g[k] - s[k] * sg) * il, g[k] * e12) for k in range(3)]
+    gdx = [embed(v, H, W) for v in _cross(dy, gc)]
+    gdy = [embed(v, H, W) for v in _cross(gc, dx)]
+    gP = [((shift(gdx[k], -1, 0) - shift(gdx[k], 1, 0)) + shift(gdy[k], 0, -1)) - shift(gdy[k], 0, 1) for k in range(3)]
+    g_sd = ((gP[0] * R[0] + gP[1] * R[1]) + gP[2] * R[2]) + G[3]
+    g_e = (1.0 - r_) * g_sd
+    dam = [None] * 7
+    dam[0] = where(ok_e, g_e / L(Ac), 0.0)
+    dam[1] = where(ok_e, ((-g_e) * L(Dc)) / (L(Ac) * L(Ac)), 0.0)
+    dam[5] = where(ok_m, r_ * g_sd, 0.0)
+    dam[6] = L(torch.zeros(H, W, dtype=am.dtype))
+    for k in range(3):
+        dam[2 + k] = (rot[0][k] * G[0] + rot[1][k] * G[1]) + rot[2][k] * G[2]
+    return dict(out=out, dam=dam, len=ln_c)
+
+
+MAPS_MUTATIONS = ("camera_space_rays", "rotation_not_transposed_back", "rotation_transposed_forward", "alpha_attached", "no_alpha",
+                  "eps_passes_nothing", "depth_gradient_dropped", "forward_differences", "border_normal_kept", "ratio_exchanged",
+                  "inf_kept", "half_pixel_rays", "dist_gradient_not_zero")
+
+
+def maps_autograd64(am, rays9, rot9, r, gout, mut=None):
+    """The same maps written for autograd in fp64 (the oracle's formulation on the rays the kernel was given, with the guards of
+    the contract), and one wrong reading of the kernels per MAPS_MUTATIONS -> (out [7,H,W], d_allmap [7,H,W] of sum(out * gout))."""
+    a = am.double().clone().requires_grad_(True)
+    rays, rot, go = rays9.double(), rot9.double(), gout.double()
+    if mut == "camera_space_rays":
+        rays = rot.T @ rays
+    sd, sn = _surf64(a, rays, r, mut, eps_passes=mut != "eps_passes_nothing")
+    rn = torch.einsum("ij,jhw->ihw" if mut != "rotation_transposed_forward" else "ji,jhw->ihw", rot, a[2:5])
+    out = torch.cat([rn, sd[None], sn.permute(2, 0, 1)])
+    seen = go.clone()
+    if mut == "depth_gradient_dropped":
+        seen[3] = 0.0
+    (out * seen).sum().backward()
+    grad = a.grad.clone()
+    if mut == "rotation_not_transposed_back":
+        grad[2:5] = torch.einsum("ij,jhw->ihw", rot, go[0:3])
+    if mut == "dist_gradient_not_zero":                      # reg_bwd_kernel's channel 6 with unit weights
+        grad[6] = 1.0 / (am.shape[-2] * am.shape[-1])
+    return out.detach(), grad
+
+
+MAPS_SIZES = dict(REG_SIZES)
+MAPS_SIZES.update({(1, 1): "a single pixel", (80, 112): "35 tiles: not a multiple of the eight tile bands, idle workgroups, a ragged last band"})
+# the sizes at which a kind's upstream gradient is a single interior pixel (one size per kind, in turn)
+_DELTA_SIZES = [size for size in MAPS_SIZES if min(size) >= 3]
+# every kind at every size on the rotated camera; the depth ratio rotates as in REG_CASES
+MAPS_CASES = [(kind, size, REG_RATIOS[(i + j) % 3], "delta" if size == _DELTA_SIZES[j % len(_DELTA_SIZES)] else "randn")
+              for i, size in enumerate(MAPS_SIZES) for j, kind in enumerate(REG_KINDS)]
+
+
+def maps_case_id(case):
+    kind, (H, W), r, pattern = case
+    return f"{kind}-{H}x{W}-r{r}-{pattern}"
+
+
+def maps_rays(size, dtype=torch.float32):
+    """-> (rays9, rot9) as [3,3] tensors for the rotated camera.  float32: the numbers fused_surface_maps.camera_world_rays hands
+    to the kernels; float64: the same derivation from the camera's fp64 matrices, what the oracle works with."""
+    if dtype == torch.float32:
+        from gaussmart_amd.fused_surface_maps import camera_world_rays
+        rays, rot = camera_world_rays(reg_camera(size, rotated=True))
+        return tuple(torch.tensor(list(v), dtype=torch.float32).reshape(3, 3) for v in (rays, rot))
+    wvt, _ = reg_camera_f64(size, rotated=True)
+    return wvt.T.inverse()[:3, :3] @ reg_kinv(size, rotated=True, dtype=torch.float64), wvt[:3, :3].clone()
+
+
+@functools.lru_cache(maxsize=None)
+def maps_gout(case):
+    """-> the upstream gradient of the seven output planes, fp32 [7,H,W].  randn: every pixel; delta: zero but at one interior
+    pixel (lit, and on a 16x16 tile's edge where there is one), so that a gradient landing on the wrong neighbour cannot hide."""
+    kind, (H, W), r, pattern = case
+    g = torch.Generator().manual_seed(5000 + 100 * REG_KINDS.index(kind) + 7 * H + W)
+    gout = torch.randn(7, H, W, generator=g)
+    if pattern == "delta":
+        ys, xs = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+        inner = (ys >= 1) & (ys <= H - 2) & (xs >= 1) & (xs <= W - 2)
+        edge = ((ys % 16 == 0) | (ys % 16 == 15) | (xs % 16 == 0) | (xs % 16 == 15))
+        lit = reg_allmap(kind, (H, W))[1] > 0
+        for cand in (inner & lit & edge, inner & lit, inner):
+            if bool(cand.any()):
+                break
+        at = cand.nonzero()[int(torch.randint(int(cand.sum()), (1,), generator=g))]
+        keep = torch.zeros(H, W, dtype=torch.bool)
+        keep[at[0], at[1]] = True
+        gout = torch.where(keep, gout, torch.zeros_like(gout))
+    return gout.contiguous()
+
+
+@functools.lru_cache(maxsize=None)
+def maps_truth(case):
+    kind, size, r, _ = case
+    rays9, rot9 = maps_rays(size)
+    return maps_chain(reg_allmap(kind, size).double(), rays9.double(), rot9.double(), f32(r), maps_gout(case).double(), bars=True)
 
 
 # ------------------------------------------------------------------------------------------------ objective finish

@@ -1,8 +1,9 @@
 """loss.hip and regularizer.hip on the device, pixel by pixel, through the C ABI: gsr_loss_forward / _backward, gsr_regularizer_forward /
-_backward / _backward_partials and gsr_objective_finish against the fp64 twins of tests/objective_cases.py, each quantity held to
-the bar derived there (tests/test_objective_cpu.py proves every bar reachable and tight without a GPU).  Every output is pre-filled
-with NaN: a slot or a pixel nobody writes shows.  GSR_OBJECTIVE_PARITY_REPORT=<file>: the measured errors and bars are appended
-there (profiles/objective_parity.txt is such a run)."""
+_backward / _backward_partials, gsr_surface_maps_forward / _backward and gsr_objective_finish against the fp64 twins of
+tests/objective_cases.py, each quantity held to the bar derived there (tests/test_objective_cpu.py proves every bar reachable and
+tight without a GPU).  Every output is pre-filled with NaN: a slot or a pixel nobody writes shows.
+GSR_OBJECTIVE_PARITY_REPORT=<file>: the measured errors and bars are appended there (profiles/objective_parity.txt and
+profiles/surface_maps_parity.txt are such runs)."""
 import ctypes as C
 import os
 
@@ -139,6 +140,138 @@ def test_regularizer_forward_and_backward_per_pixel(gpu_device, held, case):
     if kind == "island":
         # the lit pixel's cross product is exactly 0 (all four neighbours are holes): reg_bwd_kernel hands nothing to them
         assert float(got[[0, 1, 5]].abs().sum()) == 0.0
+    if kind == "micro":
+        # a lit surface whose every cross product is below 1e-12: the same, at every pixel
+        assert float(got[[0, 1, 5]].abs().sum()) == 0.0
+
+
+# ------------------------------------------------------------------------------------------------ surface maps
+def _c9(t):
+    return (C.c_float * 9)(*t.reshape(-1).tolist())
+
+
+def _maps_forward(L, am, rays, rot, r):
+    out = nans(tuple(am.shape), am.device)
+    _, H, W = am.shape
+    _lib.check(L.gsr_surface_maps_forward(ptr(am), H, W, rays, rot, r, ptr(out), stream(am.device)))
+    return out
+
+
+def _maps_backward(L, am, rays, rot, r, gout):
+    dam = nans(tuple(am.shape), am.device)
+    _, H, W = am.shape
+    _lib.check(L.gsr_surface_maps_backward(ptr(am), H, W, rays, rot, r, ptr(gout), ptr(dam), stream(am.device)))
+    return dam
+
+
+@pytest.mark.parametrize("case", OC.MAPS_CASES, ids=OC.maps_case_id)
+def test_surface_maps_forward_and_backward_per_pixel(gpu_device, held, case):
+    L, dev = _lib.lib(), gpu_device
+    kind, size, r, _ = case
+    H, W = size
+    name = "maps " + OC.maps_case_id(case)
+    amh, gh = OC.reg_allmap(kind, size), OC.maps_gout(case)
+    am, gout = amh.to(dev), gh.to(dev)
+    rays, rot = (_c9(t) for t in OC.maps_rays(size))
+    truth = OC.maps_truth(case)
+    outs = [_maps_forward(L, am, rays, rot, r) for _ in range(2)]
+    dams = [_maps_backward(L, am, rays, rot, r, gout) for _ in range(2)]
+    torch.cuda.synchronize(dev)
+    assert bool(torch.isfinite(outs[0]).all()) and bool(torch.isfinite(dams[0]).all())      # every element was written
+    assert torch.equal(outs[0], outs[1]) and torch.equal(dams[0], dams[1])                  # the same call twice: the same bits
+    out, dam = outs[0].cpu(), dams[0].cpu()
+    lit = amh[1] > 0
+    for which, sel in (("lit", lit), ("holes", ~lit)):
+        for c in range(7):
+            held(name, f"out[{c}] {which}", out[c], truth["out"][c], where=sel)
+            held(name, f"d_allmap[{c}] {which}", dam[c], truth["dam"][c], where=sel)
+    # exact facts.  surf_normal is 0 on the border, everywhere when there is no interior; rend_dist is outside this node; no
+    # gradient passes where there is no splat
+    border = torch.ones(H, W, dtype=torch.bool)
+    if H >= 3 and W >= 3:
+        border[1:-1, 1:-1] = False
+    assert float(out[4:7][:, border].abs().sum()) == 0.0
+    assert float(dam[6].abs().sum()) == 0.0
+    assert float(dam[0][~lit].abs().sum()) == 0.0 and float(dam[1][~lit].abs().sum()) == 0.0
+    # surf_depth where D / A or the median is not a number the reference keeps: nan_to_num(., 0, 0) stands in, to the bit (one
+    # of the two products is with an exact 0, so a contracted multiply-add gives the same bits)
+    e, med = amh[0] / amh[1], amh[5]
+    replaced = ~torch.isfinite(e) | ~torch.isfinite(med)
+    if bool(replaced.any()):
+        r32 = torch.tensor(r, dtype=torch.float32)
+        want = (1.0 - r32) * torch.nan_to_num(e, 0.0, 0.0) + r32 * torch.nan_to_num(med, 0.0, 0.0)
+        both = torch.isfinite(e) & torch.isfinite(med)
+        assert not bool((replaced & both).any()) and torch.equal(out[3][replaced], want[replaced])
+    if kind == "nonfinite" and H * W >= 9:
+        assert bool(((amh[1] == 0) & (amh[0] > 0)).any()) and bool(torch.isnan(med).any()) and bool(torch.isinf(med).any())
+    # the gradient of surf_normal on the border is never read (the border is a constant): NaN there changes no bit
+    poisoned = gh.clone()
+    poisoned[4:7][:, border] = float("nan")
+    dam_p = _maps_backward(L, am, rays, rot, r, poisoned.to(dev))
+    cleared = gh.clone()
+    cleared[4:7][:, border] = 0.0
+    dam_c = _maps_backward(L, am, rays, rot, r, cleared.to(dev))
+    torch.cuda.synchronize(dev)
+    assert torch.equal(dam_p, dam_c) and torch.equal(dam_c, dams[0])
+
+
+WRAPPER_CASES = [next(c for c in OC.MAPS_CASES if c[0] == kind and c[1] == size)
+                 for kind, size in zip(OC.REG_KINDS, [(17, 33), (31, 18), (48, 40)] * 4)]
+
+
+@pytest.mark.parametrize("case", WRAPPER_CASES, ids=OC.maps_case_id)
+def test_surface_maps_node_passes_partial_gradients(gpu_device, case):
+    """fused_surface_maps.surface_maps: whichever of its three outputs is consumed, allmap.grad holds the bits of the direct call
+    with zeros for the gradients that did not arrive; a non-contiguous allmap gives the bits of its contiguous copy."""
+    from gaussmart_amd.fused_surface_maps import surface_maps
+    L, dev = _lib.lib(), gpu_device
+    kind, size, r, _ = case
+    H, W = size
+    cam = OC.reg_camera(size, rotated=True)
+    am, gout = OC.reg_allmap(kind, size).to(dev), OC.maps_gout(case).to(dev)
+    rays, rot = (_c9(t) for t in OC.maps_rays(size))
+    out = _maps_forward(L, am, rays, rot, r)
+    planes = {"rend_normal": slice(0, 3), "surf_depth": slice(3, 4), "surf_normal": slice(4, 7)}
+    wide = torch.zeros(7, H + 2, W + 5, device=dev)
+    wide[:, 1:H + 1, 3:W + 3] = am
+    for used in (["surf_depth"], ["surf_normal"], ["rend_normal"], list(planes)):
+        seen = torch.zeros_like(gout)
+        for k in used:
+            seen[planes[k]] = gout[planes[k]]
+        want = _maps_backward(L, am, rays, rot, r, seen)
+        for leaf in (am.clone().requires_grad_(True), wide[:, 1:H + 1, 3:W + 3].detach().requires_grad_(True)):
+            maps = dict(zip(planes, surface_maps(leaf, cam, r)))
+            for k, s in planes.items():
+                assert torch.equal(maps[k], out[s]), (used, k)
+            sum((maps[k] * gout[planes[k]]).sum() for k in used).backward()
+            assert torch.equal(leaf.grad, want), used
+    assert not wide[:, 1:H + 1, 3:W + 3].is_contiguous()
+
+
+def test_moved_camera_gives_the_new_pose(gpu_device):
+    """The per-camera caches follow the pose: after a camera was moved in place, the fused maps and the fused regularizer give the
+    bits of a fresh camera at the new pose."""
+    from gaussmart_amd.fused_regularizer import surface_regularizer
+    from gaussmart_amd.fused_surface_maps import surface_maps
+    from gaussmart_amd.synthetic import jittered_cameras
+    dev = gpu_device
+    H, W = 31, 18
+    am = OC.reg_allmap("sphere", (H, W)).to(dev)
+
+    def run(cam):
+        a = am.clone().requires_grad_(True)
+        maps = surface_maps(a, cam, 0.3)
+        loss, nm, dm = surface_regularizer(a, cam, 0.3, 0.05, 100.0)
+        (sum(m.sum() for m in maps) + loss).backward()
+        return [m.detach().clone() for m in maps] + [loss.detach().clone(), nm.clone(), dm.clone(), a.grad.clone()]
+
+    cam_a, cam_b = jittered_cameras(3, W, H, seed=5, device=dev, amount=0.4)[1:]
+    before = run(cam_a)
+    cam_a.world_view_transform.copy_(cam_b.world_view_transform)
+    cam_a.full_proj_transform.copy_(cam_b.full_proj_transform)
+    moved, fresh = run(cam_a), run(jittered_cameras(3, W, H, seed=5, device=dev, amount=0.4)[2])
+    assert all(torch.equal(x, y) for x, y in zip(moved, fresh))
+    assert not torch.equal(moved[0], before[0]) and not torch.equal(moved[2], before[2])
 
 
 # ------------------------------------------------------------------------------------------------ objective finish
