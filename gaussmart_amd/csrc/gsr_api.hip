@@ -533,7 +533,10 @@ extern "C" int32_t gsr_buffer_field(int32_t which, const char* name, int32_t N, 
         if (!strcmp(name, "splat")) { *offset = L.splat; *bytes = size_t(N) * GSR_SPLAT_FLOATS * 4; return GSR_OK; }
         if (!strcmp(name, "clamped")) { *offset = L.clamped; *bytes = size_t(N) * 4; return GSR_OK; }
         if (!strcmp(name, "tiles_touched")) { *offset = L.tiles_touched; *bytes = size_t(N) * 4; return GSR_OK; }
+        if (!strcmp(name, "tile_rect")) { *offset = L.tile_rect; *bytes = size_t(N) * 8; return GSR_OK; }
         if (!strcmp(name, "depth_key")) { *offset = L.depth_key; *bytes = size_t(N) * 4; return GSR_OK; }
+        // (reserved and written only by a call that is neither forward-only nor colour-cached: GsrGeomLayout's with_jac)
+        if (!strcmp(name, "color_jac")) { *offset = L.color_jac; *bytes = size_t(N) * 9 * 4; return GSR_OK; }
         if (!strcmp(name, "order")) { *offset = L.order; *bytes = size_t(N) * 4; return GSR_OK; }
         if (!strcmp(name, "offs")) { *offset = L.offs; *bytes = size_t(N + 1) * 4; return GSR_OK; }
     } else if (which == GSR_BUF_BINNING) {

@@ -634,15 +634,28 @@ class GaussianRasterizer(nn.Module):
 
 
 def rasterize_debug(means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                    cov3D_precomp=None, *, raster_settings, flags=None):
+                    cov3D_precomp=None, *, raster_settings, flags=None, raw_features=None, color_cache=None):
     """Forward only, returning the operator outputs AND typed views of every saved buffer field
-    (include/gsr.h: gsr_buffer_field).  Used by the parity tests; no autograd."""
+    (include/gsr.h: gsr_buffer_field).  Used by the parity tests; no autograd.
+    `raw_features` = (features_dc [N,1,3], features_rest [N,K-1,3]): the raw signature (GSR_FLAG_RAW_PARAMS, split SH
+    storage) -- opacities, scales and rotations are then the raw parameters -- with the optional `color_cache` [13 N] of
+    FusedAdam (GSR_FLAG_COLOR_CACHED: "color_jac" is then absent from GEOM and comes back as None, as it does with
+    GSR_FLAG_FORWARD_ONLY in `flags`)."""
     device = means3D.device
     rs = raster_settings
-    inputs, g, channels, sh_coeffs = _pack_reference(means3D, shs, colors_precomp, opacities, scales, rotations,
-                                                     cov3D_precomp)
-    color, radii, allmap, D, alloc, _ = _forward(rs, g, sh_coeffs, DEFAULT_FLAGS if flags is None else flags, channels,
-                                                 device)
+    flags = DEFAULT_FLAGS if flags is None else int(flags)
+    if raw_features is not None:
+        if shs is not None or colors_precomp is not None or cov3D_precomp is not None:
+            raise ValueError("raw_features excludes shs, colors_precomp and cov3D_precomp")
+        inputs, g, sh_coeffs = _pack_raw(means3D, raw_features[0], raw_features[1], opacities, scales, rotations, color_cache)
+        channels = 3
+        flags |= _lib.GSR_FLAG_RAW_PARAMS | (_lib.GSR_FLAG_COLOR_CACHED if color_cache is not None else 0)
+    else:
+        if color_cache is not None:
+            raise ValueError("color_cache needs raw_features")
+        inputs, g, channels, sh_coeffs = _pack_reference(means3D, shs, colors_precomp, opacities, scales, rotations,
+                                                         cov3D_precomp)
+    color, radii, allmap, D, alloc, _ = _forward(rs, g, sh_coeffs, flags, channels, device)
     torch.cuda.synchronize(device)
     N = g.count
     H, W = int(rs.image_height), int(rs.image_width)
@@ -650,8 +663,10 @@ def rasterize_debug(means3D, opacities, shs=None, colors_precomp=None, scales=No
     res = dict(color=color, allmap=allmap, radii=radii, num_rendered=D, _lease=alloc.kept)
     spec = {
         _lib.GSR_BUF_GEOM: [("splat", torch.float32, (N, 20)), ("clamped", torch.int32, (N,)),
-                            ("tiles_touched", torch.int32, (N,)), ("depth_key", torch.int32, (N,)),
-                            ("order", torch.int32, (N,)), ("offs", torch.int32, (N + 1,))],
+                            ("tiles_touched", torch.int32, (N,)), ("tile_rect", torch.int32, (N, 2)),
+                            ("depth_key", torch.int32, (N,)), ("order", torch.int32, (N,)), ("offs", torch.int32, (N + 1,))]
+                           + ([] if flags & (_lib.GSR_FLAG_COLOR_CACHED | _lib.GSR_FLAG_FORWARD_ONLY)     # (not reserved then)
+                              else [("color_jac", torch.float32, (N, 3, 3))]),
         _lib.GSR_BUF_BINNING: [("point_list", torch.int32, (D,)), ("inst_row", torch.int32, (D,)),
                                ("ranges", torch.int32, (-1, 2)), ("covered", torch.int32, (-1, 4)),
                                ("touch", torch.int32, (D,)), ("row_count", torch.uint8, (D,))],
@@ -663,6 +678,7 @@ def rasterize_debug(means3D, opacities, shs=None, colors_precomp=None, scales=No
             off, nbytes = _lib.buffer_field(which, name, N, D, W, H)
             res[name] = buf[off:off + nbytes].view(dt).reshape(shape) if nbytes else \
                 torch.empty(0, dtype=dt, device=device).reshape([s if s >= 0 else 0 for s in shape])
+    res.setdefault("color_jac", None)
     # first emission index of every Gaussian (depth rank r = order^-1): offs is indexed by rank
     res["inst_begin"] = torch.zeros(N, dtype=torch.int32, device=device)
     res["inst_begin"][res["order"].long()] = res["offs"][:N]

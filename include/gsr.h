@@ -51,8 +51,8 @@ extern "C" {
                                 18: SAM image encoder and mask selection (GsrSamConfig, gsr_sam_*); still 18 with SAM's
                                     prompt encoder and mask decoder (gsr_sam_dec_*, gsr_sam_decode), with SAM2's image
                                     encoder (GsrSam2Config, gsr_sam2_*) and with SAM2's prompt encoder and mask decoder
-                                    (gsr_sam2_dec_*, gsr_sam2_decode): additions only, no existing struct or signature
-                                    changed */
+                                    (gsr_sam2_dec_*, gsr_sam2_decode), and with the gsr_buffer_field names "tile_rect" and
+                                    "color_jac": additions only, no existing struct or signature changed */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -242,7 +242,11 @@ int32_t gsr_backward_with_job(const GsrView* view, const GsrGaussians* g, int32_
 /* Introspection of the saved buffers, for parity tests.  Writes byte offset and size of a named
  * field inside buffer `which` for a problem of N Gaussians, D instances, W x H pixels.
  * Names: GEOM: "splat" f32[N,20], "clamped" u32[N], "tiles_touched" u32[N], "depth_key" u32[N],
- *        "order" u32[N] (depth rank -> Gaussian id), "offs" u32[N+1] (depth rank -> first emission index);
+ *        "order" u32[N] (depth rank -> Gaussian id), "offs" u32[N+1] (depth rank -> first emission index),
+ *        "tile_rect" u32[N,2] (x0 | y0 << 16, width | height << 16 on the 16-pixel tile grid; 0, 0 when culled),
+ *        "color_jac" f32[N,3,3] (d rgb[c] / d dir[a] of the SH colour pass, direction components independent; written
+ *        for visible Gaussians only, and present only after a gsr_forward that is neither GSR_FLAG_FORWARD_ONLY nor
+ *        GSR_FLAG_COLOR_CACHED and whose colour pass is the 16-lane form -- otherwise the region is absent or stale);
  *        BINNING: "point_list" u32[D], "inst_row" u32[D] (emission index of each list entry), "ranges" u32[tiles,2],
  *                 "covered" u32[tiles,4] (list entries each 8x8 quad staged), "touch" u32[D] (per list entry: one byte per
  *                 quad, one bit per 4x4 block it was blended into; a quad's byte is defined below its `covered`),
