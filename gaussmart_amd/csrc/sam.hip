@@ -51,10 +51,7 @@ extern "C" int32_t gsr_sam_embed(const float* pixel_values, int32_t S, int32_t h
         gsr_set_error("sam embed: pixel_values / patch_w / patch_b / pos_embed / out is null");
         return GSR_E_INVALID;
     }
-    if (!ws || ws_bytes < gsr_sam_embed_workspace_bytes(S)) {
-        gsr_set_error("ws_bytes: sam embed workspace too small (%zu < %zu bytes)", ws_bytes, gsr_sam_embed_workspace_bytes(S));
-        return GSR_E_INVALID;
-    }
+    if (!vit_check_ws("sam embed", ws, ws_bytes, gsr_sam_embed_workspace_bytes(S))) return GSR_E_INVALID;
     return sv_embed(pixel_values, S, hidden, static_cast<const dn_half*>(patch_w), static_cast<const dn_half*>(patch_b),
                     static_cast<const dn_half*>(pos_embed), static_cast<dn_half*>(ws), out, static_cast<hipStream_t>(stream_));
 }
@@ -209,21 +206,13 @@ extern "C" int32_t gsr_sam_attn(const void* qkv, const void* qkv_bias, const voi
         gsr_set_error("sam attn: qkv / qkv_bias / rel_pos_h / rel_pos_w / out is null");
         return GSR_E_INVALID;
     }
-    if (!ws || ws_bytes < gsr_sam_attn_workspace_bytes(g, window, heads)) {
-        gsr_set_error("ws_bytes: sam attn workspace too small (%zu < %zu bytes)", ws_bytes, gsr_sam_attn_workspace_bytes(g, window, heads));
-        return GSR_E_INVALID;
-    }
+    if (!vit_check_ws("sam attn", ws, ws_bytes, gsr_sam_attn_workspace_bytes(g, window, heads))) return GSR_E_INVALID;
     return sv_attn(static_cast<const dn_half*>(qkv), static_cast<const dn_half*>(qkv_bias), static_cast<const dn_half*>(rel_pos_h),
                    static_cast<const dn_half*>(rel_pos_w), g, window, heads, head_dim, static_cast<float*>(ws),
                    static_cast<dn_half*>(out), static_cast<hipStream_t>(stream_));
 }
 
 // ---------------------------------------------------------------- SV_NECK
-__global__ void __launch_bounds__(256) sv_cast_kernel(const float* __restrict__ x, int64_t n, dn_half* __restrict__ y) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) y[i] = (dn_half)x[i];
-}
-
 // col[t][c 9 + ky 3 + kx] = ln[(y + ky - 1) g + (x + kx - 1)][c], zero outside the grid: Conv2d's own weight order [C,C,3,3]
 __global__ void __launch_bounds__(256) sv_im2col3_kernel(const dn_half* __restrict__ ln, int g, int Cn, dn_half* __restrict__ col) {
     const int64_t n = (int64_t)g * g * 9 * Cn;
@@ -234,14 +223,6 @@ __global__ void __launch_bounds__(256) sv_im2col3_kernel(const dn_half* __restri
     const int c = k / 9, tap = k - 9 * c, ky = tap / 3, kx = tap - 3 * ky;
     const int y = (int)(tok / g) + ky - 1, x = (int)(tok % g) + kx - 1;
     col[i] = (y >= 0 && y < g && x >= 0 && x < g) ? ln[((int64_t)y * g + x) * Cn + c] : (dn_half)0.f;
-}
-
-// [T,C] -> [C,T]
-__global__ void __launch_bounds__(256) sv_transpose_kernel(const float* __restrict__ in, int64_t T, int Cn, float* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= T * Cn) return;
-    const int64_t c = i / T, tok = i - c * T;
-    out[i] = in[tok * Cn + c];
 }
 
 struct SvNeckLayout {
@@ -264,16 +245,14 @@ static int sv_neck(const float* x, int g, int hidden, int Cn, const dn_half* con
                    const dn_half* conv2, const dn_half* ln2w, const dn_half* ln2b, float eps, const SvNeckLayout& lay, float* out,
                    hipStream_t s) {
     const int64_t T = (int64_t)g * g;
-    hipLaunchKernelGGL(sv_cast_kernel, dim3((unsigned)((T * hidden + 255) / 256)), dim3(256), 0, s, x, T * hidden, lay.xh);
-    GSR_LAUNCH_CHECK();
+    GSR_TRY(vit_cast(x, T * hidden, lay.xh, s));
     GSR_TRY(dn_linear(lay.xh, conv1, nullptr, nullptr, lay.c1, T, hidden, Cn, DN_EPI_F32, s));
     GSR_TRY(dn_norm(lay.c1, T, Cn, Cn, ln1w, ln1b, eps, lay.ln, 0, s));
     hipLaunchKernelGGL(sv_im2col3_kernel, dim3((unsigned)((T * 9 * Cn + 255) / 256)), dim3(256), 0, s, lay.ln, g, Cn, lay.col);
     GSR_LAUNCH_CHECK();
     GSR_TRY(dn_linear(lay.col, conv2, nullptr, nullptr, lay.c2, T, 9 * Cn, Cn, DN_EPI_F32, s));
     GSR_TRY(dn_norm(lay.c2, T, Cn, Cn, ln2w, ln2b, eps, lay.c1, 1, s));
-    hipLaunchKernelGGL(sv_transpose_kernel, dim3((unsigned)((T * Cn + 255) / 256)), dim3(256), 0, s, lay.c1, T, Cn, out);
-    GSR_LAUNCH_CHECK();
+    GSR_TRY(vit_transpose(lay.c1, T, Cn, nullptr, out, s));
     return GSR_OK;
 }
 
@@ -300,10 +279,7 @@ extern "C" int32_t gsr_sam_neck(const float* x, int32_t g, int32_t hidden, int32
         return GSR_E_INVALID;
     }
     SvNeckLayout lay(g, hidden, channels, ws);
-    if (!ws || ws_bytes < lay.total) {
-        gsr_set_error("ws_bytes: sam neck workspace too small (%zu < %zu bytes)", ws_bytes, lay.total);
-        return GSR_E_INVALID;
-    }
+    if (!vit_check_ws("sam neck", ws, ws_bytes, lay.total)) return GSR_E_INVALID;
     auto hp = [](const void* p) { return static_cast<const dn_half*>(p); };
     return sv_neck(x, g, hidden, channels, hp(conv1_w), hp(ln1_w), hp(ln1_b), hp(conv2_w), hp(ln2_w), hp(ln2_b), 1e-6f, lay, out,
                    static_cast<hipStream_t>(stream_));
@@ -373,14 +349,10 @@ extern "C" int32_t gsr_sam_encode(const GsrSamConfig* cfg, const void* const* we
                       gsr_sam_num_weights(cfg->layers));
         return GSR_E_INVALID;
     }
-    for (int i = 0; i < n_weights; ++i)
-        if (!weights_host[i]) { gsr_set_error("sam: weight %d of the table is null", i); return GSR_E_INVALID; }
+    if (!vit_check_table("sam", weights_host, n_weights)) return GSR_E_INVALID;
     if (!pixel_values || !out) { gsr_set_error("sam: pixel_values / out is null"); return GSR_E_INVALID; }
     SvLayout lay(cfg, ws);
-    if (!ws || ws_bytes < lay.total) {
-        gsr_set_error("ws_bytes: sam workspace too small (%zu < %zu bytes)", ws_bytes, lay.total);
-        return GSR_E_INVALID;
-    }
+    if (!vit_check_ws("sam", ws, ws_bytes, lay.total)) return GSR_E_INVALID;
     auto wp = [&](int i) { return static_cast<const dn_half*>(weights_host[i]); };
     hipStream_t s = static_cast<hipStream_t>(stream_);
     const int hid = cfg->hidden, g = cfg->image_size / VIT_PATCH;
@@ -643,10 +615,7 @@ extern "C" int32_t gsr_sam_nms(const float* boxes, const float* scores, const ui
                                size_t ws_bytes, int32_t* kept, int32_t* count, gsr_stream_t stream_) {
     if (n < 1 || n > SM_NMS_MAX) { gsr_set_error("sam nms: n %d is outside 1 .. %d", n, SM_NMS_MAX); return GSR_E_INVALID; }
     if (!boxes || !scores || !kept || !count) { gsr_set_error("sam nms: boxes / scores / kept / count is null"); return GSR_E_INVALID; }
-    if (!ws || ws_bytes < gsr_sam_nms_workspace_bytes(n)) {
-        gsr_set_error("ws_bytes: sam nms workspace too small (%zu < %zu bytes)", ws_bytes, gsr_sam_nms_workspace_bytes(n));
-        return GSR_E_INVALID;
-    }
+    if (!vit_check_ws("sam nms", ws, ws_bytes, gsr_sam_nms_workspace_bytes(n))) return GSR_E_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream_);
     int32_t* order = static_cast<int32_t*>(ws);
     hipLaunchKernelGGL(sm_rank_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scores, keep_in, n, order);

@@ -61,10 +61,7 @@ extern "C" int32_t gsr_sam2_embed(const float* pixel_values, int32_t S, int32_t 
         gsr_set_error("sam2 embed: pixel_values / patch_w / patch_b / pos_table / out is null");
         return GSR_E_INVALID;
     }
-    if (!ws || ws_bytes < gsr_sam2_embed_workspace_bytes(S)) {
-        gsr_set_error("ws_bytes: sam2 embed workspace too small (%zu < %zu bytes)", ws_bytes, gsr_sam2_embed_workspace_bytes(S));
-        return GSR_E_INVALID;
-    }
+    if (!vit_check_ws("sam2 embed", ws, ws_bytes, gsr_sam2_embed_workspace_bytes(S))) return GSR_E_INVALID;
     return hv_embed(pixel_values, S, embed, static_cast<const dn_half*>(patch_w), static_cast<const dn_half*>(patch_b),
                     static_cast<const dn_half*>(pos_table), static_cast<dn_half*>(ws), out, static_cast<hipStream_t>(stream_));
 }
@@ -235,11 +232,6 @@ extern "C" int32_t gsr_sam2_pool(const float* x, int32_t g, int32_t channels, fl
 }
 
 // ---------------------------------------------------------------- HV_NECK
-__global__ void __launch_bounds__(256) hv_cast_kernel(const float* __restrict__ x, int64_t n, dn_half* __restrict__ y) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) y[i] = (dn_half)x[i];
-}
-
 // lat[(y, x)][c] += up[(y / 2, x / 2)][c]: the top-down path's nearest up-sampling by 2 and its one fp32 addition, in place
 __global__ void __launch_bounds__(256) hv_topdown_kernel(float* __restrict__ lat, const float* __restrict__ up, int g, int Cn) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -248,16 +240,6 @@ __global__ void __launch_bounds__(256) hv_topdown_kernel(float* __restrict__ lat
     const int64_t tok = i / Cn;
     const int y = (int)(tok / g), x = (int)(tok - (int64_t)y * g);
     lat[i] = lat[i] + up[((int64_t)(y / 2) * (g / 2) + x / 2) * Cn + c];
-}
-
-// [T,C] -> [C,T], plus add[c] where add is given (one fp32 addition)
-__global__ void __launch_bounds__(256) hv_transpose_kernel(const float* __restrict__ in, int64_t T, int Cn, const float* __restrict__ add,
-                                                           float* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= T * Cn) return;
-    const int64_t c = i / T, tok = i - c * T;
-    const float v = in[tok * Cn + c];
-    out[i] = add ? v + add[c] : v;
 }
 
 struct HvNeckLayout {
@@ -289,9 +271,7 @@ static int hv_check_neck(int g0, int embed, int D, int top_down_mask) {
 
 static int hv_neck_cast(const float* x, int i, int g0, int embed, const HvNeckLayout& lay, hipStream_t s) {
     const int64_t n = (int64_t)(g0 >> i) * (g0 >> i) * ((int64_t)embed << i);
-    hipLaunchKernelGGL(hv_cast_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, lay.xh[i]);
-    GSR_LAUNCH_CHECK();
-    return GSR_OK;
+    return vit_cast(x, n, lay.xh[i], s);
 }
 
 // nw: the GSR_SAM2_W_NECK entries of the weight table; the four streams are in lay.xh already
@@ -311,17 +291,12 @@ static int hv_neck_finish(int g0, int embed, int D, int top_down_mask, const voi
     for (int i = 0; i < 2; ++i) {           // conv_s0 on level 0, conv_s1 on level 1
         const int g = g0 >> i, Co = i == 0 ? D / 8 : D / 4;
         const int64_t T = (int64_t)g * g;
-        hipLaunchKernelGGL(hv_cast_kernel, dim3((unsigned)((T * D + 255) / 256)), dim3(256), 0, s, lay.lat[i], T * D, lay.ph);
-        GSR_LAUNCH_CHECK();
+        GSR_TRY(vit_cast(lay.lat[i], T * D, lay.ph, s));
         GSR_TRY(dn_linear_k8(lay.ph, hp(8 + 2 * i), hp(9 + 2 * i), nullptr, lay.cs, T, D, Co, DN_EPI_F32, s));
-        hipLaunchKernelGGL(hv_transpose_kernel, dim3((unsigned)((T * Co + 255) / 256)), dim3(256), 0, s, lay.cs, T, Co, (const float*)nullptr, outs[i]);
-        GSR_LAUNCH_CHECK();
+        GSR_TRY(vit_transpose(lay.cs, T, Co, nullptr, outs[i], s));
     }
     const int64_t T2 = (int64_t)(g0 >> 2) * (g0 >> 2);
-    hipLaunchKernelGGL(hv_transpose_kernel, dim3((unsigned)((T2 * D + 255) / 256)), dim3(256), 0, s, lay.lat[2], T2, D,
-                       static_cast<const float*>(nw[12]), out2);
-    GSR_LAUNCH_CHECK();
-    return GSR_OK;
+    return vit_transpose(lay.lat[2], T2, D, static_cast<const float*>(nw[12]), out2, s);
 }
 
 extern "C" size_t gsr_sam2_neck_workspace_bytes(int32_t g0, int32_t embed, int32_t fpn_hidden) {
@@ -342,10 +317,7 @@ extern "C" int32_t gsr_sam2_neck(const float* const* streams_host, int32_t g0, i
     for (int i = 0; i < GSR_SAM2_W_NECK; ++i)
         if (!neck_weights_host[i]) { gsr_set_error("sam2 neck: weight %d is null", i); return GSR_E_INVALID; }
     HvNeckLayout lay(g0, embed, fpn_hidden, ws);
-    if (!ws || ws_bytes < lay.total) {
-        gsr_set_error("ws_bytes: sam2 neck workspace too small (%zu < %zu bytes)", ws_bytes, lay.total);
-        return GSR_E_INVALID;
-    }
+    if (!vit_check_ws("sam2 neck", ws, ws_bytes, lay.total)) return GSR_E_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream_);
     for (int i = 0; i < HV_STAGES; ++i) GSR_TRY(hv_neck_cast(streams_host[i], i, g0, embed, lay, s));
     return hv_neck_finish(g0, embed, fpn_hidden, top_down_mask, neck_weights_host, lay, out0, out1, out2, s);
@@ -452,18 +424,12 @@ extern "C" int32_t gsr_sam2_encode(const GsrSam2Config* cfg, const void* const* 
                         return GSR_E_INVALID;
                     }
                 }
-        for (int i = 0; i < n_weights; ++i)
-            if ((i < GSR_SAM2_W_BLOCK0 || i >= n_weights - GSR_SAM2_W_NECK) && !weights_host[i]) {
-                gsr_set_error("sam2: weight %d of the table is null", i);
-                return GSR_E_INVALID;
-            }
+        if (!vit_check_table("sam2", weights_host, GSR_SAM2_W_BLOCK0) || !vit_check_table("sam2", weights_host, n_weights, n_weights - GSR_SAM2_W_NECK))
+            return GSR_E_INVALID;
     }
     if (!pixel_values || !out0 || !out1 || !out2) { gsr_set_error("sam2: pixel_values / an output is null"); return GSR_E_INVALID; }
     HvLayout lay(cfg, ws);
-    if (!ws || ws_bytes < lay.total) {
-        gsr_set_error("ws_bytes: sam2 workspace too small (%zu < %zu bytes)", ws_bytes, lay.total);
-        return GSR_E_INVALID;
-    }
+    if (!vit_check_ws("sam2", ws, ws_bytes, lay.total)) return GSR_E_INVALID;
     auto wp = [&](int i) { return static_cast<const dn_half*>(weights_host[i]); };
     hipStream_t s = static_cast<hipStream_t>(stream_);
     const int g0 = cfg->image_size / 4;

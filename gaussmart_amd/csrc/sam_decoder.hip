@@ -401,10 +401,7 @@ static int sd_i2t_entry(const void* qx, const float* qpe, const float* k, const 
         return GSR_E_INVALID;
     }
     SdI2tLayout lay(P, T, ws);
-    if (!ws || ws_bytes < lay.total) {
-        gsr_set_error("ws_bytes: sam dec i2t workspace too small (%zu < %zu bytes)", ws_bytes, lay.total);
-        return GSR_E_INVALID;
-    }
+    if (!vit_check_ws("sam dec i2t", ws, ws_bytes, lay.total)) return GSR_E_INVALID;
     auto hp = [](const void* p) { return static_cast<const dn_half*>(p); };
     return sd_i2t<TOK>(hp(qx), qpe, k, v, hp(x), P, T, shared != 0, hp(out_w), hp(out_b), hp(ln_w), hp(ln_b), eps, lay.ctx, lay.att,
                        static_cast<dn_half*>(x_out), static_cast<hipStream_t>(stream_));
@@ -576,10 +573,7 @@ static int sd_upscale_entry(const void* x, int g, int P, const void* conv1_w, co
     }
     const bool skips = feat_s0 != nullptr;
     SdUpLayout lay(g, P, skips, ws);
-    if (!ws || ws_bytes < lay.total) {
-        gsr_set_error("ws_bytes: sam dec upscale workspace too small (%zu < %zu bytes)", ws_bytes, lay.total);
-        return GSR_E_INVALID;
-    }
+    if (!vit_check_ws("sam dec upscale", ws, ws_bytes, lay.total)) return GSR_E_INVALID;
     hipStream_t s = static_cast<hipStream_t>(stream_);
     if (skips) GSR_TRY(sd_skips(feat_s0, feat_s1, g, lay.s0t, lay.s1t, s));
     auto hp = [](const void* p) { return static_cast<const dn_half*>(p); };
@@ -687,10 +681,7 @@ static int sd_decode(const SdModel& model, int g, const void* const* weights_hos
                      int P, int image_size, void* ws, size_t ws_bytes, float* low_res, float* iou, hipStream_t s) {
     const bool skips = model.feat_s0 != nullptr;
     SdLayout lay(g, P, TOK, skips, ws);
-    if (!ws || ws_bytes < lay.total) {
-        gsr_set_error("ws_bytes: sam decoder workspace too small (%zu < %zu bytes)", ws_bytes, lay.total);
-        return GSR_E_INVALID;
-    }
+    if (!vit_check_ws("sam decoder", ws, ws_bytes, lay.total)) return GSR_E_INVALID;
     const int T = g * g;
     const int64_t R = (int64_t)P * TOK, PT = (int64_t)P * T;
     auto W = [&](int i) { return static_cast<const dn_half*>(weights_host[i]); };
@@ -824,8 +815,7 @@ static int sd_decode_check(int g, const void* const* weights_host, int n_weights
         gsr_set_error("sam decoder: the weight table is null or has %d entries (%d are needed)", n_weights, count);
         return GSR_E_INVALID;
     }
-    for (int i = 0; i < n_weights; ++i)
-        if (!weights_host[i]) { gsr_set_error("sam decoder: weight %d of the table is null", i); return GSR_E_INVALID; }
+    if (!vit_check_table("sam decoder", weights_host, n_weights)) return GSR_E_INVALID;
     if (!emb || !pe || !points || !low_res || !iou) { gsr_set_error("sam decoder: emb / pe / points / low_res / iou is null"); return GSR_E_INVALID; }
     return GSR_OK;
 }

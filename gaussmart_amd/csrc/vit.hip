@@ -50,6 +50,37 @@ extern "C" int32_t gsr_dino_norm(const float* x, int64_t rows, int32_t hidden, i
                    static_cast<hipStream_t>(stream_));
 }
 
+// ---------------------------------------------------------------- the necks' cast and transpose (SV_NECK, HV_NECK)
+__global__ void __launch_bounds__(256) vit_cast_kernel(const float* __restrict__ x, int64_t n, dn_half* __restrict__ y) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] = (dn_half)x[i];
+}
+
+// [T,C] -> [C,T]; ADD: plus add[c] (one fp32 addition)
+template <bool ADD>
+__global__ void __launch_bounds__(256) vit_transpose_kernel(const float* __restrict__ in, int64_t T, int Cn, const float* __restrict__ add,
+                                                            float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= T * Cn) return;
+    const int64_t c = i / T, tok = i - c * T;
+    const float v = in[tok * Cn + c];
+    out[i] = ADD ? v + add[c] : v;
+}
+
+int vit_cast(const float* x, int64_t n, dn_half* y, hipStream_t s) {
+    hipLaunchKernelGGL(vit_cast_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, y);
+    GSR_LAUNCH_CHECK();
+    return GSR_OK;
+}
+
+int vit_transpose(const float* in, int64_t T, int Cn, const float* add, float* out, hipStream_t s) {
+    const dim3 grid((unsigned)((T * Cn + 255) / 256));
+    if (add) hipLaunchKernelGGL(vit_transpose_kernel<true>, grid, dim3(256), 0, s, in, T, Cn, add, out);
+    else hipLaunchKernelGGL(vit_transpose_kernel<false>, grid, dim3(256), 0, s, in, T, Cn, add, out);
+    GSR_LAUNCH_CHECK();
+    return GSR_OK;
+}
+
 // ---------------------------------------------------------------- DN_LINEAR
 // D[m][n] = sum_k x[m][k] w[n][k]: both operands have k fastest, which is what the matrix instruction's A and B fragments want
 // (lane l: 8 consecutive k of row l & 31, k = 8 (l >> 5) + j).  A workgroup of 4 waves owns 128 rows x 128 columns, a wave

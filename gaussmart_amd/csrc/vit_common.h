@@ -1,6 +1,7 @@
-// What the ViT kernels (dino.hip, sam.hip, sam_decoder.hip) share: the DN_LINEAR and DN_NORM launchers (defined in vit.hip, rules
-// in include/gsr.h) with their epilogue values, the fragment types of the 32x32x16 f16 matrix instruction and the map of its
-// accumulator, the erf GELU, the index arithmetic of the 16x16 patch gather, and GSR_TRY.  The attention tile is in vit_attn.h.
+// What the ViT kernels (dino.hip, sam.hip, sam2.hip, sam_decoder.hip) share: the DN_LINEAR and DN_NORM launchers with their epilogue
+// values and the necks' cast and transpose (defined in vit.hip, rules in include/gsr.h), the fragment types of the 32x32x16 f16
+// matrix instruction and the map of its accumulator, the erf GELU, the index arithmetic of the 16x16 patch gather, GSR_TRY, and
+// the workspace and weight-table checks of the entry points.  The attention tile is in vit_attn.h.
 #pragma once
 #include "gsr_common.h"
 #include "wave_reduce.h"
@@ -45,6 +46,10 @@ int dn_linear_k8(const dn_half* x, const dn_half* w, const dn_half* bias, const 
                  int epi, hipStream_t s);
 int dn_norm(const float* x, int64_t rows, int hidden, int64_t in_stride, const dn_half* g, const dn_half* b, float eps, void* y,
             int out_f32, hipStream_t s);
+// the necks' element-wise passes (SV_NECK, HV_NECK): y = fp16(x) over n values; out [C,T] = in [T,C] transposed, plus add[c] where
+// add is given (one fp32 addition)
+int vit_cast(const float* x, int64_t n, dn_half* y, hipStream_t s);
+int vit_transpose(const float* in, int64_t T, int Cn, const float* add, float* out, hipStream_t s);
 
 // ---------------------------------------------------------------- device helpers
 // row of a 32x32 accumulator held in register `reg` of a lane of half `h` (the column is lane & 31)
@@ -81,3 +86,21 @@ __device__ __forceinline__ void vit_patch_store(dn_half* __restrict__ patches, c
 }
 
 static inline unsigned vit_patch_blocks(int64_t rows) { return (unsigned)((rows * (VIT_PATCH_K / 8) + 255) / 256); }
+
+// ---------------------------------------------------------------- argument checks of the entry points (host)
+// false, with the error set, when the workspace is missing or holds fewer than `need` bytes; `who` names it ("sam neck")
+static inline bool vit_check_ws(const char* who, const void* ws, size_t have, size_t need) {
+    if (ws && have >= need) return true;
+    gsr_set_error("ws_bytes: %s workspace too small (%zu < %zu bytes)", who, have, need);
+    return false;
+}
+
+// false, with the error set, at the first null among entries first .. n - 1 of a weight table
+static inline bool vit_check_table(const char* who, const void* const* table, int n, int first = 0) {
+    for (int i = first; i < n; ++i)
+        if (!table[i]) {
+            gsr_set_error("%s: weight %d of the table is null", who, i);
+            return false;
+        }
+    return true;
+}

@@ -19,7 +19,10 @@ What differs from the reference, on purpose:
   * one full-image crop only: no crop layers, no min_mask_region_area.  The crop-edge filter of the reference never fires
     for the single full-image crop and is left out.  SAM2 (the reference's sam2=True) is gaussmart_amd/sam2.py.
 `sam_host`, `decode_host`, `select_host` and `nms_host` are the torch twins (any device): they back `host=True` and the tests.
+This module also holds what SAM2 shares, once: `ModelWeights`, `random_tensors`, `load_decoder`, `device_pixels`,
+`grid_positional`, `decode_chunk`, and every step of `SamMaskGenerator`; sam2.py derives from these and supplies hooks only.
 """
+import copy
 import ctypes as C
 import json
 import math
@@ -144,45 +147,100 @@ class SamConfig:
                    image_size=int(v.get("image_size", 1024)), layer_norm_eps=float(v.get("layer_norm_eps", 1e-6)))
 
 
-def _shapes(config):
-    """name -> shape of transformers' SamModel.state_dict() for this configuration (built on the meta device)."""
-    from transformers import SamModel
+def model_shapes(config, model="SamModel"):
+    """name -> shape of the state_dict() of transformers' `model` for this configuration (built on the meta device)."""
+    import transformers
     with torch.device("meta"):
-        sd = SamModel(config.to_hf()).state_dict()
+        sd = getattr(transformers, model)(config.to_hf()).state_dict()
     return {k: tuple(v.shape) for k, v in sd.items()}
 
 
-class SamWeights:
-    """config + the tensors under SamModel.state_dict()'s names: the vision encoder in fp16 (what the kernels take), the
-    prompt encoder, the mask decoder and the shared positional embedding in fp32.  decoder=False: the vision encoder alone
-    (any output_channels; the stock decoder needs 256)."""
+class ModelWeights:
+    """What SamWeights and Sam2Weights share: config + the tensors under the names of a transformers model's state_dict(),
+    validated against its shapes, the vision encoder in fp16 (what the kernels take) and the rest in fp32; `copy`, `to`, `sub`
+    and the weight table of the decoder kernels.  A subclass sets the class attributes below and adds its encoder's table()."""
+    WHO, MODEL = None, None             # the prefix of every message; transformers' class whose state_dict() names the tensors
+    IGNORED = ()                        # patterns of keys that are dropped unread
+    HALF = ()                           # keys outside the vision encoder that are kept in fp16 too
+    # the decoder's weight table: the names of its head, of one layer, of the final attention and of what follows the IoU head,
+    # and the rows of the point_embed tensor (slot GSR_SAMD_W_POINT1) that the table takes
+    DEC_HEAD, DEC_LAYER, DEC_FINAL, DEC_TAIL, POINT_ROWS = (), (), (), (), slice(None)
 
     def __init__(self, config, tensors, decoder=True):
+        who = self.WHO
         self.config, self.decoder, self.tensors = config, bool(decoder), {}
-        tensors = dict(tensors)
+        tensors = {k: v for k, v in dict(tensors).items() if not any(re.search(p, k) for p in self.IGNORED)}
         for a, b in (TIED, TIED[::-1]):
             if decoder and a not in tensors and b in tensors:
                 tensors[a] = tensors[b]
-        want = {k: s for k, s in _shapes(config).items() if decoder or k.startswith(VISION)}
-        if decoder and config.output_channels != DECODER_CHANNELS:
-            raise ValueError(f"sam weights: the decoder needs {DECODER_CHANNELS} output channels, the encoder has {config.output_channels}")
+        want = {k: s for k, s in model_shapes(config, self.MODEL).items() if decoder or k.startswith(VISION)}
         unknown = sorted(set(tensors) - set(want))
         if unknown:
-            raise KeyError(f"sam weights: {len(unknown)} tensors have no place, e.g. {unknown[:3]}")
+            raise KeyError(f"{who} weights: {len(unknown)} tensors have no place, e.g. {unknown[:3]}")
         missing = sorted(set(want) - set(tensors))
         if missing:
-            raise KeyError(f"sam weights: {len(missing)} tensors are not filled, e.g. {missing[:3]}")
+            raise KeyError(f"{who} weights: {len(missing)} tensors are not filled, e.g. {missing[:3]}")
         for k, shape in want.items():
             t = tensors[k].detach()
             if tuple(t.shape) != shape:
-                raise ValueError(f"sam weights: {k} must be {list(shape)}, got {list(t.shape)}")
-            self.tensors[k] = t.to(torch.float16 if k.startswith(VISION) else torch.float32).contiguous()
+                raise ValueError(f"{who} weights: {k} must be {list(shape)}, got {list(t.shape)}")
+            self.tensors[k] = t.to(torch.float16 if k.startswith(VISION) or k in self.HALF else torch.float32).contiguous()
+
+    def copy(self, replace=None, keep=None, device=None):
+        """A copy that shares the configuration: the tensors of `replace` (name -> tensor) in place of these, only the names
+        `keep(name)` accepts, all on `device` (None: where they are).  Neither this object nor its dict is changed."""
+        w = copy.copy(self)
+        w.tensors = {k: t if device is None else t.to(device) for k, t in {**self.tensors, **(replace or {})}.items()
+                     if keep is None or keep(k)}
+        return w
 
     def to(self, device):
-        w = SamWeights.__new__(SamWeights)
-        w.config, w.decoder = self.config, self.decoder
-        w.tensors = {k: t.to(device) for k, t in self.tensors.items()}
-        return w
+        return self.copy(device=device)
+
+    def decoder_table(self):
+        """The tensors of the weight table of gsr_sam_decode (gsr_sam2_decode for Sam2Weights), in its order, on the tensors'
+        device: fp16 copies (self.tensors keeps its fp32 ones), except the positional matrix (fp32, as it is).  The two
+        transposed convolutions [ci,co,2,2] are re-laid as [(dy 2 + dx) co_n + co][ci] and their biases repeated per tap, which
+        is what one DN_LINEAR over the input channels takes."""
+        if not self.decoder:
+            raise ValueError(f"{self.WHO}: these weights hold no prompt encoder and mask decoder")
+        t, md = self.tensors, "mask_decoder."
+        names = list(self.DEC_HEAD)
+        for l in range(DEC_LAYERS):
+            names += [f"{md}transformer.layers.{l}.{k}" for k in self.DEC_LAYER]
+        names += [f"{md}transformer.{k}" for k in self.DEC_FINAL] + [md + k for k in DEC_UP + DEC_HYPER + DEC_IOU] + list(self.DEC_TAIL)
+        out = []
+        for k in names:
+            v = t[k]
+            if k == names[0]:
+                out.append(v.to(torch.float32).contiguous())
+                continue
+            if k == names[_lib.GSR_SAMD_W_POINT1]:
+                v = v[self.POINT_ROWS]
+            elif k.startswith(md + "upscale_conv") and k.endswith(".weight"):
+                v = v.permute(2, 3, 1, 0).reshape(4 * v.shape[1], v.shape[0])
+            elif k.startswith(md + "upscale_conv"):
+                v = v.repeat(4)
+            out.append(v.to(torch.float16).contiguous())
+        assert len(out) == _lib.GSR_SAMD_W_COUNT + len(self.DEC_TAIL)
+        return out
+
+    def sub(self, prefix):
+        """The tensors under `prefix`, with it removed (a sub-module's state dict), in fp32."""
+        return {k[len(prefix):]: t.to(torch.float32) for k, t in self.tensors.items() if k.startswith(prefix)}
+
+
+class SamWeights(ModelWeights):
+    """config + the tensors under SamModel.state_dict()'s names: the vision encoder in fp16 (what the kernels take), the
+    prompt encoder, the mask decoder and the shared positional embedding in fp32.  decoder=False: the vision encoder alone
+    (any output_channels; the stock decoder needs 256)."""
+    WHO, MODEL = "sam", "SamModel"
+    DEC_HEAD, DEC_LAYER, DEC_FINAL = DEC_HEAD, DEC_LAYER, DEC_FINAL
+
+    def __init__(self, config, tensors, decoder=True):
+        if decoder and config.output_channels != DECODER_CHANNELS:
+            raise ValueError(f"sam weights: the decoder needs {DECODER_CHANNELS} output channels, the encoder has {config.output_channels}")
+        super().__init__(config, tensors, decoder)
 
     def table(self):
         """The vision encoder's tensors in the order of gsr_sam_encode's weight table."""
@@ -190,34 +248,6 @@ class SamWeights:
         for l in range(self.config.num_hidden_layers):
             names += [f"{VISION}layers.{l}.{k}" for k in ENC_LAYER]
         return [self.tensors[k] for k in names + [VISION + k for k in ENC_NECK]]
-
-    def decoder_table(self):
-        """The tensors of gsr_sam_decode's weight table, in its order, on the tensors' device: fp16 copies, except the
-        positional matrix (fp32, as it is).  The two transposed convolutions [ci,co,2,2] are re-laid as [(dy 2 + dx) co_n + co]
-        [ci] and their biases repeated per tap, which is what one DN_LINEAR over the input channels takes."""
-        if not self.decoder:
-            raise ValueError("sam: these weights hold no prompt encoder and mask decoder")
-        t, md = self.tensors, "mask_decoder."
-        names = list(DEC_HEAD)
-        for l in range(DEC_LAYERS):
-            names += [f"{md}transformer.layers.{l}.{k}" for k in DEC_LAYER]
-        names += [f"{md}transformer.{k}" for k in DEC_FINAL] + [md + k for k in DEC_UP + DEC_HYPER + DEC_IOU]
-        out = []
-        for k in names:
-            v = t[k]
-            if k == DEC_HEAD[0]:
-                out.append(v.to(torch.float32).contiguous())
-                continue
-            if k.startswith(md + "upscale_conv") and k.endswith(".weight"):
-                v = v.permute(2, 3, 1, 0).reshape(4 * v.shape[1], v.shape[0])
-            elif k.startswith(md + "upscale_conv"):
-                v = v.repeat(4)
-            out.append(v.to(torch.float16).contiguous())
-        return out
-
-    def sub(self, prefix):
-        """The tensors under `prefix`, with it removed (a sub-module's state dict), in fp32."""
-        return {k[len(prefix):]: t.to(torch.float32) for k, t in self.tensors.items() if k.startswith(prefix)}
 
 
 # ---------------------------------------------------------------- segment_anything's names <-> SamModel's
@@ -363,14 +393,22 @@ def random_sam_weights(config=None, seed=0, decoder=None):
     U(0.5, 1.5), biases N(0, 0.1^2), everything rounded to fp16.  decoder: default, whenever the encoder has 256 channels."""
     cfg = config or SamConfig()
     decoder = cfg.output_channels == DECODER_CHANNELS if decoder is None else decoder
+    return SamWeights(cfg, random_tensors(model_shapes(cfg), seed, lambda k: decoder or k.startswith(VISION), rel_pos=math.sqrt(cfg.head_dim)),
+                      decoder=decoder)
+
+
+def random_tensors(shapes, seed, keep=None, unit=(), rel_pos=None):
+    """The recipe of random_sam_weights and random_sam2_weights: one draw per tensor of `shapes`, in its order, from one generator
+    (the tied copy of the positional matrix and the names `keep` refuses draw nothing).  unit: further names drawn N(0, 1);
+    rel_pos: what the N(0, 1) draws of SAM's relative-position tables are divided by."""
     g = torch.Generator().manual_seed(seed)
     tensors = {}
-    for name, shape in _shapes(cfg).items():
-        if not (decoder or name.startswith(VISION)) or name == TIED[0]:
+    for name, shape in shapes.items():
+        if name == TIED[0] or keep is not None and not keep(name):
             continue
-        if "rel_pos_" in name:
-            t = torch.randn(shape, generator=g) / math.sqrt(cfg.head_dim)
-        elif name.endswith("pos_embed") or name.endswith("positional_embedding") or len(shape) == 2 and shape[0] <= 8 and "embed" in name \
+        if rel_pos is not None and "rel_pos_" in name:
+            t = torch.randn(shape, generator=g) / rel_pos
+        elif "pos_embed" in name or name.endswith("positional_embedding") or name in unit or len(shape) == 2 and shape[0] <= 8 and "embed" in name \
                 or name.endswith("_token.weight") or name.endswith("_tokens.weight"):
             t = torch.randn(shape, generator=g)
         elif "norm" in name and name.endswith(".weight"):
@@ -380,7 +418,7 @@ def random_sam_weights(config=None, seed=0, decoder=None):
         else:
             t = torch.randn(shape, generator=g) / math.sqrt(math.prod(shape[1:]))
         tensors[name] = t.to(torch.float16)
-    return SamWeights(cfg, tensors, decoder=decoder)
+    return tensors
 
 
 # ---------------------------------------------------------------- the twin
@@ -406,12 +444,16 @@ def host_decoder(weights, dtype=torch.float32, device="cpu"):
     is SamModel.get_image_wide_positional_embeddings()."""
     from transformers.models.sam.modeling_sam import SamPromptEncoder, SamMaskDecoder, SamPositionalEmbedding
     hf = weights.config.to_hf()
-    prompt, decoder, shared = SamPromptEncoder(hf), SamMaskDecoder(hf.mask_decoder_config), SamPositionalEmbedding(hf.vision_config)
-    prompt.load_state_dict(weights.sub("prompt_encoder."), strict=True)
-    decoder.load_state_dict(weights.sub("mask_decoder."), strict=True)
-    shared.load_state_dict(weights.sub("shared_image_embedding."), strict=True)
-    prompt, decoder, shared = (m.to(device=device, dtype=dtype).eval() for m in (prompt, decoder, shared))
-    g = weights.config.grid
+    return load_decoder(weights, (SamPromptEncoder(hf), SamMaskDecoder(hf.mask_decoder_config), SamPositionalEmbedding(hf.vision_config)),
+                        weights.config.grid, dtype, device)
+
+
+def load_decoder(weights, modules, g, dtype, device):
+    """host_decoder's and host_decoder2's common part: modules = fresh (prompt encoder, mask decoder, shared positional
+    embedding) -> (prompt, decoder, wide [1,256,g,g]) holding the tensors of `weights`, in `dtype` on `device`, in eval mode."""
+    for m, prefix in zip(modules, ("prompt_encoder.", "mask_decoder.", "shared_image_embedding.")):
+        m.load_state_dict(weights.sub(prefix), strict=True)
+    prompt, decoder, shared = (m.to(device=device, dtype=dtype).eval() for m in modules)
     c = (torch.arange(g, device=device, dtype=dtype) + 0.5) / g      # get_image_wide_positional_embeddings
     with torch.no_grad():
         wide = shared(torch.stack([c[None, :].expand(g, g), c[:, None].expand(g, g)], -1)).permute(2, 0, 1)[None]
@@ -440,6 +482,16 @@ def decode_host(weights, emb, wide, points, dtype=torch.float32, device=None, mo
 
 
 # ---------------------------------------------------------------- the encoder
+def device_pixels(who, pixel_values, S):
+    """The input check of both encoders' encode(): -> f32 [3,S,S], contiguous, on the device it came on."""
+    if not isinstance(pixel_values, torch.Tensor) or not pixel_values.is_cuda:
+        raise _lib.GsrError(f"{who}: pixel_values must live on the device (no CPU path; see {who}_host)")
+    x = pixel_values.detach().reshape(-1, S, S) if pixel_values.numel() == 3 * S * S else pixel_values
+    if tuple(x.shape) != (3, S, S):
+        raise ValueError(f"{who}: expected [3,{S},{S}], got {list(pixel_values.shape)}")
+    return x.to(torch.float32).contiguous()
+
+
 class SamImageEncoder:
     """encode(pixel_values f32 [3,S,S] on the device) -> f32 [C,g,g], on the kernels."""
 
@@ -471,13 +523,8 @@ class SamImageEncoder:
 
     @torch.no_grad()
     def encode(self, pixel_values):
-        if not isinstance(pixel_values, torch.Tensor) or not pixel_values.is_cuda:
-            raise _lib.GsrError("sam: pixel_values must live on the device (no CPU path; see sam_host)")
-        S, cfg = self.config.image_size, self.config
-        x = pixel_values.detach().reshape(-1, S, S) if pixel_values.numel() == 3 * S * S else pixel_values
-        if tuple(x.shape) != (3, S, S):
-            raise ValueError(f"sam: expected [3,{S},{S}], got {list(pixel_values.shape)}")
-        x = x.to(torch.float32).contiguous()
+        cfg = self.config
+        x = device_pixels("sam", pixel_values, cfg.image_size)
         dev = x.device
         d = self._device(dev)
         out = torch.empty(cfg.output_channels, cfg.grid, cfg.grid, dtype=torch.float32, device=dev)
@@ -590,123 +637,158 @@ def select_host(low_res, iou, input_size, mask_size, pred_iou_thresh=0.86, stabi
 
 
 # ---------------------------------------------------------------- the generator
+def grid_positional(G, g):
+    """f32 [256,g,g]: get_image_wide_positional_embeddings in fp32 from the Gaussian matrix G f32 [2,128], on G's device (host_decoder's
+    wide without the batch axis)."""
+    c = (torch.arange(g, device=G.device, dtype=torch.float32) + 0.5) / g
+    xy = 2 * torch.stack([c[None, :].expand(g, g), c[:, None].expand(g, g)], -1) - 1
+    arg = 2 * np.pi * (xy @ G.to(torch.float32))
+    return torch.cat([torch.sin(arg), torch.cos(arg)], -1).permute(2, 0, 1).contiguous()
+
+
+def decode_chunk(workspace_bytes, g, P):
+    """(points per call, bytes of workspace per call) for P points at grid g: as many points as DECODER_WORKSPACE_BUDGET, read
+    now, holds (at least one, at most 65535); workspace_bytes(g, points) is the library's size function."""
+    one = workspace_bytes(g, 1)
+    per = max(1, workspace_bytes(g, 2) - one)
+    chunk = int(min(P, 65535, max(1, 1 + (DECODER_WORKSPACE_BUDGET - one) // per)))
+    while chunk > 1 and workspace_bytes(g, chunk) > DECODER_WORKSPACE_BUDGET:
+        chunk -= 1
+    return chunk, workspace_bytes(g, chunk)
+
+
 class SamMaskGenerator:
     """The reference's SamAutomaticMaskGenerator for one full-image crop.  host=True: the encoder through transformers'
-    SamVisionEncoder in fp32 and the selection through select_host, on the same device."""
+    SamVisionEncoder in fp32 and the selection through select_host, on the same device.
+    Every step lives here once.  What a model supplies (sam2.Sam2MaskGenerator does, and overrides nothing else) are the class
+    attributes below and the four methods marked "hook"."""
+    WHO = "sam"
+    ENCODER = SamImageEncoder                       # encode(pixel_values) on the kernels
+    preprocess = staticmethod(preprocess)
+    host_decoder = staticmethod(host_decoder)       # (weights, dtype, device) -> the torch modules and `wide`
+    DIRECT = False                                  # the selection resamples in one step (SM_SCORE / SM_EMIT's *_direct entries)
+    DECODE = ("gsr_sam_decode", "gsr_sam_decode_workspace_bytes")
+    HOST_HIP = (ValueError, "cannot be combined with it")
 
     def __init__(self, weights, points_per_side=32, points_per_batch=64, pred_iou_thresh=0.86, stability_score_thresh=0.92,
                  stability_score_offset=1.0, box_nms_thresh=0.7, host=False, device="cuda", decoder="torch"):
         if not weights.decoder:
-            raise ValueError("sam: the mask generator needs weights with the prompt encoder and the mask decoder")
+            raise ValueError(f"{self.WHO}: the mask generator needs weights with the prompt encoder and the mask decoder")
         if decoder not in ("torch", "hip"):
-            raise ValueError(f"sam: decoder {decoder!r} is not 'torch' or 'hip'")
+            raise ValueError(f"{self.WHO}: decoder {decoder!r} is not 'torch' or 'hip'")
         if host and decoder == "hip":
-            raise ValueError("sam: host=True runs the torch modules only; decoder='hip' cannot be combined with it")
+            raise self.HOST_HIP[0](f"{self.WHO}: host=True runs the torch modules only; decoder='hip' {self.HOST_HIP[1]}")
         self.weights, self.config, self.device, self.host = weights, weights.config, torch.device(device), bool(host)
         self.decoder = decoder
         self.points_per_side, self.points_per_batch = int(points_per_side), int(points_per_batch)
         self.pred_iou_thresh, self.stability_score_thresh = float(pred_iou_thresh), float(stability_score_thresh)
         self.stability_score_offset, self.box_nms_thresh = float(stability_score_offset), float(box_nms_thresh)
-        self.encoder = None if host else SamImageEncoder(weights)
-        self._host_encoder = self._modules = self._hip = None
+        self.encoder = None if host else self.ENCODER(weights)
+        self._host_model = self._modules = self._hip = None
         self.last_ms = {}
+
+    # -- hook: the encoder's twin in fp32 on pixel_values [3,S,S], as encoder.encode returns it
+    def _embed_host(self, x):
+        if self._host_model is None:
+            self._host_model = host_encoder(self.weights, torch.float32, self.device)
+        return sam_host(self.weights, x, torch.float32, self.device, self._host_model)
+
+    # -- hook: the torch decode call on what embed returned
+    def _decode_torch(self, emb, points):
+        return decode_host(self.weights, emb, self._decoder()[2], points, torch.float32, self.device, self._decoder(), self.points_per_batch)
+
+    # -- hook: the embedding as the maps of the decode call, in its argument order
+    def _maps(self, emb):
+        g = self.config.grid
+        return [emb.reshape(DECODER_CHANNELS, g, g)]
+
+    # -- hook: what decoder="hip" is not built for
+    def _check_hip(self):
+        if self.config.grid > 64:
+            raise NotImplementedError(f"sam: decoder='hip' is built for grids up to 64 (image_size <= 1024), not {self.config.grid}")
 
     # -- the torch modules of the decoder
     def _decoder(self):
         if self._modules is None:
-            self._modules = host_decoder(self.weights, torch.float32, self.device)
+            self._modules = self.host_decoder(self.weights, torch.float32, self.device)
         return self._modules
 
-    # -- the weight table of gsr_sam_decode and the positional embedding of the grid
+    # -- the weight table of the decode call and the positional embedding of the grid
     def _decoder_hip(self):
         if self._hip is None:
-            if self.config.grid > 64:
-                raise NotImplementedError(f"sam: decoder='hip' is built for grids up to 64 (image_size <= 1024), not {self.config.grid}")
-            w = SamWeights.__new__(SamWeights)
-            w.config, w.decoder = self.config, True
-            w.tensors = {k: t.to(self.device) for k, t in self.weights.tensors.items() if not k.startswith(VISION)}
-            tensors = w.decoder_table()
+            self._check_hip()
+            tensors = self.weights.copy(keep=lambda k: not k.startswith(VISION), device=self.device).decoder_table()
             table = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-            g = self.config.grid
-            G = tensors[0].to(torch.float32)
-            c = (torch.arange(g, device=self.device, dtype=torch.float32) + 0.5) / g
-            xy = 2 * torch.stack([c[None, :].expand(g, g), c[:, None].expand(g, g)], -1) - 1
-            arg = 2 * np.pi * (xy @ G)
-            wide = torch.cat([torch.sin(arg), torch.cos(arg)], -1).permute(2, 0, 1).contiguous()
-            self._hip = dict(tensors=tensors, table=table, n=len(tensors), wide=wide)
+            self._hip = dict(tensors=tensors, table=table, n=len(tensors), wide=grid_positional(tensors[0], self.config.image_size // PATCH))
         return self._hip
 
     @torch.no_grad()
     def embed(self, image):
-        """HxWx3 uint8 -> dict(emb f32 [1,C,g,g] on the device, input_size, mask_size)."""
-        x, input_size, mask_size = preprocess(image, self.config.image_size)
+        """HxWx3 uint8 -> dict(emb on the device, input_size, mask_size).  emb: f32 [1,C,g,g]; for SAM2 its three f32 maps."""
+        x, input_size, mask_size = self.preprocess(image, self.config.image_size)
         x = x.to(self.device)
-        if self.host:
-            if self._host_encoder is None:
-                self._host_encoder = host_encoder(self.weights, torch.float32, self.device)
-            emb = sam_host(self.weights, x, torch.float32, self.device, self._host_encoder)
-        else:
-            emb = self.encoder.encode(x)
-        return dict(emb=emb[None].to(torch.float32), input_size=input_size, mask_size=mask_size)
+        emb = self._embed_host(x) if self.host else self.encoder.encode(x)
+        emb = emb[None].to(torch.float32) if isinstance(emb, torch.Tensor) else [m.to(torch.float32) for m in emb]
+        return dict(emb=emb, input_size=input_size, mask_size=mask_size)
 
     @torch.no_grad()
     def decode(self, emb, points):
-        """emb [1,C,g,g], points f32 [P,2] (x, y) in the input frame -> (low_res f32 [P,3,L,L], iou f32 [P,3]).  decoder="torch":
-        transformers' modules in fp32, points_per_batch at a time; "hip": gsr_sam_decode, as many points per call as
-        DECODER_WORKSPACE_BUDGET bytes of workspace hold."""
+        """emb as embed returns it, points f32 [P,2] (x, y) in the input frame -> (low_res f32 [P,3,L,L], iou f32 [P,3]).
+        decoder="torch": transformers' modules in fp32, points_per_batch at a time; "hip": gsr_sam_decode (gsr_sam2_decode), as
+        many points per call as sam.DECODER_WORKSPACE_BUDGET bytes of workspace hold."""
         if self.decoder == "hip":
             return self._decode_hip(emb, points)
-        low, iou = decode_host(self.weights, emb, self._decoder()[2], points, torch.float32, self.device, self._decoder(),
-                               self.points_per_batch)
+        low, iou = self._decode_torch(emb, points)
         return low.to(torch.float32).contiguous(), iou.to(torch.float32).contiguous()
 
     def _decode_hip(self, emb, points):
-        if not emb.is_cuda:
-            raise _lib.GsrError("sam: decoder='hip' needs the embedding on the device (no CPU path; see decode_host)")
-        d, L, g, S = self._decoder_hip(), _lib.lib(), self.config.grid, self.config.image_size
-        dev = emb.device
-        emb = emb.reshape(DECODER_CHANNELS, g, g).to(torch.float32).contiguous()
+        maps = self._maps(emb)
+        if not all(m.is_cuda for m in maps):
+            raise _lib.GsrError(f"{self.WHO}: decoder='hip' needs the embedding on the device (no CPU path; see decode_host / decode_host2)")
+        d, L, S = self._decoder_hip(), _lib.lib(), self.config.image_size
+        g, dev = S // PATCH, maps[-1].device
+        maps = [m.to(torch.float32).contiguous() for m in maps]
         pts = points.to(device=dev, dtype=torch.float32).reshape(-1, 2).contiguous()
         P = pts.shape[0]
         low = torch.empty(P, 3, 4 * g, 4 * g, dtype=torch.float32, device=dev)
         iou = torch.empty(P, 3, dtype=torch.float32, device=dev)
         if P == 0:
             return low, iou
-        one = L.gsr_sam_decode_workspace_bytes(g, 1)
-        per = max(1, L.gsr_sam_decode_workspace_bytes(g, 2) - one)
-        chunk = int(min(P, 65535, max(1, 1 + (DECODER_WORKSPACE_BUDGET - one) // per)))
-        while chunk > 1 and L.gsr_sam_decode_workspace_bytes(g, chunk) > DECODER_WORKSPACE_BUDGET:
-            chunk -= 1
-        nbytes = L.gsr_sam_decode_workspace_bytes(g, chunk)
+        decode, workspace_bytes = (getattr(L, name) for name in self.DECODE)
+        chunk, nbytes = decode_chunk(workspace_bytes, g, P)
         ws = workspace(nbytes, dev)
         for k in range(0, P, chunk):
             n = min(chunk, P - k)
-            _lib.check(L.gsr_sam_decode(g, d["table"], d["n"], ptr(emb), ptr(d["wide"]), ptr(pts[k:k + n]), n, S, ptr(ws), nbytes,
-                                        ptr(low[k:k + n]), ptr(iou[k:k + n]), stream(dev)))
+            _lib.check(decode(g, d["table"], d["n"], *[ptr(m) for m in maps], ptr(d["wide"]), ptr(pts[k:k + n]), n, S, ptr(ws), nbytes,
+                              ptr(low[k:k + n]), ptr(iou[k:k + n]), stream(dev)))
         return low, iou
 
     @torch.no_grad()
     def select(self, low_res, iou, input_size, mask_size):
         """The reference's gates in its order: iou > pred_iou_thresh; inter / union >= stability_score_thresh (0 / 0 is
         rejected); SM_NMS; SM_EMIT.  Candidates are ordered point-major, then mask index.  One host synchronisation, for
-        the kept count.  -> dict(masks uint8 [m,oh,ow], index, area, boxes XYXY inclusive, predicted_iou, stability_score)."""
+        the kept count.  DIRECT (SAM2): the planes are resampled in ONE step from the L x L logits to mask_size (SAM2's
+        postprocess_masks) and input_size is not read.
+        -> dict(masks uint8 [m,oh,ow], index, area, boxes XYXY inclusive, predicted_iou, stability_score)."""
         args = (self.pred_iou_thresh, self.stability_score_thresh, self.stability_score_offset, self.box_nms_thresh)
         if self.host:
-            return select_host(low_res, iou, input_size, mask_size, *args)
+            return select_host(low_res, iou, input_size, mask_size, *args, direct=self.DIRECT)
         if not low_res.is_cuda:
-            raise _lib.GsrError("sam: select needs device tensors (no CPU path; see select_host)")
+            raise _lib.GsrError(f"{self.WHO}: select needs device tensors (no CPU path; see select_host)")
         dev, Lr = low_res.device, int(low_res.shape[-1])
         logits = low_res.reshape(-1, Lr, Lr).to(torch.float32).contiguous()
         scores = iou.reshape(-1).to(torch.float32).contiguous()
         n = logits.shape[0]
-        (ih, iw), (oh, ow) = input_size, mask_size
+        oh, ow = mask_size
         L = _lib.lib()
+        frame = (oh, ow) if self.DIRECT else (*input_size, oh, ow)
+        score, emit = (getattr(L, name + ("_direct" if self.DIRECT else "")) for name in ("gsr_sam_mask_score", "gsr_sam_mask_emit"))
         first = scores > self.pred_iou_thresh
         skip = (~first).to(torch.uint8)
         counts = torch.empty(n, 3, dtype=torch.int32, device=dev)
         boxes = torch.empty(n, 4, dtype=torch.float32, device=dev)
-        _lib.check(L.gsr_sam_mask_score(ptr(logits), n, Lr, ih, iw, oh, ow, MASK_THRESHOLD, self.stability_score_offset, ptr(skip),
-                                        ptr(counts), ptr(boxes), stream(dev)))
+        _lib.check(score(ptr(logits), n, Lr, *frame, MASK_THRESHOLD, self.stability_score_offset, ptr(skip), ptr(counts), ptr(boxes),
+                         stream(dev)))
         stab = counts[:, 1].to(torch.float32) / counts[:, 2].to(torch.float32)
         keep_in = (first & (stab >= self.stability_score_thresh)).to(torch.uint8)
         kept = torch.empty(n, dtype=torch.int32, device=dev)
@@ -718,7 +800,7 @@ class SamMaskGenerator:
         m = int(count.item())           # the one synchronisation
         index = kept[:m].contiguous()
         masks = torch.empty(m, oh, ow, dtype=torch.uint8, device=dev)
-        _lib.check(L.gsr_sam_mask_emit(ptr(logits), n, Lr, ih, iw, oh, ow, MASK_THRESHOLD, ptr(index), m, ptr(masks), stream(dev)))
+        _lib.check(emit(ptr(logits), n, Lr, *frame, MASK_THRESHOLD, ptr(index), m, ptr(masks), stream(dev)))
         idx = index.to(torch.int64)
         return dict(masks=masks, index=idx, area=counts[idx, 0].to(torch.int64), boxes=boxes[idx], predicted_iou=scores[idx],
                     stability_score=stab[idx], keep_in=keep_in.to(torch.bool), stability_all=stab)

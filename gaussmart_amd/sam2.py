@@ -25,12 +25,12 @@ What differs from the reference, on purpose:
     the IoU head.  Not built: the object-score output, boxes and mask prompts, several points per prompt, single-mask output
     with its dynamic stability selection.  host=True runs the torch modules only and refuses decoder="hip".
 `sam2_host`, `decode_host2` and `sam.select_host(direct=True)` are the torch twins (any device): they back `host=True` and the
-tests."""
+tests.  This module holds what is SAM2's alone (configuration, names, position table, transform, encoder, twins); the weights'
+validation and decoder table, the random recipe and every step of the generator are sam.py's, reached through `Sam2Weights`'
+and `Sam2MaskGenerator`'s class attributes and hooks."""
 import ctypes as C
 import json
-import math
 import os
-import re
 from dataclasses import dataclass
 
 import numpy as np
@@ -233,14 +233,6 @@ class Sam2Config:
         return cfg
 
 
-def _shapes(config):
-    """name -> shape of transformers' Sam2Model.state_dict() for this configuration (built on the meta device)."""
-    from transformers import Sam2Model
-    with torch.device("meta"):
-        sd = Sam2Model(config.to_hf()).state_dict()
-    return {k: tuple(v.shape) for k, v in sd.items()}
-
-
 def position_table(pos_embed, pos_embed_window, g):
     """HV_EMBED's table, fp16 [g,g,embed]: Sam2HieraDetModel._get_pos_embed in fp32, rounded once."""
     pe = F.interpolate(pos_embed.to(torch.float32), size=(g, g), mode="bicubic")
@@ -249,35 +241,15 @@ def position_table(pos_embed, pos_embed_window, g):
     return pe.permute(0, 2, 3, 1)[0].to(torch.float16).contiguous()
 
 
-class Sam2Weights:
+class Sam2Weights(S1.ModelWeights):
     """config + the tensors under Sam2Model.state_dict()'s names: what the kernels read (the vision encoder and the mask
     decoder's conv_s0 / conv_s1) in fp16; the prompt encoder, the rest of the mask decoder, no_memory_embedding and the
     shared positional matrix in fp32."""
+    WHO, MODEL, IGNORED, HALF = "sam2", "Sam2Model", IGNORED, CONV_S
+    DEC_HEAD, DEC_LAYER, DEC_FINAL, DEC_TAIL, POINT_ROWS = DEC_HEAD, DEC_LAYER, DEC_FINAL, (OBJ_TOKEN,), slice(1, 2)
 
     def __init__(self, config, tensors):
-        self.config, self.tensors = config.check(), {}
-        tensors = {k: v for k, v in dict(tensors).items() if not any(re.search(p, k) for p in IGNORED)}
-        for a, b in (TIED, TIED[::-1]):
-            if a not in tensors and b in tensors:
-                tensors[a] = tensors[b]
-        want = _shapes(config)
-        unknown = sorted(set(tensors) - set(want))
-        if unknown:
-            raise KeyError(f"sam2 weights: {len(unknown)} tensors have no place, e.g. {unknown[:3]}")
-        missing = sorted(set(want) - set(tensors))
-        if missing:
-            raise KeyError(f"sam2 weights: {len(missing)} tensors are not filled, e.g. {missing[:3]}")
-        for k, shape in want.items():
-            t = tensors[k].detach()
-            if tuple(t.shape) != shape:
-                raise ValueError(f"sam2 weights: {k} must be {list(shape)}, got {list(t.shape)}")
-            self.tensors[k] = t.to(torch.float16 if k.startswith(VISION) or k in CONV_S else torch.float32).contiguous()
-
-    def to(self, device):
-        w = Sam2Weights.__new__(Sam2Weights)
-        w.config = self.config
-        w.tensors = {k: t.to(device) for k, t in self.tensors.items()}
-        return w
+        super().__init__(config.check(), tensors)
 
     def table(self):
         """The tensors of gsr_sam2_encode's weight table, in its order (None: the projection of a block that starts no
@@ -298,35 +270,6 @@ class Sam2Weights:
         out.append(t[NO_MEMORY].to(torch.float32).reshape(-1).contiguous())
         assert len(out) == _lib.GSR_SAM2_W_BLOCK0 + _lib.GSR_SAM2_W_PER_BLOCK * cfg.total_blocks + _lib.GSR_SAM2_W_NECK
         return out
-
-    def decoder_table(self):
-        """The tensors of gsr_sam2_decode's weight table, in its order, on the tensors' device: fp16 copies (self.tensors keeps
-        its fp32 ones), except the positional matrix (fp32, as it is).  The two transposed convolutions [ci,co,2,2] are re-laid
-        as [(dy 2 + dx) co_n + co][ci] and their biases repeated per tap, as SamWeights.decoder_table does."""
-        t, md = self.tensors, "mask_decoder."
-        names = list(DEC_HEAD)
-        for l in range(S1.DEC_LAYERS):
-            names += [f"{md}transformer.layers.{l}.{k}" for k in DEC_LAYER]
-        names += [f"{md}transformer.{k}" for k in DEC_FINAL] + [md + k for k in S1.DEC_UP + S1.DEC_HYPER + S1.DEC_IOU] + [OBJ_TOKEN]
-        out = []
-        for k in names:
-            v = t[k]
-            if k == DEC_HEAD[0]:
-                out.append(v.to(torch.float32).contiguous())
-                continue
-            if k == POINT_EMBED:
-                v = v[1:2]
-            elif k.startswith(md + "upscale_conv") and k.endswith(".weight"):
-                v = v.permute(2, 3, 1, 0).reshape(4 * v.shape[1], v.shape[0])
-            elif k.startswith(md + "upscale_conv"):
-                v = v.repeat(4)
-            out.append(v.to(torch.float16).contiguous())
-        assert len(out) == _lib.GSR_SAM2D_W_COUNT
-        return out
-
-    def sub(self, prefix):
-        """The tensors under `prefix`, with it removed (a sub-module's state dict), in fp32."""
-        return {k[len(prefix):]: t.to(torch.float32) for k, t in self.tensors.items() if k.startswith(prefix)}
 
 
 def load_sam2_weights(path):
@@ -358,22 +301,7 @@ def random_sam2_weights(config=None, seed=0):
     tables, no_memory_embedding, the embeddings and the tokens N(0, 1), LayerNorm gains U(0.5, 1.5), biases N(0, 0.1^2),
     everything rounded to fp16.  (Default initialisation zeroes the position tables and no_memory_embedding.)"""
     cfg = config or Sam2Config()
-    g = torch.Generator().manual_seed(seed)
-    tensors = {}
-    for name, shape in _shapes(cfg).items():
-        if name == TIED[0]:
-            continue
-        if "pos_embed" in name or name.endswith("positional_embedding") or name == NO_MEMORY or len(shape) == 2 and shape[0] <= 8 and "embed" in name \
-                or name.endswith("_token.weight") or name.endswith("_tokens.weight"):
-            t = torch.randn(shape, generator=g)
-        elif "norm" in name and name.endswith(".weight"):
-            t = 0.5 + torch.rand(shape, generator=g)
-        elif name.endswith(".bias"):
-            t = 0.1 * torch.randn(shape, generator=g)
-        else:
-            t = torch.randn(shape, generator=g) / math.sqrt(math.prod(shape[1:]))
-        tensors[name] = t.to(torch.float16)
-    return Sam2Weights(cfg, tensors)
+    return Sam2Weights(cfg, S1.random_tensors(S1.model_shapes(cfg, Sam2Weights.MODEL), seed, unit=(NO_MEMORY,)))
 
 
 # ---------------------------------------------------------------- the twins
@@ -400,17 +328,8 @@ def host_decoder2(weights, dtype=torch.float32, device="cpu"):
     Sam2Model.get_image_wide_positional_embeddings()."""
     from transformers.models.sam2.modeling_sam2 import Sam2PromptEncoder, Sam2MaskDecoder, Sam2PositionalEmbedding
     hf = weights.config.to_hf()
-    prompt, decoder, shared = (Sam2PromptEncoder(hf.prompt_encoder_config), Sam2MaskDecoder(hf.mask_decoder_config),
-                               Sam2PositionalEmbedding(hf.prompt_encoder_config))
-    prompt.load_state_dict(weights.sub("prompt_encoder."), strict=True)
-    decoder.load_state_dict(weights.sub("mask_decoder."), strict=True)
-    shared.load_state_dict(weights.sub("shared_image_embedding."), strict=True)
-    prompt, decoder, shared = (m.to(device=device, dtype=dtype).eval() for m in (prompt, decoder, shared))
-    g = weights.config.image_size // 16
-    c = (torch.arange(g, device=device, dtype=dtype) + 0.5) / g
-    with torch.no_grad():
-        wide = shared(torch.stack([c[None, :].expand(g, g), c[:, None].expand(g, g)], -1)).permute(2, 0, 1)[None]
-    return prompt, decoder, wide
+    return S1.load_decoder(weights, (Sam2PromptEncoder(hf.prompt_encoder_config), Sam2MaskDecoder(hf.mask_decoder_config),
+                                     Sam2PositionalEmbedding(hf.prompt_encoder_config)), weights.config.image_size // S1.PATCH, dtype, device)
 
 
 @torch.no_grad()
@@ -459,13 +378,8 @@ class Sam2ImageEncoder:
 
     @torch.no_grad()
     def encode(self, pixel_values):
-        if not isinstance(pixel_values, torch.Tensor) or not pixel_values.is_cuda:
-            raise _lib.GsrError("sam2: pixel_values must live on the device (no CPU path; see sam2_host)")
-        S, cfg = self.config.image_size, self.config
-        x = pixel_values.detach().reshape(-1, S, S) if pixel_values.numel() == 3 * S * S else pixel_values
-        if tuple(x.shape) != (3, S, S):
-            raise ValueError(f"sam2: expected [3,{S},{S}], got {list(pixel_values.shape)}")
-        x = x.to(torch.float32).contiguous()
+        cfg = self.config
+        x = S1.device_pixels("sam2", pixel_values, cfg.image_size)
         dev = x.device
         d = self._device(dev)
         D, g = cfg.fpn_hidden_size, cfg.grids()
@@ -495,132 +409,30 @@ def preprocess2(image_u8, image_size=1024):
 
 # ---------------------------------------------------------------- the generator
 class Sam2MaskGenerator(S1.SamMaskGenerator):
-    """The reference's SAM2AutomaticMaskGenerator for one full-image crop, with SamMaskGenerator's interface.  host=True: the
-    encoder through transformers' Sam2Model in fp32 and the selection through sam.select_host(direct=True), on the same device.
-    decoder="hip": the prompt encoder and the mask decoder through gsr_sam2_decode instead of transformers' modules."""
+    """The reference's SAM2AutomaticMaskGenerator for one full-image crop: SamMaskGenerator with SAM2's encoder, transform, twins
+    and decode call.  host=True: the encoder through transformers' Sam2Model in fp32 and the selection through
+    sam.select_host(direct=True), on the same device.  decoder="hip": the prompt encoder and the mask decoder through
+    gsr_sam2_decode instead of transformers' modules.  emb is the list of the encoder's three maps throughout."""
+    WHO = "sam2"
+    ENCODER = Sam2ImageEncoder
+    preprocess = staticmethod(preprocess2)
+    host_decoder = staticmethod(host_decoder2)
+    DIRECT = True
+    DECODE = ("gsr_sam2_decode", "gsr_sam2_decode_workspace_bytes")
+    HOST_HIP = (NotImplementedError, "is not built for it")
 
-    def __init__(self, weights, points_per_side=32, points_per_batch=64, pred_iou_thresh=0.86, stability_score_thresh=0.92,
-                 stability_score_offset=1.0, box_nms_thresh=0.7, host=False, device="cuda", decoder="torch"):
-        if decoder not in ("torch", "hip"):
-            raise ValueError(f"sam2: decoder {decoder!r} is not 'torch' or 'hip'")
-        if host and decoder == "hip":
-            raise NotImplementedError("sam2: host=True runs the torch modules only; decoder='hip' is not built for it")
-        self.weights, self.config, self.device, self.host = weights, weights.config, torch.device(device), bool(host)
-        self.decoder = decoder
-        self.points_per_side, self.points_per_batch = int(points_per_side), int(points_per_batch)
-        self.pred_iou_thresh, self.stability_score_thresh = float(pred_iou_thresh), float(stability_score_thresh)
-        self.stability_score_offset, self.box_nms_thresh = float(stability_score_offset), float(box_nms_thresh)
-        self.encoder = None if host else Sam2ImageEncoder(weights)
-        self._host_model = self._modules = self._hip = None
-        self.last_ms = {}
+    def _embed_host(self, x):
+        if self._host_model is None:
+            self._host_model = host_model(self.weights, torch.float32, self.device)
+        return sam2_host(self.weights, x, torch.float32, self.device, self._host_model)
 
-    def _decoder(self):
-        if self._modules is None:
-            self._modules = host_decoder2(self.weights, torch.float32, self.device)
-        return self._modules
+    def _decode_torch(self, emb, points):
+        return decode_host2(self.weights, emb, points, torch.float32, self.device, self._decoder(), self.points_per_batch)
 
-    @torch.no_grad()
-    def embed(self, image):
-        """HxWx3 uint8 -> dict(emb: the three f32 maps on the device, input_size (S, S), mask_size)."""
-        x, input_size, mask_size = preprocess2(image, self.config.image_size)
-        x = x.to(self.device)
-        if self.host:
-            if self._host_model is None:
-                self._host_model = host_model(self.weights, torch.float32, self.device)
-            emb = sam2_host(self.weights, x, torch.float32, self.device, self._host_model)
-        else:
-            emb = self.encoder.encode(x)
-        return dict(emb=[m.to(torch.float32) for m in emb], input_size=input_size, mask_size=mask_size)
+    def _maps(self, emb):
+        g, D = self.config.image_size // S1.PATCH, self.config.fpn_hidden_size
+        return [m.reshape(ch, n, n) for m, ch, n in zip(emb, (D // 8, D // 4, D), (4 * g, 2 * g, g))]
 
-    # -- the weight table of gsr_sam2_decode and the positional embedding of the grid (host_decoder2's wide, in fp32)
-    def _decoder_hip(self):
-        if self._hip is None:
-            if self.config.fpn_hidden_size != S1.DECODER_CHANNELS:
-                raise NotImplementedError(f"sam2: decoder='hip' is built for {S1.DECODER_CHANNELS} channels, not {self.config.fpn_hidden_size}")
-            g = self.config.image_size // 16
-            w = Sam2Weights.__new__(Sam2Weights)
-            w.config = self.config
-            w.tensors = {k: t.to(self.device) for k, t in self.weights.tensors.items() if not k.startswith(VISION)}
-            tensors = w.decoder_table()
-            table = (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-            G = tensors[0]
-            c = (torch.arange(g, device=self.device, dtype=torch.float32) + 0.5) / g
-            xy = 2 * torch.stack([c[None, :].expand(g, g), c[:, None].expand(g, g)], -1) - 1
-            arg = 2 * np.pi * (xy @ G)
-            wide = torch.cat([torch.sin(arg), torch.cos(arg)], -1).permute(2, 0, 1).contiguous()
-            self._hip = dict(tensors=tensors, table=table, n=len(tensors), wide=wide)
-        return self._hip
-
-    def _decode_hip(self, emb, points):
-        if not all(m.is_cuda for m in emb):
-            raise _lib.GsrError("sam2: decoder='hip' needs the three maps on the device (no CPU path; see decode_host2)")
-        d, L, S = self._decoder_hip(), _lib.lib(), self.config.image_size
-        g, D = S // 16, self.config.fpn_hidden_size
-        dev = emb[2].device
-        s0, s1, top = (m.reshape(ch, n, n).to(torch.float32).contiguous() for m, ch, n in zip(emb, (D // 8, D // 4, D), (4 * g, 2 * g, g)))
-        pts = points.to(device=dev, dtype=torch.float32).reshape(-1, 2).contiguous()
-        P = pts.shape[0]
-        low = torch.empty(P, 3, 4 * g, 4 * g, dtype=torch.float32, device=dev)
-        iou = torch.empty(P, 3, dtype=torch.float32, device=dev)
-        if P == 0:
-            return low, iou
-        budget = S1.DECODER_WORKSPACE_BUDGET
-        one = L.gsr_sam2_decode_workspace_bytes(g, 1)
-        per = max(1, L.gsr_sam2_decode_workspace_bytes(g, 2) - one)
-        chunk = int(min(P, 65535, max(1, 1 + (budget - one) // per)))
-        while chunk > 1 and L.gsr_sam2_decode_workspace_bytes(g, chunk) > budget:
-            chunk -= 1
-        nbytes = L.gsr_sam2_decode_workspace_bytes(g, chunk)
-        ws = workspace(nbytes, dev)
-        for k in range(0, P, chunk):
-            n = min(chunk, P - k)
-            _lib.check(L.gsr_sam2_decode(g, d["table"], d["n"], ptr(s0), ptr(s1), ptr(top), ptr(d["wide"]), ptr(pts[k:k + n]), n, S,
-                                         ptr(ws), nbytes, ptr(low[k:k + n]), ptr(iou[k:k + n]), stream(dev)))
-        return low, iou
-
-    @torch.no_grad()
-    def decode(self, emb, points):
-        """emb: the three maps, points f32 [P,2] (x, y) in the S x S frame -> (low_res f32 [P,3,L,L], iou f32 [P,3]).
-        decoder="torch": transformers' modules in fp32, points_per_batch at a time; "hip": gsr_sam2_decode, as many points per
-        call as sam.DECODER_WORKSPACE_BUDGET bytes of workspace hold."""
-        if self.decoder == "hip":
-            return self._decode_hip(emb, points)
-        low, iou = decode_host2(self.weights, emb, points, torch.float32, self.device, self._decoder(), self.points_per_batch)
-        return low.to(torch.float32).contiguous(), iou.to(torch.float32).contiguous()
-
-    @torch.no_grad()
-    def select(self, low_res, iou, input_size, mask_size):
-        """SamMaskGenerator.select's gates in the same order, on planes resampled in ONE step from the L x L logits to
-        mask_size (SAM2's postprocess_masks); input_size is not read."""
-        args = (self.pred_iou_thresh, self.stability_score_thresh, self.stability_score_offset, self.box_nms_thresh)
-        if self.host:
-            return S1.select_host(low_res, iou, input_size, mask_size, *args, direct=True)
-        if not low_res.is_cuda:
-            raise _lib.GsrError("sam2: select needs device tensors (no CPU path; see sam.select_host(direct=True))")
-        dev, Lr = low_res.device, int(low_res.shape[-1])
-        logits = low_res.reshape(-1, Lr, Lr).to(torch.float32).contiguous()
-        scores = iou.reshape(-1).to(torch.float32).contiguous()
-        n = logits.shape[0]
-        oh, ow = mask_size
-        L = _lib.lib()
-        first = scores > self.pred_iou_thresh
-        skip = (~first).to(torch.uint8)
-        counts = torch.empty(n, 3, dtype=torch.int32, device=dev)
-        boxes = torch.empty(n, 4, dtype=torch.float32, device=dev)
-        _lib.check(L.gsr_sam_mask_score_direct(ptr(logits), n, Lr, oh, ow, S1.MASK_THRESHOLD, self.stability_score_offset, ptr(skip),
-                                               ptr(counts), ptr(boxes), stream(dev)))
-        stab = counts[:, 1].to(torch.float32) / counts[:, 2].to(torch.float32)
-        keep_in = (first & (stab >= self.stability_score_thresh)).to(torch.uint8)
-        kept = torch.empty(n, dtype=torch.int32, device=dev)
-        count = torch.zeros(1, dtype=torch.int32, device=dev)
-        nbytes = L.gsr_sam_nms_workspace_bytes(n)
-        ws = workspace(nbytes, dev)
-        _lib.check(L.gsr_sam_nms(ptr(boxes), ptr(scores), ptr(keep_in), n, self.box_nms_thresh, ptr(ws), nbytes, ptr(kept), ptr(count),
-                                 stream(dev)))
-        m = int(count.item())           # the one synchronisation
-        index = kept[:m].contiguous()
-        masks = torch.empty(m, oh, ow, dtype=torch.uint8, device=dev)
-        _lib.check(L.gsr_sam_mask_emit_direct(ptr(logits), n, Lr, oh, ow, S1.MASK_THRESHOLD, ptr(index), m, ptr(masks), stream(dev)))
-        idx = index.to(torch.int64)
-        return dict(masks=masks, index=idx, area=counts[idx, 0].to(torch.int64), boxes=boxes[idx], predicted_iou=scores[idx],
-                    stability_score=stab[idx], keep_in=keep_in.to(torch.bool), stability_all=stab)
+    def _check_hip(self):
+        if self.config.fpn_hidden_size != S1.DECODER_CHANNELS:
+            raise NotImplementedError(f"sam2: decoder='hip' is built for {S1.DECODER_CHANNELS} channels, not {self.config.fpn_hidden_size}")

@@ -71,22 +71,17 @@ def main(argv=None):
                 print(f"sam_cli: {args.sam_checkpoint} is not a {args.model_type} (embed {have.embed_dim}, blocks {tuple(have.blocks_per_stage)})",
                       file=sys.stderr)
                 raise SystemExit(2)
-        gen = S2.Sam2MaskGenerator(weights, points_per_side=args.points_per_side, pred_iou_thresh=args.pred_iou_thresh,
-                                   stability_score_thresh=args.stability_score_thresh, host=args.host, device=args.device,
-                                   decoder=args.decoder)
-        mask_size = lambda image: S2.preprocess2(image, weights.config.image_size)[2]
     else:
         weights = S.load_sam_weights(args.sam_checkpoint)
-        mask_size = lambda image: S.preprocess(image, weights.config.image_size)[2]
-    if args.model_type is not None and not args.sam2:
-        want, have = S.SamConfig.preset(args.model_type), weights.config
-        if (want.hidden_size, want.num_hidden_layers, want.num_attention_heads) != (have.hidden_size, have.num_hidden_layers, have.num_attention_heads):
-            print(f"sam_cli: {args.sam_checkpoint} is not a {args.model_type} (hidden {have.hidden_size}, {have.num_hidden_layers} layers)",
-                  file=sys.stderr)
-            raise SystemExit(2)
-    if not args.sam2:
-        gen = S.SamMaskGenerator(weights, points_per_side=args.points_per_side, pred_iou_thresh=args.pred_iou_thresh,
-                                 stability_score_thresh=args.stability_score_thresh, host=args.host, device=args.device, decoder=args.decoder)
+        if args.model_type is not None:
+            want, have = S.SamConfig.preset(args.model_type), weights.config
+            if (want.hidden_size, want.num_hidden_layers, want.num_attention_heads) != (have.hidden_size, have.num_hidden_layers, have.num_attention_heads):
+                print(f"sam_cli: {args.sam_checkpoint} is not a {args.model_type} (hidden {have.hidden_size}, {have.num_hidden_layers} layers)",
+                      file=sys.stderr)
+                raise SystemExit(2)
+    gen = (S2.Sam2MaskGenerator if args.sam2 else S.SamMaskGenerator)(
+        weights, points_per_side=args.points_per_side, pred_iou_thresh=args.pred_iou_thresh,
+        stability_score_thresh=args.stability_score_thresh, host=args.host, device=args.device, decoder=args.decoder)
     mask_dir = os.path.join(args.output_path, "segments", "masks")
     copy_dir = os.path.join(args.output_path, "segments", "images")
     os.makedirs(mask_dir, exist_ok=True)
@@ -99,7 +94,7 @@ def main(argv=None):
         if masks:
             S.save_segments_boxes(masks, out)
         else:               # the layout of an empty view: [0,h,w] masks
-            e = mask_size(image)
+            e = gen.preprocess(image, weights.config.image_size)[2]
             np.savez(out, masks=np.zeros((0, *e), bool), boxes=np.zeros((0, 4), np.int64), areas=np.zeros((0,), np.int64))
         shutil.copy(path, os.path.join(copy_dir, files[i]))
         print(json.dumps({"view": i, "image": files[i], "masks": len(masks), "host": bool(args.host), "decoder": args.decoder,

@@ -25,11 +25,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-import numpy as np                                           # noqa: E402
 import torch                                                 # noqa: E402
 
-from sam_bench import attempt, fmt, timed                    # noqa: E402
-from gaussmart_amd import _lib, sam as S1, sam2 as S2        # noqa: E402
+from sam_bench import attempt, decoder_whole, image, selection         # noqa: E402
+from gaussmart_amd import _lib, sam2 as S2                   # noqa: E402
 from gaussmart_amd._dev import ptr, stream, workspace       # noqa: E402
 
 
@@ -180,31 +179,19 @@ def attention(cfg, dev, args, out):
             ptr(qkv), g, w, stride, heads, hd, ptr(o), stream(dev))), dev, args, 4.0 * (g // stride) ** 2 * s * s * heads * hd)
 
 
-def selection(dev, args, out, points=1024):
-    gen = torch.Generator().manual_seed(2)
-    Lr, n = 256, points * 3
-    ys, xs = torch.meshgrid(torch.arange(Lr, dtype=torch.float32, device=dev), torch.arange(Lr, dtype=torch.float32, device=dev), indexing="ij")
-    rnd = lambda lo, hi: (lo + (hi - lo) * torch.rand(n, generator=gen)).to(dev)[:, None, None]
-    a, cy, cx, r = rnd(20.0, 120.0), rnd(0.0, 256.0), rnd(0.0, 256.0), rnd(16.0, 128.0)
-    low = torch.empty(n, Lr, Lr, device=dev)
-    for k in range(0, n, 256):
-        sl = slice(k, k + 256)
-        noise = torch.nn.functional.interpolate(torch.randn(a[sl].shape[0], 1, 32, 32, generator=gen).to(dev), (Lr, Lr), mode="bilinear")[:, 0]
-        low[sl] = a[sl] * (r[sl] - torch.sqrt((ys - cy[sl]) ** 2 + (xs - cx[sl]) ** 2)) / r[sl] + 0.7 * noise
-    low = low.reshape(points, 3, Lr, Lr)
-    iou = (0.5 + 0.5 * torch.rand(points, 3, generator=gen)).to(dev)
-    stub = S2.Sam2MaskGenerator.__new__(S2.Sam2MaskGenerator)
-    stub.host, stub.pred_iou_thresh, stub.stability_score_thresh, stub.stability_score_offset, stub.box_nms_thresh = False, 0.86, 0.92, 1.0, 0.7
-    out(f" one-step select: {points} points x 3 masks of {Lr}x{Lr} logits, thresholds 0.86 / 0.92 / 0.7:")
-    for size in ((768, 1024), (680, 1024)):
-        kept = None
-        try:
-            kept = len(stub.select(low, iou, None, size)["index"])
-        except Exception as e:
-            out(f"  select {size} failed: {type(e).__name__}: {e}")
-        attempt(out, f"kernels, masks {size[1]}x{size[0]} ({kept} kept)", lambda: stub.select(low, iou, None, size), dev, args)
-        attempt(out, f"select_host direct (torch fp32), masks {size[1]}x{size[0]}", lambda: S1.select_host(low, iou, None, size, direct=True), dev, args)
-        torch.cuda.empty_cache()
+class Sam2:
+    """sam_bench.Sam for SAM2: what the shared sections (selection, decoder_whole, image) read of the model."""
+    generator, twin, entry, modules = S2.Sam2MaskGenerator, "decode_host2", "gsr_sam2_decode", "Sam2PromptEncoder and Sam2MaskDecoder"
+    host_decoder, decode_host = staticmethod(S2.host_decoder2), staticmethod(S2.decode_host2)
+
+    @staticmethod
+    def embedding(g, dev):
+        gen = torch.Generator().manual_seed(5)
+        return [torch.randn(shape, generator=gen).to(torch.float16).float().to(dev) for shape in ((32, 4 * g, 4 * g), (64, 2 * g, 2 * g), (256, g, g))]
+
+    @staticmethod
+    def frame(size):
+        return size, size
 
 
 CHUNK = 256         # points per call of the stage entry points: about what sam.DECODER_WORKSPACE_BUDGET gives the whole decoder at g = 64
@@ -282,68 +269,6 @@ def decoder_stages(cfg, w, dev, args, out, points=1024):
             attempt(out, f"B upscale, round {rnd}", fn_b, dev, args, flop)
 
 
-def decoder_whole(cfg, w, dev, args, out, points=1024):
-    """The whole prompt encoder and mask decoder for `points` points: the kernels next to decode_host2 in fp32 (what the
-    generator runs by default) and in fp16 (the strongest stock alternative), on the same GPU in the same run."""
-    g, S = cfg.image_size // 16, cfg.image_size
-    gen5 = torch.Generator().manual_seed(5)
-    maps = [torch.randn(shape, generator=gen5).to(torch.float16).float().to(dev) for shape in ((32, 4 * g, 4 * g), (64, 2 * g, 2 * g), (256, g, g))]
-    pts = S1.point_grid(int(round(points ** 0.5)), (S, S))
-    out(f" whole decoder, g = {g}, {len(pts)} points (decoder='hip' chunks them by {S1.DECODER_WORKSPACE_BUDGET >> 20} MiB of workspace; "
-        f"decode_host2 takes 64 at a time):")
-    gen = S2.Sam2MaskGenerator(w, device=dev, decoder="hip")
-    t = {}
-    try:
-        with torch.no_grad():
-            t["hip"] = timed(lambda: gen.decode(maps, pts), dev, args.warmup, args.repeats)
-        out(fmt("kernels (gsr_sam2_decode)", t["hip"]))
-        ours = gen.decode(maps, pts)
-    except Exception as e:
-        out(f"  kernels (gsr_sam2_decode) failed: {type(e).__name__}: {e}")
-        ours = None
-    for dtype, label in ((torch.float32, "fp32 (the generator's default)"), (torch.float16, "fp16")):
-        try:
-            modules = S2.host_decoder2(w, dtype, dev)
-            with torch.no_grad():
-                t[label[:4]] = timed(lambda: S2.decode_host2(w, maps, pts, dtype, dev, modules), dev, args.warmup, args.repeats)
-            out(fmt(f"decode_host2 {label}", t[label[:4]]))
-            if ours is not None:
-                lo, io = S2.decode_host2(w, maps, pts, dtype, dev, modules)
-                out(f"  max |kernels - decode_host2 {label[:4]}|: masks {float((lo.float() - ours[0]).abs().max()):.3e}, "
-                    f"iou {float((io.float() - ours[1]).abs().max()):.3e}")
-            del modules
-        except Exception as e:
-            out(f"  decode_host2 {label} failed: {type(e).__name__}: {e}")
-        torch.cuda.empty_cache()
-    if "hip" in t and "fp16" in t:
-        margin = t["fp16"][0] - t["hip"][0]
-        spread = max(t["hip"][2] - t["hip"][1], t["fp16"][2] - t["fp16"][1])
-        verdict = "below" if margin > spread else "NOT below"
-        out(f"  kernels {verdict} decode_host2 fp16: margin {margin:.3f} ms against a spread of {spread:.3f} ms (the larger min..max)")
-    if "hip" in t and "fp32" in t:
-        out(f"  kernels {'below' if t['hip'][0] < t['fp32'][0] else 'NOT below'} decode_host2 fp32: {t['fp32'][0] / t['hip'][0]:.2f} x")
-
-
-def image(cfg, w, dev, args, out, decoder="torch"):
-    rng = np.random.default_rng(3)
-    img = rng.integers(0, 255, (768, 1024, 3), dtype=np.uint8)
-    gen = S2.Sam2MaskGenerator(w, points_per_side=args.points_per_side, device=dev, decoder=decoder)
-    rows = []
-    for _ in range(args.warmup + 3):
-        gen.generate_device(img)
-        rows.append(dict(gen.last_ms))
-    last = rows[-1]
-    total = sum(last.values())
-    out(f" one 1024x768 image, {args.points_per_side ** 2} points, decoder={decoder!r} (host preprocessing inside embed; the last of "
-        f"{len(rows)} runs):")
-    for k in ("embed", "decode", "select"):
-        out(f"  {k:<52s} {last[k]:9.3f} ms  ({100 * last[k] / total:.1f} % of the image)")
-    if decoder == "torch":
-        out("  decode is transformers' Sam2PromptEncoder and Sam2MaskDecoder in fp32 torch, as they are")
-    else:
-        out("  decode is gsr_sam2_decode: the kernels of csrc/sam_decoder.hip")
-
-
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sam2_bench.txt"))
@@ -372,11 +297,11 @@ def main(argv=None):
         f"weights) on {torch.cuda.get_device_name(0)}; torch {torch.__version__}, transformers {transformers.__version__}")
     out(f"median of {args.repeats} timed calls after {args.warmup} warm-up calls, (min .. max); TFLOP/s = operations counted from the shapes / median")
     for name, section in (("encoder", lambda: encoder(cfg, w, dev, args, out)), ("attention", lambda: attention(cfg, dev, args, out)),
-                          ("selection", lambda: selection(dev, args, out)),
+                          ("selection", lambda: selection(dev, args, out, model=Sam2)),
                           ("decoder stages", lambda: decoder_stages(cfg, w, dev, args, out)),
-                          ("decoder", lambda: decoder_whole(cfg, w, dev, args, out)),
-                          ("image (torch)", lambda: image(cfg, w, dev, args, out, "torch")),
-                          ("image (hip)", lambda: image(cfg, w, dev, args, out, "hip"))):
+                          ("decoder", lambda: decoder_whole(cfg, w, dev, args, out, model=Sam2)),
+                          ("image (torch)", lambda: image(cfg, w, dev, args, out, "torch", Sam2)),
+                          ("image (hip)", lambda: image(cfg, w, dev, args, out, "hip", Sam2))):
         try:
             section()
         except Exception as e:

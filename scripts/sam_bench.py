@@ -152,14 +152,33 @@ def whole(cfg, w, dev, args, out):
         torch.cuda.empty_cache()
 
 
-def selection(dev, args, out, points=1024):
+class Sam:
+    """What selection, decoder_whole and image read of a model (scripts/sam2_bench.py passes its own)."""
+    generator, twin, entry, modules = S.SamMaskGenerator, "decode_host", "gsr_sam_decode", "prompt encoder and mask decoder"
+    host_decoder = staticmethod(S.host_decoder)
+
+    @staticmethod
+    def embedding(g, dev):
+        return torch.randn(1, 256, g, g, generator=torch.Generator().manual_seed(5)).to(torch.float16).float().to(dev)
+
+    @staticmethod
+    def frame(size):
+        return size - 8, size
+
+    @staticmethod
+    def decode_host(w, emb, pts, dtype, dev, modules):
+        return S.decode_host(w, emb, None, pts, dtype, dev, modules)
+
+
+def selection(dev, args, out, points=1024, model=Sam):
     # cones a (r - d) / r plus smooth noise: a in [20, 120] puts about half of them above the stability threshold (the
     # score of a clean cone is ((1 - 1/a) / (1 + 1/a))^2), and predicted ious uniform in [0.5, 1] let 28 % through the first gate
+    direct = model.generator.DIRECT          # SAM2: one resampling to the mask's size, input_size is not read
     gen = torch.Generator().manual_seed(2)
     Lr, n = 256, points * 3
     ys, xs = torch.meshgrid(torch.arange(Lr, dtype=torch.float32, device=dev), torch.arange(Lr, dtype=torch.float32, device=dev), indexing="ij")
     rnd = lambda lo, hi: (lo + (hi - lo) * torch.rand(n, generator=gen)).to(dev)[:, None, None]
-    a, cy, cx, r = rnd(20.0, 120.0), rnd(0.0, 170.0), rnd(0.0, 256.0), rnd(16.0, 128.0)
+    a, cy, cx, r = rnd(20.0, 120.0), rnd(0.0, 256.0 if direct else 170.0), rnd(0.0, 256.0), rnd(16.0, 128.0)
     low = torch.empty(n, Lr, Lr, device=dev)
     for k in range(0, n, 256):
         sl = slice(k, k + 256)
@@ -167,17 +186,19 @@ def selection(dev, args, out, points=1024):
         low[sl] = a[sl] * (r[sl] - torch.sqrt((ys - cy[sl]) ** 2 + (xs - cx[sl]) ** 2)) / r[sl] + 0.7 * noise
     low = low.reshape(points, 3, Lr, Lr)
     iou = (0.5 + 0.5 * torch.rand(points, 3, generator=gen)).to(dev)
-    stub = S.SamMaskGenerator.__new__(S.SamMaskGenerator)
+    stub = model.generator.__new__(model.generator)
     stub.host, stub.pred_iou_thresh, stub.stability_score_thresh, stub.stability_score_offset, stub.box_nms_thresh = False, 0.86, 0.92, 1.0, 0.7
-    out(f" select: {points} points x 3 masks of {Lr}x{Lr} logits ({low.numel() * 4 / 1e6:.0f} MB held), thresholds 0.86 / 0.92 / 0.7:")
+    out(f" {'one-step ' if direct else ''}select: {points} points x 3 masks of {Lr}x{Lr} logits"
+        f"{'' if direct else f' ({low.numel() * 4 / 1e6:.0f} MB held)'}, thresholds 0.86 / 0.92 / 0.7:")
     for size in ((768, 1024), (680, 1024)):
-        kept = None
+        kept, frame = None, None if direct else size
         try:
-            kept = len(stub.select(low, iou, size, size)["index"])
+            kept = len(stub.select(low, iou, frame, size)["index"])
         except Exception as e:
             out(f"  select {size} failed: {type(e).__name__}: {e}")
-        attempt(out, f"kernels, masks {size[1]}x{size[0]} ({kept} kept)", lambda: stub.select(low, iou, size, size), dev, args)
-        attempt(out, f"select_host (torch fp32), masks {size[1]}x{size[0]}", lambda: S.select_host(low, iou, size, size), dev, args)
+        attempt(out, f"kernels, masks {size[1]}x{size[0]} ({kept} kept)", lambda: stub.select(low, iou, frame, size), dev, args)
+        attempt(out, f"select_host{' direct' if direct else ''} (torch fp32), masks {size[1]}x{size[0]}",
+                lambda: S.select_host(low, iou, frame, size, direct=direct), dev, args)
         torch.cuda.empty_cache()
 
 
@@ -222,51 +243,51 @@ def decoder_stages(cfg, w, dev, args, out, P=256):
         2.0 * P * T * (256 * 256 + 4 * 64 * 128 + 16 * 32 * 3))
 
 
-def decoder_whole(cfg, w, dev, args, out, points=1024):
-    """The whole prompt encoder and mask decoder for `points` points: the kernels next to decode_host in fp32 (what the
-    generator runs by default) and in fp16 (the strongest stock alternative), on the same GPU in the same run."""
-    g = cfg.grid
-    emb = torch.randn(1, 256, g, g, generator=torch.Generator().manual_seed(5)).to(torch.float16).float().to(dev)
-    pts = S.point_grid(int(round(points ** 0.5)), (cfg.image_size - 8, cfg.image_size))
+def decoder_whole(cfg, w, dev, args, out, points=1024, model=Sam):
+    """The whole prompt encoder and mask decoder for `points` points: the kernels next to the model's decode_host in fp32 (what
+    the generator runs by default) and in fp16 (the strongest stock alternative), on the same GPU in the same run."""
+    g, twin, entry = cfg.image_size // 16, model.twin, model.entry
+    emb = model.embedding(g, dev)
+    pts = S.point_grid(int(round(points ** 0.5)), model.frame(cfg.image_size))
     out(f" whole decoder, g = {g}, {len(pts)} points (decoder='hip' chunks them by {S.DECODER_WORKSPACE_BUDGET >> 20} MiB of workspace; "
-        f"decode_host takes 64 at a time):")
-    gen = S.SamMaskGenerator(w, device=dev, decoder="hip")
+        f"{twin} takes 64 at a time):")
+    gen = model.generator(w, device=dev, decoder="hip")
     t = {}
     try:
         with torch.no_grad():
             t["hip"] = timed(lambda: gen.decode(emb, pts), dev, args.warmup, args.repeats)
-        out(fmt("kernels (gsr_sam_decode)", t["hip"]))
+        out(fmt(f"kernels ({entry})", t["hip"]))
         ours = gen.decode(emb, pts)
     except Exception as e:
-        out(f"  kernels (gsr_sam_decode) failed: {type(e).__name__}: {e}")
+        out(f"  kernels ({entry}) failed: {type(e).__name__}: {e}")
         ours = None
     for dtype, label in ((torch.float32, "fp32 (the generator's default)"), (torch.float16, "fp16")):
         try:
-            modules = S.host_decoder(w, dtype, dev)
+            modules = model.host_decoder(w, dtype, dev)
             with torch.no_grad():
-                t[label[:4]] = timed(lambda: S.decode_host(w, emb, None, pts, dtype, dev, modules), dev, args.warmup, args.repeats)
-            out(fmt(f"decode_host {label}", t[label[:4]]))
+                t[label[:4]] = timed(lambda: model.decode_host(w, emb, pts, dtype, dev, modules), dev, args.warmup, args.repeats)
+            out(fmt(f"{twin} {label}", t[label[:4]]))
             if ours is not None:
-                lo, io = S.decode_host(w, emb, None, pts, dtype, dev, modules)
-                out(f"  max |kernels - decode_host {label[:4]}|: masks {float((lo.float() - ours[0]).abs().max()):.3e}, "
+                lo, io = model.decode_host(w, emb, pts, dtype, dev, modules)
+                out(f"  max |kernels - {twin} {label[:4]}|: masks {float((lo.float() - ours[0]).abs().max()):.3e}, "
                     f"iou {float((io.float() - ours[1]).abs().max()):.3e}")
             del modules
         except Exception as e:
-            out(f"  decode_host {label} failed: {type(e).__name__}: {e}")
+            out(f"  {twin} {label} failed: {type(e).__name__}: {e}")
         torch.cuda.empty_cache()
     if "hip" in t and "fp16" in t:
         margin = t["fp16"][0] - t["hip"][0]
         spread = max(t["hip"][2] - t["hip"][1], t["fp16"][2] - t["fp16"][1])
         verdict = "below" if margin > spread else "NOT below"
-        out(f"  kernels {verdict} decode_host fp16: margin {margin:.3f} ms against a spread of {spread:.3f} ms (the larger min..max)")
+        out(f"  kernels {verdict} {twin} fp16: margin {margin:.3f} ms against a spread of {spread:.3f} ms (the larger min..max)")
     if "hip" in t and "fp32" in t:
-        out(f"  kernels {'below' if t['hip'][0] < t['fp32'][0] else 'NOT below'} decode_host fp32: {t['fp32'][0] / t['hip'][0]:.2f} x")
+        out(f"  kernels {'below' if t['hip'][0] < t['fp32'][0] else 'NOT below'} {twin} fp32: {t['fp32'][0] / t['hip'][0]:.2f} x")
 
 
-def image(cfg, w, dev, args, out, decoder="torch"):
+def image(cfg, w, dev, args, out, decoder="torch", model=Sam):
     rng = np.random.default_rng(3)
     img = rng.integers(0, 255, (768, 1024, 3), dtype=np.uint8)
-    gen = S.SamMaskGenerator(w, points_per_side=args.points_per_side, device=dev, decoder=decoder)
+    gen = model.generator(w, points_per_side=args.points_per_side, device=dev, decoder=decoder)
     rows = []
     for _ in range(args.warmup + 3):
         gen.generate_device(img)
@@ -277,9 +298,9 @@ def image(cfg, w, dev, args, out, decoder="torch"):
     for k in ("embed", "decode", "select"):
         out(f"  {k:<52s} {last[k]:9.3f} ms  ({100 * last[k] / total:.1f} % of the image)")
     if decoder == "torch":
-        out("  decode is transformers' prompt encoder and mask decoder in fp32 torch, as they are")
+        out(f"  decode is transformers' {model.modules} in fp32 torch, as they are")
     else:
-        out("  decode is gsr_sam_decode: the kernels of csrc/sam_decoder.hip")
+        out(f"  decode is {model.entry}: the kernels of csrc/sam_decoder.hip")
 
 
 def main(argv=None):

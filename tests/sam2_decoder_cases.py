@@ -49,12 +49,7 @@ def points(name):
     return S1.point_grid(side, (cfg.image_size, cfg.image_size))[:n].contiguous()
 
 
-def _without(w, key):
-    out = S2.Sam2Weights.__new__(S2.Sam2Weights)
-    out.config = w.config
-    out.tensors = dict(w.tensors)
-    out.tensors[key] = torch.zeros_like(w.tensors[key])
-    return out
+_without = DC._without
 
 
 @torch.no_grad()
@@ -132,59 +127,9 @@ def bars_line(name, b):
             f"moved by {moves}, neighbours {b['neighbours'] / b['bar_mask']:.0f}x")
 
 
-# ---------------------------------------------------------------- fp64 restatements of the stage rules, any number of tokens
-def t2i64(q, kx, kpe, v, shared, scale=0.25):
-    """SD_T2I's attention in fp64 from the inputs as given -> (out [P,n,128], bar).  q f32 [P,n,128]; kx, v fp16 [T,128] or
-    [P,T,128]; kpe f32 [T,128] or None.  sam_decoder_cases.t2i64 for n tokens."""
-    P, n = q.shape[:2]
-    k = kx.double() + (0 if kpe is None else kpe.double())
-    v = v.double()
-    if shared:
-        k, v = k[None].expand(P, -1, -1), v[None].expand(P, -1, -1)
-    T = k.shape[1]
-    qh = q.double().reshape(P, n, 8, 16).permute(0, 2, 1, 3)                # [P,8,n,16]
-    kh, vh = (x.reshape(P, T, 8, 16).permute(0, 2, 1, 3) for x in (k, v))   # [P,8,T,16]
-    s = (qh @ kh.transpose(-1, -2)) * scale
-    p = torch.softmax(s, -1)
-    o = p @ vh
-    mag = (qh.abs() @ kh.abs().transpose(-1, -2)) * scale
-    es = (16 + 2) * U32 * mag + 2 * U32 * s.abs()       # the key's addition, the chain of 16, the scale
-    spread = (s.max(-1, keepdim=True).values - s).max(-1, keepdim=True).values
-    delta = 2 * es.max(-1, keepdim=True).values + 4 * U32 * (1 + spread)    # expf: 2 ulp, and its argument's rounding
-    A = p @ vh.abs()
-    e = (2 * delta + 2 * (T // 256 + 20) * U32) * A     # numerator and l: T / 256 additions per thread, 6 + 3 in the tree, the quotient
-    bar = e + round16(o, e)
-    back = lambda x: x.permute(0, 2, 1, 3).reshape(P, n, 128)
-    return back(o), back(bar)
-
-
-def i2t64(qx, qpe, k, v, x, shared, ow, ob, lw, lb, norm=True, eps=1e-5):
-    """SD_I2T in fp64 with layer_norm4's eps -> (stream [P,T,256], bar).  k, v f32 [P,n,128].  norm=False: layer_norm4 left out
-    (the wrong reading).  sam_decoder_cases.i2t64 for n tokens."""
-    P, n = k.shape[:2]
-    q = qx.double() + qpe.double()
-    x = x.double()
-    if shared:
-        q, x = q[None].expand(P, -1, -1), x[None].expand(P, -1, -1)
-    T = q.shape[1]
-    qh = q.reshape(P, T, 8, 16).permute(0, 2, 1, 3)                          # [P,8,T,16]
-    kh, vh = (t.double().reshape(P, n, 8, 16).permute(0, 2, 1, 3) for t in (k, v))
-    s = (qh @ kh.transpose(-1, -2)) * 0.25
-    p = torch.softmax(s, -1)
-    ctx = (p @ vh).permute(0, 2, 1, 3).reshape(P, T, 128)
-    mag = (qh.abs() @ kh.abs().transpose(-1, -2)) * 0.25
-    delta = 2 * ((18 * U32 * mag + 2 * U32 * s.abs()).max(-1, keepdim=True).values) + 8 * U32
-    e_ctx = ((2 * delta + 20 * U32) * (p @ vh.abs())).permute(0, 2, 1, 3).reshape(P, T, 128)
-    e_ctx = e_ctx + round16(ctx, e_ctx)                                     # ctx is ROUNDED TO fp16
-    W = ow.double()
-    a = ctx @ W.T + ob.double()
-    e_a = e_ctx @ W.abs().T + (128 + 2) * U32 * (ctx.abs() @ W.abs().T + ob.double().abs())
-    y = x + a
-    e_y = e_a + U32 * y.abs()
-    if not norm:
-        return y, e_y + round16(y, e_y)
-    out, e = DC._ln64(y, e_y, lw.double(), lb.double(), eps)
-    return out, e + round16(out, e)
+# ---------------------------------------------------------------- fp64 restatements of the stage rules: SAM's, for eight tokens
+t2i64 = DC.t2i64
+i2t64 = functools.partial(DC.i2t64, eps=1e-5)       # layer_norm4's eps in SAM2; a call's own eps= still decides
 
 
 def up64(x, g, c1w, c1b, lw, lb, c2w, c2b, hyper, s0, s1, s1_after_norm=False, s0_after_gelu=False, swap0=False, swap1=False):

@@ -41,11 +41,7 @@ def points(name):
 
 
 def _without(w, key):
-    out = S.SamWeights.__new__(S.SamWeights)
-    out.config, out.decoder = w.config, w.decoder
-    out.tensors = dict(w.tensors)
-    out.tensors[key] = torch.zeros_like(w.tensors[key])
-    return out
+    return w.copy(replace={key: torch.zeros_like(w.tensors[key])})
 
 
 @functools.lru_cache(maxsize=None)
@@ -139,15 +135,15 @@ def prompt64(pts, S_, G, point1, nap, padding_as_point=False):
 
 
 def t2i64(q, kx, kpe, v, shared, scale=0.25):
-    """SD_T2I's attention in fp64 from the inputs as given -> (out [P,7,128], bar).  q f32 [P,7,128]; kx, v fp16 [T,128] or
-    [P,T,128]; kpe f32 [T,128] or None."""
-    P = q.shape[0]
+    """SD_T2I's attention in fp64 from the inputs as given -> (out [P,n,128], bar).  q f32 [P,n,128], n tokens per point (7
+    for SAM, 8 for SAM2); kx, v fp16 [T,128] or [P,T,128]; kpe f32 [T,128] or None."""
+    P, n = q.shape[:2]
     k = kx.double() + (0 if kpe is None else kpe.double())
     v = v.double()
     if shared:
         k, v = k[None].expand(P, -1, -1), v[None].expand(P, -1, -1)
     T = k.shape[1]
-    qh = q.double().reshape(P, 7, 8, 16).permute(0, 2, 1, 3)                # [P,8,7,16]
+    qh = q.double().reshape(P, n, 8, 16).permute(0, 2, 1, 3)                # [P,8,n,16]
     kh, vh = (x.reshape(P, T, 8, 16).permute(0, 2, 1, 3) for x in (k, v))   # [P,8,T,16]
     dots = qh @ kh.transpose(-1, -2)
     s = dots * scale
@@ -160,7 +156,7 @@ def t2i64(q, kx, kpe, v, shared, scale=0.25):
     A = p @ vh.abs()
     e = (2 * delta + 2 * (T // 256 + 20) * U32) * A     # numerator and l: T / 256 additions per thread, 6 + 3 in the tree, the quotient
     bar = e + round16(o, e)
-    back = lambda x: x.permute(0, 2, 1, 3).reshape(P, 7, 128)
+    back = lambda x: x.permute(0, 2, 1, 3).reshape(P, n, 128)
     return back(o), back(bar)
 
 
@@ -179,15 +175,16 @@ def _ln64(y, ey, gamma, beta, eps):
 
 
 def i2t64(qx, qpe, k, v, x, shared, ow, ob, lw, lb, norm=True, eps=1e-6):
-    """SD_I2T in fp64 -> (stream [P,T,256], bar).  norm=False: layer_norm4 left out (the wrong reading)."""
-    P = k.shape[0]
+    """SD_I2T in fp64 -> (stream [P,T,256], bar).  k, v f32 [P,n,128], n tokens per point; eps: layer_norm4's (SAM2's is 1e-5).
+    norm=False: layer_norm4 left out (the wrong reading)."""
+    P, n = k.shape[:2]
     q = qx.double() + qpe.double()
     x = x.double()
     if shared:
         q, x = q[None].expand(P, -1, -1), x[None].expand(P, -1, -1)
     T = q.shape[1]
     qh = q.reshape(P, T, 8, 16).permute(0, 2, 1, 3)                          # [P,8,T,16]
-    kh, vh = (t.double().reshape(P, 7, 8, 16).permute(0, 2, 1, 3) for t in (k, v))
+    kh, vh = (t.double().reshape(P, n, 8, 16).permute(0, 2, 1, 3) for t in (k, v))
     s = (qh @ kh.transpose(-1, -2)) * 0.25
     p = torch.softmax(s, -1)
     ctx = (p @ vh).permute(0, 2, 1, 3).reshape(P, T, 128)
