@@ -28,6 +28,7 @@ GSR_SAMD_W_LAYER0, GSR_SAMD_W_PER_LAYER, GSR_SAMD_W_FINAL, GSR_SAMD_W_UP, GSR_SA
 # include/gsr.h: the weight table of gsr_sam2_decode is gsr_sam_decode's under SAM2's names plus the object-score token
 GSR_SAMD_W_POINT1 = 1
 GSR_SAM2D_W_OBJ_TOKEN, GSR_SAM2D_W_COUNT = 118, 119
+GSR_CK_KMAX, GSR_CK_CHUNK, GSR_CK_MAX_CAMERAS = 16, 64, 4096     # include/gsr.h: CK_LLOYD (gaussmart_amd/camera_select.py)
 
 GSR_BUF_GEOM, GSR_BUF_BINNING, GSR_BUF_IMAGE, GSR_BUF_SCRATCH, GSR_BUF_SCRATCH2 = range(5)
 GSR_BUF_SYNC_SH = 100     # not a buffer: "the SH colour pass is about to be enqueued" (GSR_FLAG_DEFER_COLOR)
@@ -416,7 +417,9 @@ def lib():
                 ("gsr_sam2_dec_num_weights", C.c_int32, []),
                 ("gsr_sam2_decode_workspace_bytes", sz, [C.c_int32] * 2),
                 ("gsr_sam2_decode", C.c_int32, [C.c_int32, C.POINTER(vp), C.c_int32, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, sz, vp, vp,
-                                                vp])):
+                                                vp]),
+                ("gsr_cam_lloyd_workspace_bytes", sz, [C.c_int32] * 2),
+                ("gsr_cam_lloyd", C.c_int32, [vp, C.c_int32, vp, vp, C.c_int32, f64, C.c_int32] + [vp] * 6 + [sz, vp])):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
         L.gsr_profile_enable.restype = None
         L.gsr_profile_enable.argtypes = [C.c_int32]

@@ -825,6 +825,15 @@ class SamMaskGenerator:
         """uint8 [m,oh,ow] on the device, in NMS order: index k is segment id k in segment_init.label_points."""
         return self._run(image)[2]["masks"]
 
+    def generate_segments(self, image):
+        """(generate_device's masks, still on the device; what save_segments_boxes stores for generate's list: dict(masks bool
+        [m,oh,ow], boxes XYXY = [x, y, x + w, y + h] i64 [m,4], areas i64 [m]) on the host) from ONE run and one copy of the masks:
+        gaussmart_amd.identify_cli labels the cloud from the first and writes segments_NNN.npz from the second."""
+        sel = self._run(image)[2]
+        host = dict(masks=sel["masks"].cpu().numpy().astype(bool), boxes=sel["boxes"].cpu().numpy().astype(np.int64).reshape(-1, 4),
+                    areas=sel["area"].cpu().numpy().astype(np.int64).reshape(-1))
+        return sel["masks"], host
+
     def generate(self, image):
         """The reference's list of dicts, in NMS order."""
         e, points, sel = self._run(image)

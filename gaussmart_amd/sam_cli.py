@@ -18,8 +18,10 @@ the kernels of csrc/sam2.hip, the same files and JSON lines.  Its --sam_checkpoi
 Sam2Model names (gaussmart_amd.sam2.load_sam2_weights).  --decoder hip runs SAM2's prompt encoder and mask decoder on the same
 kernels of csrc/sam_decoder.hip (eight tokens per point, the two high-resolution skips, a sigmoid on the IoU head); with --host
 it is refused, since --host runs the torch modules only.
-Not built: crop layers, min_mask_region_area, the camera clustering that picks the views (step 1), and for SAM2 the
-object-score output, boxes and mask prompts, several points per prompt and single-mask output.
+The views come from the caller here; `python -m gaussmart_amd.identify_cli` picks them as the reference does (step 1, the camera
+clustering of gaussmart_amd.camera_select) and runs steps 1 to 5 in one process.
+Not built: crop layers, min_mask_region_area, and for SAM2 the object-score output, boxes and mask prompts, several points per
+prompt and single-mask output.
 """
 import argparse
 import json
@@ -30,6 +32,35 @@ import sys
 import numpy as np
 
 from . import sam as S
+
+
+def make_generator(args):
+    """(generator, weights) for parsed arguments sam_checkpoint, sam2, model_type, host, decoder, device, points_per_side,
+    pred_iou_thresh and stability_score_thresh (this command's and gaussmart_amd.identify_cli's)."""
+    if args.model_type is not None and (args.model_type in ("vit_h", "vit_l", "vit_b")) == args.sam2:
+        print(f"sam_cli: --model_type {args.model_type} does not go with {'--sam2' if args.sam2 else 'SAM (no --sam2)'}", file=sys.stderr)
+        raise SystemExit(2)
+    if args.sam2:
+        from . import sam2 as S2
+        weights = S2.load_sam2_weights(args.sam_checkpoint)
+        if args.model_type is not None:
+            want, have = S2.Sam2Config.preset(args.model_type), weights.config
+            if (want.embed_dim, want.num_heads, tuple(want.blocks_per_stage)) != (have.embed_dim, have.num_heads, tuple(have.blocks_per_stage)):
+                print(f"sam_cli: {args.sam_checkpoint} is not a {args.model_type} (embed {have.embed_dim}, blocks {tuple(have.blocks_per_stage)})",
+                      file=sys.stderr)
+                raise SystemExit(2)
+    else:
+        weights = S.load_sam_weights(args.sam_checkpoint)
+        if args.model_type is not None:
+            want, have = S.SamConfig.preset(args.model_type), weights.config
+            if (want.hidden_size, want.num_hidden_layers, want.num_attention_heads) != (have.hidden_size, have.num_hidden_layers, have.num_attention_heads):
+                print(f"sam_cli: {args.sam_checkpoint} is not a {args.model_type} (hidden {have.hidden_size}, {have.num_hidden_layers} layers)",
+                      file=sys.stderr)
+                raise SystemExit(2)
+    gen = (S2.Sam2MaskGenerator if args.sam2 else S.SamMaskGenerator)(
+        weights, points_per_side=args.points_per_side, pred_iou_thresh=args.pred_iou_thresh,
+        stability_score_thresh=args.stability_score_thresh, host=args.host, device=args.device, decoder=args.decoder)
+    return gen, weights
 
 
 def main(argv=None):
@@ -59,29 +90,7 @@ def main(argv=None):
     if bad:
         print(f"sam_cli: views {bad} are outside the {len(files)} images of {image_dir}", file=sys.stderr)
         raise SystemExit(2)
-    if args.model_type is not None and (args.model_type in ("vit_h", "vit_l", "vit_b")) == args.sam2:
-        print(f"sam_cli: --model_type {args.model_type} does not go with {'--sam2' if args.sam2 else 'SAM (no --sam2)'}", file=sys.stderr)
-        raise SystemExit(2)
-    if args.sam2:
-        from . import sam2 as S2
-        weights = S2.load_sam2_weights(args.sam_checkpoint)
-        if args.model_type is not None:
-            want, have = S2.Sam2Config.preset(args.model_type), weights.config
-            if (want.embed_dim, want.num_heads, tuple(want.blocks_per_stage)) != (have.embed_dim, have.num_heads, tuple(have.blocks_per_stage)):
-                print(f"sam_cli: {args.sam_checkpoint} is not a {args.model_type} (embed {have.embed_dim}, blocks {tuple(have.blocks_per_stage)})",
-                      file=sys.stderr)
-                raise SystemExit(2)
-    else:
-        weights = S.load_sam_weights(args.sam_checkpoint)
-        if args.model_type is not None:
-            want, have = S.SamConfig.preset(args.model_type), weights.config
-            if (want.hidden_size, want.num_hidden_layers, want.num_attention_heads) != (have.hidden_size, have.num_hidden_layers, have.num_attention_heads):
-                print(f"sam_cli: {args.sam_checkpoint} is not a {args.model_type} (hidden {have.hidden_size}, {have.num_hidden_layers} layers)",
-                      file=sys.stderr)
-                raise SystemExit(2)
-    gen = (S2.Sam2MaskGenerator if args.sam2 else S.SamMaskGenerator)(
-        weights, points_per_side=args.points_per_side, pred_iou_thresh=args.pred_iou_thresh,
-        stability_score_thresh=args.stability_score_thresh, host=args.host, device=args.device, decoder=args.decoder)
+    gen, weights = make_generator(args)
     mask_dir = os.path.join(args.output_path, "segments", "masks")
     copy_dir = os.path.join(args.output_path, "segments", "images")
     os.makedirs(mask_dir, exist_ok=True)

@@ -17,50 +17,8 @@ import sys
 import numpy as np
 
 from . import segment_init as SI
+from .camera_select import NERF_IMG_WH, TYT_FOCAL, TYT_IMG_WH, load_cameras  # noqa: F401  (load_cameras lives there now)
 from .scene_io import read_ply_vertices
-
-NERF_IMG_WH = (1024, 1024)          # identification/camera_loader.py:63
-TYT_IMG_WH = (979, 543)             # :125
-TYT_FOCAL = (501.0, 277.0)          # :127
-
-
-def _intrinsics(fx, fy, cx, cy):
-    return np.array([[fx, 0.0, cx, 0.0], [0.0, fy, cy, 0.0], [0.0, 0.0, 1.0, 0.0], [0.0, 0.0, 0.0, 1.0]])
-
-
-def load_cameras(path, kind):
-    """{view index: camera dict} in the layouts of identification/camera_loader.py."""
-    if kind == "dtu":
-        views = {}
-        with np.load(path) as z:
-            for key in z.files:
-                name, _, idx = key.rpartition("_")
-                if name and idx.isdigit():
-                    views.setdefault(int(idx), {})[name] = z[key]
-        for i, cam in views.items():
-            missing = [k for k in ("world_mat", "camera_mat", "scale_mat") if k not in cam]
-            if missing:
-                raise ValueError(f"{path}: view {i} lacks {', '.join(missing)}")
-        return views
-    data = np.load(path)
-    if data.ndim != 2:
-        raise ValueError(f"{path}: expected a 2-D array of poses, got shape {list(data.shape)}")
-    if kind == "nerf":
-        if data.shape[1] not in (17, 19):
-            raise ValueError(f"{path}: a nerf pose row has 17 or 19 values, got {data.shape[1]}")
-        w, h = NERF_IMG_WH
-        return {i: {"world_mat": np.linalg.inv(row[:16].reshape(4, 4)), "scale_mat": np.eye(4),
-                    "camera_mat": _intrinsics(float(row[16]), float(row[16]), w / 2.0, h / 2.0)} for i, row in enumerate(data)}
-    if data.shape[1] not in (14, 16):
-        raise ValueError(f"{path}: a tyt pose row has 14 or 16 values, got {data.shape[1]}")
-    w, h = TYT_IMG_WH
-    views = {}
-    for i, row in enumerate(data[:data.shape[0] // 2]):
-        c2w = np.eye(4)
-        c2w[:3, :4] = row[:12].reshape(3, 4)
-        views[i] = {"world_mat": np.linalg.inv(c2w), "scale_mat": np.eye(4), "img_size": np.array([w, h]),
-                    "camera_mat": _intrinsics(TYT_FOCAL[0], TYT_FOCAL[1], w / 2.0, h / 2.0)}
-    return views
 
 
 def write_cloud_ply(path, points, colors=None, normals=None):

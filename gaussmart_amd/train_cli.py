@@ -7,7 +7,12 @@ is downloaded): it is logged to MODEL/dino_loss_log.csv and carries no gradient,
 
     python -m gaussmart_amd.train_cli -s <colmap-or-blender-scene> -m <output dir> [--iterations 30000] [--eval]
         [--dino_dir DIR [--lambda_dino 0.05] [--dino_start_iter 3000] [--host]]
+        [--run_segmentation --dataset_type dtu|nerf|tyt --sam_checkpoint FILE_OR_DIR [--skip_camera_clustering] [--sam2] [--clean]]
     torchrun --nproc-per-node 8 -m gaussmart_amd.train_cli -s ... -m ...        # view-parallel
+
+--run_segmentation is the reference's train.py:362-367,380-406: before training, steps 1 to 5 of identification/main.py run in this
+process (gaussmart_amd.identify_cli: view selection, SAM / SAM2 masks, labels) into MODEL/segmentation, and --segmentation_dir is set
+to the result unless one was given.
 """
 import argparse
 import json
@@ -16,6 +21,7 @@ import time
 
 import torch
 
+from . import identify_cli
 from .gaussian_model import GaussianModel
 from .gaussian_renderer import render
 from .losses import psnr
@@ -53,6 +59,10 @@ def main(argv=None):
     ap.add_argument("--segmentation_dir", default=None,
                     help="directory with segment_indices.npy / mask_areas.npy (gaussmart_amd.segment_cli's OUT/segments/point_cloud): "
                          "the initial cloud is augmented per segment")
+    ap.add_argument("--run_segmentation", action="store_true",
+                    help="run gaussmart_amd.identify_cli on the scene first (into MODEL/segmentation) and train from its labels")
+    ap.add_argument("--dataset_type", choices=("dtu", "nerf", "tyt"), default="tyt", help="with --run_segmentation: the scan's layout")
+    identify_cli.add_arguments(ap)
     ap.add_argument("--uniform_upsampling", action="store_true",
                     help="without mask areas: augment the initial cloud as one segment")
     ap.add_argument("--dino_dir", default=None,
@@ -72,6 +82,18 @@ def main(argv=None):
     if world > 1:
         dist.init_process_group("nccl", device_id=dev)
     torch.manual_seed(0)
+
+    if args.run_segmentation:
+        seg_out = os.path.join(args.model_path, "segmentation")
+        if rank == 0:
+            seg_args = ["-s", args.source_path, "-o", seg_out, "-t", args.dataset_type, "--device", str(dev), "--overwrite"]
+            seg_args += [f"--{name}" for name in ("skip_camera_clustering", "sam2", "clean") if getattr(args, name)]
+            seg_args += ["--sam_checkpoint", args.sam_checkpoint] if args.sam_checkpoint else []
+            identify_cli.main(seg_args)
+        if world > 1:
+            dist.barrier()
+        if args.segmentation_dir is None:
+            args.segmentation_dir = os.path.join(seg_out, "segments", "point_cloud")
 
     opt = OptimizationParams(iterations=args.iterations, lambda_normal=args.lambda_normal, lambda_dist=args.lambda_dist)
     pipe = PipelineParams(depth_ratio=args.depth_ratio)

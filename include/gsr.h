@@ -52,7 +52,8 @@ extern "C" {
                                     prompt encoder and mask decoder (gsr_sam_dec_*, gsr_sam_decode), with SAM2's image
                                     encoder (GsrSam2Config, gsr_sam2_*) and with SAM2's prompt encoder and mask decoder
                                     (gsr_sam2_dec_*, gsr_sam2_decode), and with the gsr_buffer_field names "tile_rect" and
-                                    "color_jac": additions only, no existing struct or signature changed */
+                                    "color_jac", and with the camera clustering of the view selection (gsr_cam_lloyd):
+                                    additions only, no existing struct or signature changed */
 #define GSR_MAX_CHANNELS 64   /* widest per-pixel payload of gsr_forward / gsr_backward */
 
 typedef void* gsr_stream_t; /* hipStream_t */
@@ -1554,6 +1555,47 @@ size_t gsr_sam2_workspace_bytes(const GsrSam2Config* cfg);
 int32_t gsr_sam2_num_weights(int32_t total_blocks);
 int32_t gsr_sam2_encode(const GsrSam2Config* cfg, const void* const* weights_host, int32_t n_weights, const float* pixel_values,
                         void* ws, size_t ws_bytes, float* out0, float* out1, float* out2, gsr_stream_t stream);
+
+/* ---------------------------------------------------------------- camera clustering (step 1 of identification/main.py)
+ * The reference picks the views it segments by k-means over the camera centres (identification/clustering_cameras.py):
+ * scikit-learn's KMeans for every k from 3 to 15 with n_init = 10, 130 independent fits of at most a few hundred points in three
+ * dimensions.  The initial centres are drawn on the host from scikit-learn's random stream (gaussmart_amd/camera_select.py);
+ * the Lloyd iterations of ALL fits are one launch of gsr_cam_lloyd, one workgroup per fit, the points in LDS.  fp64 throughout,
+ * no fused multiply-add, and every sum in a stated order, so that camera_select.lloyd_batch_host (numpy) gives the same bits in
+ * labels, centres, inertia, n_iter and status.
+ *   CK_LLOYD   x f64 [n,3] (the caller has subtracted the mean), per fit f: k_f in 1 .. GSR_CK_KMAX and centres0[f] f64
+ *              [GSR_CK_KMAX,3] (rows >= k_f are not read).  d(i, c) = ((x_i0 - c_0)^2 + (x_i1 - c_1)^2) + (x_i2 - c_2)^2, the
+ *              three squares summed left to right.  One iteration, from the centres C:
+ *                label_i = the lowest c at which d(i, c) is smallest (a later c wins only with a strictly smaller d);
+ *                for every cluster c and every chunk of GSR_CK_CHUNK consecutive indices (chunk j holds indices 64 j ..
+ *                  min(n, 64 j + 64) - 1): the sums of x_0, x_1, x_2 and the member count over the chunk's members of c, each
+ *                  started at +0 and added in ascending index; then, started at +0 again, the chunks added in ascending j;
+ *                a cluster without members: status = 1 and the fit ENDS with this iteration's labels, the centres C unmoved,
+ *                  n_iter counting this iteration (the caller redoes the fit on the host, which relocates such a centre as
+ *                  scikit-learn does);
+ *                new_c = sum / count, one division per axis; shift = sum over c ascending, from +0, of d(new_c, C_c);
+ *                the centres become the new ones; then, in this order: labels equal to the previous iteration's (the first
+ *                  iteration compares with "none") -> stop (strict convergence); shift <= tol -> stop; max_iter iterations
+ *                  done -> stop.  After either of the last two stops the labels are computed once more against the final
+ *                  centres.
+ *              inertia = per chunk, from +0 in ascending index, the sum of d(i, centre of label_i); then the chunks from +0 in
+ *              ascending order.  n_iter = iterations run.  This is scikit-learn 1.7's _kmeans_single_lloyd with the distances
+ *              written out instead of expanded, without its relocation of empty clusters and with the shift's square roots
+ *              (squared again there) left out.
+ * Outputs per fit: labels i32 [n], centres f64 [GSR_CK_KMAX,3] (rows >= k_f are 0), inertia f64, n_iter i32, status i32 (0 done,
+ * 1 a cluster lost all members, 2 k_f outside 1 .. GSR_CK_KMAX: labels -1, nothing iterated).  k, like every array, is DEVICE
+ * memory; the caller's stream, nothing synchronises.  No workspace is needed up to the cap (gsr_cam_lloyd_workspace_bytes is 0
+ * and ws may be NULL); the arguments stay so that a route through global memory would not change the signature.
+ * Refused before anything is launched, with a message: n < 1, n_fits < 0, max_iter < 1, tol < 0 or NaN, a null array (all
+ * GSR_E_INVALID); n > GSR_CK_MAX_CAMERAS (GSR_E_UNSUPPORTED; 24 bytes of LDS per point, 96 KiB of the CU's 160 KiB at the cap,
+ * beside 32 KiB of chunk sums: the message names the host route, camera_select.lloyd_batch_host). */
+#define GSR_CK_KMAX 16
+#define GSR_CK_CHUNK 64
+#define GSR_CK_MAX_CAMERAS 4096
+size_t gsr_cam_lloyd_workspace_bytes(int32_t n, int32_t n_fits);
+int32_t gsr_cam_lloyd(const double* x, int32_t n, const double* centres0, const int32_t* k, int32_t n_fits, double tol,
+                      int32_t max_iter, int32_t* labels, double* centres, double* inertia, int32_t* n_iter, int32_t* status,
+                      void* ws, size_t ws_bytes, gsr_stream_t stream);
 
 /* Opt-in per-kernel timing with HIP events on the launch stream (bench.py's roofline figures).
  * `mask`: bit k enables kernel k in the order of the names below (-1 = all, 0 = off); timing only
