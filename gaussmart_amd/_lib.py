@@ -46,6 +46,7 @@ GSR_FLAG_AABB_GRAD_CUTOFF1 = 512  # recalled quirk 3: centre gradient chained wi
 GSR_FLAG_NO_DIST_MEDIAN = 4096   # forward + backward: distortion and median depth are not consumed (lambda_dist = 0, depth_ratio = 0)
 GSR_FLAG_COLOR_ONLY = 2048       # forward: allmap is not consumed (no regularizer active): not accumulated, not written
 GSR_FLAG_NO_SURFACE_GRAD = 1024  # backward: dL/dallmap is identically zero (no regularizer active): 4-part-record kernel
+GSR_FLAG_TIGHT_TILES = 8192      # forward: tile rects clipped to the tiles the alpha box reaches (same results, shorter lists)
 GSR_FLAG_FACTORED_SH_GRAD = 32   # backward writes the masked colour gradient [N,3] instead of the SH gradient arrays
 
 KERNEL_NAMES = ("preprocess_fwd", "sort_hist", "sort_scatter", "scan", "emit_instances",

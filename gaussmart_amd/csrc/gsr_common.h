@@ -244,6 +244,19 @@ __device__ __forceinline__ bool gsr_rect_overlaps_quad(uint32_t wx, uint32_t wy,
     const int y0 = (int)(short)(wy & 0xFFFFu), y1 = (int)(short)(wy >> 16);
     return x0 <= bx0 + 7 && x1 >= bx0 && y0 <= by0 + 7 && y1 >= by0;
 }
+// GSR_FLAG_TIGHT_TILES: clip the tile rect [x0, x1) x [y0, y1) to the tiles of which at least one 8x8 quad passes
+// gsr_rect_overlaps_quad for the cull rect (wx, wy).  The test is separable and a tile's two quads per axis are adjacent,
+// so along x the tile tx passes iff rx0 <= 16 tx + 15 and rx1 >= 16 tx, i.e. floor(rx0 / 16) <= tx <= floor(rx1 / 16)
+// (arithmetic shifts: floor for negative ends too); "never culled" [-32768, 32767] keeps everything, "cannot reach
+// 1/255" (x0 = 32767 > x1 = -32768) keeps nothing.  Returns the number of tiles left.
+__device__ __forceinline__ int gsr_clip_tile_rect(uint32_t wx, uint32_t wy, int& x0, int& y0, int& x1, int& y1) {
+    static_assert(GSR_TILE == 16, "two 8-pixel quads per tile and axis");
+    const int rx0 = (int)(short)(wx & 0xFFFFu), rx1 = (int)(short)(wx >> 16);
+    const int ry0 = (int)(short)(wy & 0xFFFFu), ry1 = (int)(short)(wy >> 16);
+    x0 = max(x0, rx0 >> 4); x1 = min(x1, (rx1 >> 4) + 1);
+    y0 = max(y0, ry0 >> 4); y1 = min(y1, (ry1 >> 4) + 1);
+    return (x1 > x0 && y1 > y0) ? (x1 - x0) * (y1 - y0) : 0;
+}
 // Second, tighter stage of the quad cull (render_fwd): can the splat reach alpha >= 1/255 anywhere in the pixel box
 // [bx0, bx0+7] x [by0, by0+7]?  {alpha >= 1/255} = {rho3d <= c2} u {rho2d <= c2}, c2 = 2 ln(255 opa) (inflated like the
 // cull rect of preprocess_fwd):

@@ -22,6 +22,7 @@ struct PreParams {
     float mod;
     const float* view; const float* proj; const float* campos;
     bool raw;
+    bool tight;      // GSR_FLAG_TIGHT_TILES: the tile rect is clipped to the tiles the alpha box reaches
     const float* means; const float* shs; const float* shs_rest; const float* colors; const float* opac;
     const float* scales; const float* rots; const float* tprecomp;
     float* splat; uint32_t* clamped; uint32_t* tiles; uint2* rect; uint32_t* dkey; int32_t* radii;
@@ -148,7 +149,7 @@ __device__ __forceinline__ uint32_t preprocess_one(const PreParams& p, const int
 
     int x0, y0, x1, y1;
     gsr_tile_rect(cx, cy, (int)radius, p.gx, p.gy, x0, y0, x1, y1);
-    const int ntiles = (x1 - x0) * (y1 - y0);
+    int ntiles = (x1 - x0) * (y1 - y0);
     if (ntiles == 0) return 0u;
 
     uint32_t clamp_bits = 0;
@@ -200,6 +201,14 @@ __device__ __forceinline__ uint32_t preprocess_one(const PreParams& p, const int
                 }
             }
         }
+    }
+
+    // GSR_FLAG_TIGHT_TILES: a tile none of whose four quads passes the compositing kernels' rect cull is never listed.
+    // Integer work on the finished box; a Gaussian left without tiles keeps its record and its radius (it is visible to
+    // the colour pass, the backward and the densification statistics as before) and emits nothing.
+    if (p.tight) {
+        ntiles = gsr_clip_tile_rect(rect_x, rect_y, x0, y0, x1, y1);
+        if (ntiles == 0) { x0 = 0; y0 = 0; x1 = 0; y1 = 0; }
     }
 
     float4* rec = reinterpret_cast<float4*>(p.splat + (size_t)idx * GSR_SPLAT_FLOATS);
@@ -390,6 +399,7 @@ static void fill_pre_params(PreParams& p, const GsrView& v, const GsrGaussians& 
     p.deg = v.sh_degree; p.M = v.sh_coeffs; p.mod = v.scale_modifier;
     p.view = v.viewmatrix; p.proj = v.projmatrix; p.campos = v.campos;
     p.raw = (v.flags & (uint32_t)GSR_FLAG_RAW_PARAMS) != 0;
+    p.tight = (v.flags & (uint32_t)GSR_FLAG_TIGHT_TILES) != 0;
     p.means = g.means3D; p.shs = g.shs; p.shs_rest = g.shs_rest; p.colors = (v.channels == 3 && !(v.flags & (uint32_t)GSR_FLAG_COLOR_CACHED)) ? g.colors_precomp : nullptr /* wide payloads are read by id in K6/K7; a colour cache is applied where the colour pass would run */; p.opac = g.opacities;
     p.scales = g.scales; p.rots = g.rotations; p.tprecomp = g.transmat_precomp;
     p.splat = splat; p.clamped = clamped; p.tiles = tiles_touched; p.rect = tile_rect; p.dkey = depth_key; p.radii = radii;

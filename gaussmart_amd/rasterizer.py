@@ -480,7 +480,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xyz, means2D, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, raster_settings, flags,
-                color_cache=None, state=None, color_only=False, no_dist_median=False):
+                color_cache=None, state=None, color_only=False, no_dist_median=False, tight_tiles=False):
         device = xyz.device
         rs = raster_settings
         tensors, g, M = _pack_raw(xyz, f_dc, f_rest, opacity_raw, scaling_raw, rotation_raw, color_cache)
@@ -491,6 +491,8 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
             flags |= _lib.GSR_FLAG_NO_DIST_MEDIAN
         if color_cache is not None:       # the SH colour of this view was left by the optimiser step (FusedAdam.color_cache)
             flags |= _lib.GSR_FLAG_COLOR_CACHED
+        if tight_tiles:                   # list only the tiles a splat's alpha box reaches (the lists are not the reference's then)
+            flags |= _lib.GSR_FLAG_TIGHT_TILES
         pending = state.pop_pending() if state is not None else None
         hook = color_stream = None
         if pending is not None:
@@ -551,7 +553,7 @@ class _RasterizeGaussiansRaw(torch.autograd.Function):
         if factored:
             ctx.state.color_grad = ColorGradRecord(flat, flat[:n_head], record, N, ctx.sh_coeffs,
                                                    ctx.raster_settings.sh_degree, xyz)
-        return d_xyz, d_2d, d_dc, d_rest, d_op, d_sc, d_rot, None, None, None, None, None, None
+        return d_xyz, d_2d, d_dc, d_rest, d_op, d_sc, d_rot, None, None, None, None, None, None, None
 
 
 def _wants_grad(*tensors):
@@ -569,7 +571,7 @@ def _forward_only(rs, g, sh_coeffs, flags, device):
 
 def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw, rotation_raw,
                             raster_settings, flags=None, factored_sh_grad=False, color_cache=None, state=None, color_only=False,
-                            no_dist_median=False):
+                            no_dist_median=False, tight_tiles=False):
     """(color, radii, allmap) from the model's raw parameter tensors; activations fused in-kernel.
     `state`: the model's RasterState (hand-over slots with the optimiser step); None for a caller that has neither a
     pipelined update in flight nor a factored gradient to receive.
@@ -579,7 +581,9 @@ def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_ra
     `color_only`: the caller consumes the colour image alone (a training step with no regularizer active): allmap comes back
     as None -- the forward neither accumulates nor writes it (GSR_FLAG_COLOR_ONLY), the backward runs without its terms.
     `no_dist_median`: the caller consumes neither the distortion nor the median-depth channel of allmap (lambda_dist = 0 and
-    depth_ratio = 0, the reference's defaults): both come back as zeros (GSR_FLAG_NO_DIST_MEDIAN)."""
+    depth_ratio = 0, the reference's defaults): both come back as zeros (GSR_FLAG_NO_DIST_MEDIAN).
+    `tight_tiles`: a training forward lists a splat only in the tiles its alpha box reaches (GSR_FLAG_TIGHT_TILES): same
+    images and gradients bit for bit, shorter tile lists; the inference path keeps the reference's lists."""
     flags = DEFAULT_FLAGS if flags is None else flags
     if factored_sh_grad and state is None:
         raise ValueError("factored_sh_grad needs state=RasterState(): the backward leaves its colour-gradient record there")
@@ -594,7 +598,7 @@ def rasterize_gaussians_raw(xyz, means2D, features_dc, features_rest, opacity_ra
     color, radii, allmap = _RasterizeGaussiansRaw.apply(xyz, means2D, features_dc, features_rest, opacity_raw, scaling_raw,
                                                         rotation_raw, raster_settings, flags,
                                                         color_cache if factored_sh_grad else None, state, bool(color_only),
-                                                        bool(no_dist_median))
+                                                        bool(no_dist_median), bool(tight_tiles))
     return color, radii, (None if color_only else allmap)
 
 

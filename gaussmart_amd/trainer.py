@@ -118,7 +118,8 @@ def training_step(gaussians, viewpoint_cam, gt_image, opt, pipe, background, ite
         # the distortion and median-depth channels: the forward does not accumulate them
         no_dm = not (opt.lambda_dist > 0.0 and iteration > 3000) and float(getattr(pipe, "depth_ratio", 0.0)) == 0.0
         render_pkg = render_fn(viewpoint_cam, gaussians, pipe, background, surface_maps=False, factored_sh_grad=True,
-                               color_only=no_reg and lean, no_dist_median=no_dm and lean)
+                               color_only=no_reg and lean, no_dist_median=no_dm and lean,
+                               tight_tiles=bool(getattr(pipe, "tight_tile_rects", True)))
     else:
         render_pkg = render_fn(viewpoint_cam, gaussians, pipe, background,
                                surface_maps=(not on_device) or bool(getattr(pipe, "reference_objective", False)))

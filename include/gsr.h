@@ -116,6 +116,14 @@ enum {
                                        --lambda_normal 0 --lambda_dist 0) and the first 7,000 iterations of every run
                                        (train.py:132-133).  The compositing backward then runs without the surface terms on a
                                        16-float staged record; same gradients as without the flag, bit for bit */
+    GSR_FLAG_TIGHT_TILES = 8192,    /* gsr_forward: a Gaussian's tile rect is the reference's (the square of its major 3-sigma
+                                       extent) INTERSECTED with the tiles its alpha box reaches -- the conservative pixel box of
+                                       {alpha >= 1/255} in the splat record, the one the compositing kernels cull every 8x8 quad
+                                       with.  A tile is kept iff at least one of its four quads passes that cull, so only list
+                                       entries that every wave of their tile rejects are never created: colour, allmap, radii
+                                       and every gradient are those of the default lists bit for bit.  tiles_touched, tile_rect,
+                                       point_list, ranges and num_rendered are NOT the reference's any more (a Gaussian may keep
+                                       radii > 0 and no tile at all); callers that compare lists leave the flag off */
     GSR_FLAG_FACTORED_SH_GRAD = 32  /* gsr_backward with `shs`: the SH gradient of one view is the outer product
                                        basis_k(dir) x g_c of the 16 basis values of the view direction and the
                                        clamp-masked colour gradient g = dL/drgb (utils/sh_utils.py:57-112 is linear in
